@@ -19,10 +19,17 @@ warm-up step, the last one enqueues the sampling of step K + 1).
 `python bench.py --gpus N` without a launcher starts the N ranks itself (re-executes under torch.distributed.run,
 the reference's counterpart is nerfstudio's mp.spawn around fruit_pipeline.py:116-118) and fails unless N ranks run.
 
-Extra objects in the JSON line:  roofline (dominant entry point among the HBM- / MFMA-bound ones, chosen by its time
-over the timed window itself, HIP events on the stream of the launch, every 10th step, streams serialised on those steps), cpu_baseline (the oracle's train step on the host cores, rank 0, bounded sample),
-breakdown_ms (per entry point, from a short instrumented pass after the timed region), quality (PSNR / IoU on
-held-out views after --quality-steps more steps).
+A plain run sets up, warms up, times the K steps and prints the line; its only extra object is roofline (dominant entry
+point among the HBM- / MFMA-bound ones, chosen by its time over the timed window itself, HIP events on the stream of the
+launch, every 10th step, streams serialised on those steps).  Everything that takes runs of its own comes with --full:
+value_fp32_arithmetic (the same window in fp32 MFMA chains), cpu_baseline (the oracle's train step on the host cores,
+rank 0, bounded sample), breakdown_ms (per entry point, from a short instrumented pass after the timed region), quality
+(PSNR / IoU on held-out views after --quality-steps more steps, checksum gates), secondary (eval / export rates, other
+streams / arithmetic / plugin API, fruit count, fruit_nerf_big).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): the losses and metrics it
+returned, the camera pose corrections and a fixed, seeded sample of the parameters after its optimiser step.  Inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -497,11 +504,33 @@ def _group_report(dev) -> dict:
     return {"world_size": world, "backend": str(dist.get_backend()), "devices": len(set(seen))}
 
 
+DUMP_PARAMETER_SAMPLE = 1 << 22        # 16 MB of the 19.4 M fp32 parameters
+
+
+def dump_outputs(path, run, ld, md) -> None:
+    """--dump-outputs: the (loss_dict, metrics_dict) the last timed step returned, the pose corrections and a seeded
+    sample (fixed by the arena's size) of the parameter arena it left, one float32 .npy per name."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().reshape(-1).cpu().numpy() for k, v in {**ld, **md}.items()}
+    params = run.model.arena().params.detach().cpu().numpy()
+    idx = np.random.default_rng(0).choice(params.size, min(params.size, DUMP_PARAMETER_SAMPLE), replace=False)
+    arrays["parameters_sample"] = params[np.sort(idx)]
+    if run.camera is not None:
+        arrays["camera_pose_adjustment"] = run.camera[0].pose_adjustment.detach().float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a.astype(np.float32))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline window: fp32-arithmetic window, per-entry-point breakdown, "
+                         "quality gate, secondary rates, fruit_nerf_big, CPU baseline (the --no-* options below prune it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--quality-steps", type=int, default=-1,
                     help="training steps before the held-out PSNR / IoU / fruit-count gate; -1 = up to the reference's "
                          "max_num_iterations (30 000 for fruit_nerf, fruit_nerf_config.py:32; 3 000 for the bigger methods)")
@@ -632,13 +661,15 @@ def main() -> None:
             dist.barrier()
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, run, ld, md)
 
     # ---- roofline of the dominant entry point (and of the dominant one bound by the other roofline) --------------------
     roofline, roofline_other = rooflines_of(run, recs, n_prof, dist_on, pmc, field_records)
     # the SAME window (fresh model, same seeds, warm-up, steps and event-timed steps) in the strictly-fp32 arithmetic
     # (v_mfma_f32_16x16x4_f32 chains, forward and backward): the reference's own arithmetic, next to the headline's
     value_fp32 = None
-    if world == 1 and args.mlp_precision != "fp32" and not dist_on:
+    if args.full and world == 1 and args.mlp_precision != "fp32" and not dist_on:
         r32 = MethodRun(args.method, "fp32", args.camera_optimizer, dev, rank, world, data, train_ids, len(i_train))
         for _ in range(args.warmup):
             r32.one_step()
@@ -656,7 +687,7 @@ def main() -> None:
 
     # ---- per-entry-point breakdown (short instrumented pass, outside the timed region; N = 1 only: the
     # other ranks have left, so no collective may run here) ------------------------------------------------
-    nb = 12 if world == 1 else 0
+    nb = 12 if args.full and world == 1 else 0
     L.profile_enable(True)
     saved_serialize, _training.SERIALIZE_STREAMS = _training.SERIALIZE_STREAMS, True   # nothing next to a bracketed launch
     for _ in range(nb):
@@ -697,7 +728,7 @@ def main() -> None:
         return round(float(np.mean(psnrs)), 3), round(inter / max(union, 1.0), 4)
 
     quality = None
-    if not args.no_quality and world == 1:
+    if args.full and not args.no_quality and world == 1:
         # the reference trains fruit_nerf for 30 000 iterations (fruit_nerf_config.py:32); the bigger methods (100 000
         # iterations there) get a bounded 3 000-step look
         target = run.step_idx + args.quality_steps if args.quality_steps >= 0 else \
@@ -774,7 +805,7 @@ def main() -> None:
 
     # ---- secondary metrics: full-image eval rays/s and volume-export samples/s, trained weights ----
     secondary = None
-    if not args.no_quality and world == 1:
+    if args.full and not args.no_quality and world == 1:
         import copy
         from fruitnerf_amd.data.fruit_datamanager import ExportDataManager
         from fruitnerf_amd.export.exporter_utils import sample_volume
@@ -966,9 +997,9 @@ def main() -> None:
         model.train()
 
     # ---- fruit_nerf_big (BASELINE configs 3, 5) on the same scene: a short window of the bigger method, so that its
-    # throughput and both roofline fractions are in the default line (8192 rays, 512/256/128 samples, T = 2^21, RAdam)
+    # throughput and both roofline fractions are in the --full line (8192 rays, 512/256/128 samples, T = 2^21, RAdam)
     big = None
-    if args.method == "fruit_nerf" and not args.no_big and not args.no_quality and world == 1:
+    if args.full and args.method == "fruit_nerf" and not args.no_big and not args.no_quality and world == 1:
         del emodel, pipe, sets
         torch.cuda.empty_cache()
         rb_ = MethodRun("fruit_nerf_big", args.mlp_precision, args.camera_optimizer, dev, rank, world, data, train_ids,
@@ -1023,7 +1054,7 @@ def main() -> None:
 
     # ---- CPU baseline: the oracle's training step on the host cores -------------------------------------------------
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from oracle import fruit_oracle as fo
         from oracle import ns_torch as ns
         # BASELINE.md §2 protocol: the method's batch size, oracle/ PyTorch-CPU fp32, median of the timed steps.

@@ -33,7 +33,7 @@ def pytest_sessionstart(session):
 _FIRST = ("test_golden", "test_gpu_forward_parity", "test_gpu_reference_pins", "test_gpu_properties",
           "test_gpu_training_parity", "test_gpu_trained_state", "test_gpu_bf16", "test_gpu_modes", "test_gpu_cloud",
           "test_gpu_determinism")
-_LAST = ("test_gpu_sharding", "test_gpu_distributed")
+_LAST = ("test_gpu_sharding", "test_gpu_distributed", "test_gpu_bench")
 
 
 def pytest_collection_modifyitems(session, config, items):

@@ -12,8 +12,7 @@ reference's OWN code (/root/reference, read at generation time only):
     process wrote it and once `module.`-prefixed, as DDP wrote it (`fruit_pipeline.py:116`).
 
 The fixture keeps the key list, the shapes and which load variants went through; tests/test_reference_pins.py checks the
-product's key set against it both ways and repeats the load with the fixture's keys (and, where /root/reference exists,
-runs `run_reference_load_pipeline()` below live).
+product's key set against it both ways and repeats the load with the fixture's keys.
 
     python tests/golden/make_reference_pipeline_golden.py"""
 import os

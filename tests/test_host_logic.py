@@ -385,6 +385,35 @@ def test_bench_roofline_bookkeeping():
     assert l2["bound"] == "l2" and l2["peak"] == bench.L2_PEAK_GBS and l2["frac"] < 1.0
 
 
+def test_bench_dump_outputs_writes_float32_files_under_64_mb(tmp_path):
+    """--dump-outputs: one float32 .npy per returned loss / metric, the pose corrections and a parameter sample that is
+    the same on every call (fixed seed, sorted indices) and keeps the directory under 64 MB."""
+    import importlib.util
+    import os
+    import types
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    params = torch.arange(1 << 24, dtype=torch.float32)              # every entry distinct (exact in float32)
+    pose = types.SimpleNamespace(pose_adjustment=torch.ones(90, 6, dtype=torch.float64))
+    run = types.SimpleNamespace(model=types.SimpleNamespace(arena=lambda: types.SimpleNamespace(params=params)),
+                                camera=(pose, None, None))
+    ld = {"rgb_loss": torch.tensor(0.5), "semantics_loss": torch.tensor(0.25), "interlevel_loss": torch.tensor(0.125)}
+    md = {"psnr": torch.tensor(30.0), "distortion": torch.tensor(1e-3)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), run, ld, md)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(f"{k}.npy" for k in [*ld, *md, "parameters_sample", "camera_pose_adjustment"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b), f
+    s = np.load(tmp_path / "a" / "parameters_sample.npy")
+    assert s.size == bench.DUMP_PARAMETER_SAMPLE and np.all(np.diff(s) > 0)      # distinct entries, in arena order
+    assert float(np.load(tmp_path / "a" / "rgb_loss.npy")[0]) == 0.5
+
+
 def test_sampler_look_ahead_is_the_schedule():
     """ProposalNetworkSampler.updated_after(step) / FruitModel.anneal_at(step + 1) — what FruitModel.sample_ahead assumes
     about the NEXT iteration while the current one is finishing — against what that iteration then sees

@@ -404,24 +404,3 @@ def test_update_to_step_invalidates_what_was_sampled_ahead():
     before = model.lookahead_version()
     model.update_to_step(10)
     assert model.lookahead_version() != before
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/fruit_nerf"), reason="needs the reference sources (build box only)")
-@pytest.mark.parametrize("prefix", ["", "module."])
-def test_reference_load_pipeline_runs_on_the_product_model(prefix):
-    """The reference's OWN FruitPipeline.load_pipeline, executed live on a pipeline whose `_model` is the product model
-    (in a subprocess: the stub import machinery it needs must not leak into this test session)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys, torch; sys.path.insert(0, %r)\n"
-            "from tests.golden import make_reference_pipeline_golden as m\n"
-            "ref = m.reference_model().state_dict()\n"
-            "pipe, loaded = m.run_reference_load_pipeline(%r, ref)\n"
-            "got = pipe._model.state_dict()\n"
-            "assert set(got) == set(ref), (set(got) ^ set(ref))\n"
-            "assert all(torch.equal(got[k], v) for k, v in ref.items())\n"
-            "print('loaded', len(ref))\n" % (root, prefix))
-    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr[-2000:]
-    assert "loaded 42" in res.stdout

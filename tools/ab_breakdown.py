@@ -1,4 +1,4 @@
-"""Per-entry-point A/B of two bench lines (stdin: two JSON lines, prev then curr)."""
+"""Per-entry-point A/B of two `bench.py --full` lines (stdin: two JSON lines, prev then curr)."""
 import json, sys
 a, b = [json.loads(l) for l in sys.stdin if l.startswith("{")][:2]
 print("step", a["ms_per_step"], b["ms_per_step"])

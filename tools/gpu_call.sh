@@ -4,7 +4,7 @@
 # Every leg writes gpurun_out/<tag>/<leg name>.log (merged back by gpurun) and prints one summary line.  Legs:
 #   tests[=<pytest args>]     pytest -m gpu (default: the whole suite, -x)
 #   smoke                     __graft_entry__.build() + smoke()
-#   bench[=<bench.py args>]   python bench.py <args>            (log name: bench, bench2, ... in order of appearance)
+#   bench[=<bench.py args>]   python bench.py --full <args>     (log name: bench, bench2, ... in order of appearance)
 #   driver                    the driver's command: bench.py --gpus 1 --steps 20 --warmup 5
 #   ab=<ENV=a|b>[,<bench args>]   tools/ab_quick.py-style same-process A/B is python-side; this leg runs bench.py twice with ENV
 #                             set to a, then b, on the quick settings (--no-cpu-baseline --no-quality), alternating 2x
@@ -36,7 +36,7 @@ for leg in "$@"; do
       python tools/bench_line.py $O/driver.log;;
     bench)
       n=bench$nb; nb=$((nb+1))
-      python bench.py $arg > $O/$n.log 2>$O/$n.err; echo "[bench $arg] rc $? -> $n.log"
+      python bench.py --full $arg > $O/$n.log 2>$O/$n.err; echo "[bench --full $arg] rc $? -> $n.log"
       python tools/bench_line.py $O/$n.log;;
     ab)
       envs=${arg%%,*}; extra=""; [[ "$arg" == *,* ]] && extra=${arg#*,}

@@ -168,8 +168,8 @@ json.dump({'source': f'profiles/{tag}_kernel_trace_pmc.md: rocprofv3 --pmc FETCH
 out.append('\n## Bench lines of the same build (un-profiled)\n')
 out.append('| command | rays/s | ms/step | `roofline` | `roofline_other_bound` |')
 out.append('|---|---|---|---|---|')
-for fn, cmd in (('bench_fruit_nerf.log', 'python bench.py'), ('bench_fruit_nerf_fp32.log', 'python bench.py --mlp-precision fp32'),
-                ('bench_fruit_nerf_big.log', 'python bench.py --method fruit_nerf_big')):
+for fn, cmd in (('bench_fruit_nerf.log', 'python bench.py --full'), ('bench_fruit_nerf_fp32.log', 'python bench.py --full --mlp-precision fp32'),
+                ('bench_fruit_nerf_big.log', 'python bench.py --full --method fruit_nerf_big')):
     import os
     if not os.path.exists(base + fn):
         continue
