@@ -3,7 +3,8 @@ FruitNeRF's hot path executes (TEST INFRASTRUCTURE, parity unpinned: see oracle/
 
 nerfstudio is NOT in /root/reference (pinned dependency, /root/reference/pyproject.toml:10) and
 not installable here, so every class below restates the published 0.3.2 algorithm; the reference
-call site that reaches it is cited instead.  Pure PyTorch, CPU, fp32.
+call site that reaches it is cited instead.  Pure PyTorch, CPU, fp32 (dtype-preserving: the ray, sampling, rendering
+and loss pieces evaluate float64 inputs in float64, the high-precision reference of the per-ray kernel tests).
 """
 from __future__ import annotations
 
@@ -56,7 +57,8 @@ class RaySamples:
         alphas = 1 - torch.exp(-delta_density)
         transmittance = torch.cumsum(delta_density[..., :-1, :], dim=-2)
         transmittance = torch.cat(
-            [torch.zeros((*transmittance.shape[:1], 1, 1), device=densities.device), transmittance], dim=-2
+            [torch.zeros((*transmittance.shape[:1], 1, 1), dtype=delta_density.dtype, device=densities.device),
+             transmittance], dim=-2
         )
         transmittance = torch.exp(-transmittance)
         weights = alphas * transmittance
@@ -348,7 +350,7 @@ class SpacedSampler(nn.Module):
         consume the same random numbers; None -> torch.rand like nerfstudio."""
         num_samples = num_samples or self.num_samples
         num_rays = ray_bundle.origins.shape[0]
-        bins = torch.linspace(0.0, 1.0, num_samples + 1).to(ray_bundle.origins.device)[None, ...]
+        bins = torch.linspace(0.0, 1.0, num_samples + 1, dtype=ray_bundle.origins.dtype).to(ray_bundle.origins.device)[None, ...]
         if self.train_stratified and self.training:
             if t_rand is None:
                 if self.single_jitter:
@@ -408,16 +410,16 @@ class PDFSampler(nn.Module):
         cdf = torch.min(torch.ones_like(pdf), torch.cumsum(pdf, dim=-1))
         cdf = torch.cat([torch.zeros_like(cdf[..., :1]), cdf], dim=-1)
         if self.train_stratified and self.training:
-            u = torch.linspace(0.0, 1.0 - (1.0 / num_bins), steps=num_bins, device=cdf.device)
+            u = torch.linspace(0.0, 1.0 - (1.0 / num_bins), steps=num_bins, dtype=cdf.dtype, device=cdf.device)
             u = u.expand(size=(*cdf.shape[:-1], num_bins))
             if rand is None:
                 if self.single_jitter:
-                    rand = torch.rand((*cdf.shape[:-1], 1), device=cdf.device)
+                    rand = torch.rand((*cdf.shape[:-1], 1), dtype=cdf.dtype, device=cdf.device)
                 else:
-                    rand = torch.rand((*cdf.shape[:-1], num_samples + 1), device=cdf.device)
+                    rand = torch.rand((*cdf.shape[:-1], num_samples + 1), dtype=cdf.dtype, device=cdf.device)
             u = u + rand / num_bins
         else:
-            u = torch.linspace(0.0, 1.0 - (1.0 / num_bins), steps=num_bins, device=cdf.device)
+            u = torch.linspace(0.0, 1.0 - (1.0 / num_bins), steps=num_bins, dtype=cdf.dtype, device=cdf.device)
             u = u + 1.0 / (2 * num_bins)
             u = u.expand(size=(*cdf.shape[:-1], num_bins))
         u = u.contiguous()
@@ -545,7 +547,7 @@ def render_accumulation(weights: Tensor) -> Tensor:
 def render_depth_median(weights: Tensor, ray_samples: RaySamples) -> Tensor:
     steps = (ray_samples.frustums.starts + ray_samples.frustums.ends) / 2
     cumulative_weights = torch.cumsum(weights[..., 0], dim=-1)
-    split = torch.ones((*weights.shape[:-2], 1), device=weights.device) * 0.5
+    split = torch.ones((*weights.shape[:-2], 1), dtype=cumulative_weights.dtype, device=weights.device) * 0.5
     median_index = torch.searchsorted(cumulative_weights, split, side="left")
     median_index = torch.clamp(median_index, 0, steps.shape[-2] - 1)
     return torch.gather(steps[..., 0], dim=-1, index=median_index)

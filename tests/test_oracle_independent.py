@@ -210,3 +210,82 @@ def test_image_metrics_oracle_against_an_independent_ssim():
     mask[2, 1, 0] = mask[0, 0, 0] = 1.0
     r = om.image_metrics(np.zeros((12, 11, 3)) + 0.5, np.zeros((12, 11, 3)) + 0.5 + 1e-3, sem, mask)
     assert r["iou"] == 0.5 and r["iou_sigmoid"] == 2 / 132    # sigmoid(1) > 0.5 everywhere
+
+
+def test_per_ray_pieces_evaluate_float64_inputs_in_float64():
+    """The per-ray GPU tests (test_gpu_ray_kernels.py) use these ns_torch pieces on float64 inputs as their
+    high-precision reference: each must return float64 and agree with the float64 derivations of independent.py to
+    ~1e-12 (a float32 intermediate anywhere in the chain would show up as ~1e-7)."""
+    f8 = torch.float64
+    rng = np.random.default_rng(9)
+    R, S = 5, 24
+    edges = np.sort(rng.uniform(0, 4, (R, S + 1)), axis=-1)
+    sigma = rng.uniform(0, 30, (R, S))
+    rs = ns.RaySamples(frustums=ns.Frustums(None, None, torch.tensor(edges[:, :-1, None]), torch.tensor(edges[:, 1:, None]),
+                                            None), deltas=torch.tensor(np.diff(edges, axis=-1))[..., None])
+    w = rs.get_weights(torch.tensor(sigma)[..., None])
+    assert w.dtype == f8
+    assert np.abs(w[..., 0].numpy() - ind.render_weights(sigma, np.diff(edges, axis=-1))).max() < 1e-12
+    med = ns.render_depth_median(w, rs)
+    assert med.dtype == f8
+    mids = (edges[:, :-1] + edges[:, 1:]) / 2
+    assert np.abs(med[:, 0].numpy() - [ind.weighted_median(mids[r], w[r, :, 0].numpy()) for r in range(R)]).max() == 0.0
+    p = torch.tensor(rng.standard_normal((400, 3)) * 3)
+    got = ns.SceneContraction()(p)
+    assert got.dtype == f8 and np.abs(got.numpy() - ind.contract_linf(p.numpy())).max() < 1e-12
+    aabb = torch.tensor([[-1.0, -2.0, -0.5], [1.0, 2.0, 1.5]], dtype=f8)
+    x = ns.get_normalized_positions(p, aabb)
+    assert x.dtype == f8 and np.abs(x.numpy() - (p.numpy() - [-1.0, -2.0, -0.5]) / [2.0, 4.0, 2.0]).max() < 1e-15
+    fr = ns.Frustums(p[:R], p[R:2 * R], torch.tensor(edges[:, :1]), torch.tensor(edges[:, 1:2]), None)
+    assert fr.get_positions().dtype == f8
+    # PDF sampler: inverse of the padded histogram's CDF, in float64
+    rb = ns.RayBundle(torch.zeros(R, 3, dtype=f8), torch.tensor([[0.0, 0.0, 1.0]], dtype=f8).repeat(R, 1),
+                      torch.ones(R, 1, dtype=f8), nears=torch.full((R, 1), 0.05, dtype=f8),
+                      fars=torch.full((R, 1), 1000.0, dtype=f8))
+    first = ns.UniformLinDispPiecewiseSampler(num_samples=S, single_jitter=True)
+    first.eval()
+    prev = first(rb)
+    assert prev.spacing_starts.dtype == f8 and prev.frustums.starts.dtype == f8
+    wp = torch.tensor(rng.uniform(0, 1, (R, S, 1)) ** 4)
+    wp[0] = 0.0
+    for training in (False, True):
+        sampler = ns.PDFSampler(num_samples=16, include_original=False, single_jitter=True)
+        sampler.train(training)
+        rand = torch.tensor(rng.uniform(0, 1, (R, 1)))
+        out = sampler(rb, prev, wp, rand=rand if training else None)
+        assert out.spacing_starts.dtype == f8 and out.frustums.starts.dtype == f8
+        bins = torch.cat([out.spacing_starts[..., 0], out.spacing_ends[..., -1:, 0]], -1).numpy()
+        ed = torch.cat([prev.spacing_starts[..., 0], prev.spacing_ends[..., -1:, 0]], -1).numpy()
+        u = np.arange(17) / 17 + (rand.numpy() / 17 if training else 1.0 / 34)
+        for r in range(R):
+            mass = wp[r, :, 0].numpy() + 0.01
+            assert np.abs(ind.histogram_cdf(ed[r], mass / mass.sum(), bins[r]) - (u[r] if training else u)).max() < 1e-12
+        eu = torch.cat([out.frustums.starts[..., 0], out.frustums.ends[..., -1:, 0]], -1).numpy()
+        want = np.vectorize(lambda s: ind.lin_disp_piecewise(s, 0.05, 1000.0))(bins)
+        assert np.abs(eu / want - 1).max() < 1e-12
+    # interlevel and distortion losses
+    def hist(k):
+        t = np.sort(rng.uniform(0, 1, (R, k + 1)), axis=-1)
+        t[:, 0], t[:, -1] = 0.0, 1.0
+        wk = rng.uniform(0, 1, (R, k)) ** 3
+        return t, wk / wk.sum(-1, keepdims=True) * rng.uniform(0.3, 1.0, (R, 1))
+
+    def rs64(t):
+        t = torch.tensor(t)
+        return ns.RaySamples(frustums=ns.Frustums(None, None, t[:, :-1, None], t[:, 1:, None], None),
+                             spacing_starts=t[:, :-1, None], spacing_ends=t[:, 1:, None])
+    (t, wf), (t0, w0) = hist(12), hist(20)
+    il = ns.interlevel_loss([torch.tensor(w0)[..., None], torch.tensor(wf)[..., None]], [rs64(t0), rs64(t)])
+    want = np.mean([ind.outer_measure_loss(t[r], wf[r], t0[r], w0[r], eps=1e-7) for r in range(R)])
+    assert il.dtype == f8 and abs(float(il) - want) < 1e-12 * max(1.0, want) and want > 1e-4
+    dl = ns.distortion_loss([torch.tensor(wf)[..., None]], [rs64(t)])
+    assert dl.dtype == f8 and abs(float(dl) - np.mean([ind.distortion(t[r], wf[r]) for r in range(R)])) < 1e-12
+    # compositing
+    rgb = torch.tensor(rng.uniform(0, 1, (R, S, 3)))
+    for training in (False, True):
+        c = ns.render_rgb_last_sample(rgb, w, training)
+        wn = w[..., 0].numpy()
+        want = (wn[..., None] * rgb.numpy()).sum(1) + rgb.numpy()[:, -1] * (1 - wn.sum(1))[:, None]
+        assert c.dtype == f8 and np.abs(c.numpy() - (want if training else np.clip(want, 0, 1))).max() < 1e-12
+    sem = torch.tensor(rng.standard_normal((R, S, 1)))
+    assert ns.render_semantics(sem, w).dtype == f8 and ns.render_accumulation(w).dtype == f8
