@@ -58,13 +58,13 @@ enum ProfOp : int {
 };
 // Dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize — a PER-DEVICE attribute of the kernel.
 // Set once per (kernel instantiation, device); a failure is reported and retried on the next call, never cached.
-template <class K>
-static inline int ensure_dyn_lds(K kernel, int bytes) {
+template <auto Kernel>
+static inline int ensure_dyn_lds(int bytes) {
   static unsigned long long done_mask = 0ull;  // one bit per device id < 64 (one static per kernel instantiation)
   int dev = 0;
   FNR_HIP(hipGetDevice(&dev));
   if (dev < 64 && ((done_mask >> dev) & 1ull)) return FNR_OK;
-  FNR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  FNR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   if (dev < 64) done_mask |= 1ull << dev;
   return FNR_OK;
 }
@@ -107,14 +107,15 @@ __device__ __forceinline__ void nt_store(float2* p, const float2& v) {
   __builtin_nontemporal_store(t, reinterpret_cast<nt_f2*>(p));
 }
 // Class c is streaming iff bit c of FNR_NT_MASK is set.  NT_JAC_LD is off because it buys nothing (same-box A/B, round 6:
-// 5.72 vs 5.74 M rays/s).  Round 5 switched it off for another reason — with the Jacobian's loads in
-// k_field_mlp_bwd_base_coop streaming, training stopped being bit-reproducible — and suspected the loads ("may `nt` loads
-// complete out of order with plain ones at a partial s_waitcnt vmcnt(n)?").  Round 6 measured: they may not
-// (tools/microbench/nt_load_order.hip, nt_visibility.hip: 0 events in 1e11 partial waits / 300 buffer rewrites per mode, across
-// policies, stores, address-register reuse, a streaming second stream); the defect sat in that kernel's position-gradient
-// reduction, in an instruction selection hipcc only makes in the schedule the `nt` loads give it, and is fenced there
-// (field_mlp_bf16.hip "EVERY PARTIAL SUM IS PINNED"; profiles/r06_raw/nt_hunt.md).  Partial waits with accesses of both
-// policies in flight are everywhere in this library (tools/isa_nt_scan.py: 71 places) and are fine.
+// 5.72 vs 5.74 M rays/s).  Round 5 switched it off for another reason — with the Jacobian's loads in the base-branch backward
+// of the time (the cooperative k_field_mlp_bwd_base_coop, since retired) streaming, training stopped being bit-reproducible —
+// and suspected the loads ("may `nt` loads complete out of order with plain ones at a partial s_waitcnt vmcnt(n)?").  Round 6
+// measured: they may not (tools/microbench/nt_load_order.hip, nt_visibility.hip: 0 events in 1e11 partial waits / 300 buffer
+// rewrites per mode, across policies, stores, address-register reuse, a streaming second stream); the defect sat in that
+// kernel's position-gradient reduction, in an instruction selection hipcc only makes in the schedule the `nt` loads give it.
+// The same reduction in its per-wave successor is fenced (field_mlp_bwd_pw.hip "EVERY PARTIAL SUM IS PINNED";
+// profiles/r06_raw/nt_hunt.md).  Partial waits with accesses of both policies in flight are everywhere in this library
+// (tools/isa_nt_scan.py: 71 places) and are fine.
 #ifndef FNR_NT_MASK
 #define FNR_NT_MASK 0xef
 #endif

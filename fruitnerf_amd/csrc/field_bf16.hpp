@@ -399,4 +399,39 @@ __device__ __forceinline__ void bf_layer_T1(const bf16x8* __restrict__ segT, con
   bf_layer_acc1<NS, NIBO, (NOB + 1) / 2>(segT, x, o, lane);
 }
 
+// ---- host entry points of the bf16-pipe modes (fnr_field_net.mlp_mode != 0), called from field_mlp.hip / field_mlp_bwd.hip ----
+// cfg: 0 `fruit_nerf`, 1 `fruit_nerf_big`; mode: MLP_BF16 | MLP_BF16X3; image_ws: the fragment image the caller has packed
+// (k_prepare_field / launch_pack_field_weights_bf16), field_bf16_image_bytes() covers both shapes at BF_MAX_PIECES.
+size_t field_bf16_image_bytes();  // field_mlp_bf16.hip, like the next three
+int field_mlp_fwd_bf16(int cfg, int mode, const FieldPtrs& p, const float* packed, void* image_ws, const float* ray_bias,
+                       const RaysDev& rd, int S, long long N, const float2* feats, const uint8_t* selector, float* density,
+                       float* rgb, float* logit, float* geo_out, float* h_buf, hipStream_t st);
+int field_mlp_fwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
+                               const float* h_buf, float* logit, hipStream_t st);
+int field_mlp_bwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
+                               const float* h_saved, const float* d_logit, float* partials, long long blocks,
+                               hipStream_t st);
+namespace pw {
+// what the branches of one per-wave backward share (field_mlp_bwd_launch builds it once)
+struct BwdArgs {
+  const float* packed;
+  const __bf16* image;
+  const float* ray_bias;
+  RaysDev rd;
+  int S;
+  long long N;
+  const float2* feats;
+  const float* h_saved;
+  const uint8_t* selector;
+  const float *d_density, *d_rgb, *d_logit;
+  float2* d_feats;
+  float *d_h, *gsum_tile, *gsum_extra, *partials;
+  long long blocks;  // workgroups = partial images, the same for every branch
+  hipStream_t st;
+};
+}  // namespace pw
+// branch: 0 colour, 1 semantic (`fruit_nerf` only), 2 base — with jac and d_pos, the base branch also writes the position
+// gradient.  field_mlp_bwd_pw.hip
+int field_mlp_bwd_pw(int cfg, int mode, int branch, const pw::BwdArgs& a, const float2* jac, float4* d_pos);
+
 }  // namespace fnr

@@ -43,13 +43,6 @@ int field_ptrs(const fnr_field_net* net, FieldPtrs& p, int* cfg_id) {
   return FNR_OK;
 }
 
-// bf16 / bf16x3 modes (field_mlp_bf16.hip)
-int field_mlp_fwd_bf16(int cfg, int mode, const FieldPtrs& p, const float* packed, void* image_ws, const float* ray_bias,
-                       const RaysDev& rd, int S, long long N, const float2* feats, const uint8_t* selector, float* density,
-                       float* rgb, float* logit, float* geo_out, float* h_buf, hipStream_t st);
-size_t field_bf16_image_bytes();
-int field_mlp_fwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
-                               const float* h_buf, float* logit, hipStream_t st);
 // workspace layout of fnr_field_mlp_fwd: [fp32 fragment image | bf16 fragment image (3 pieces) | per-ray colour bias]
 static inline size_t fwd_ws_packed_bytes() { return ((size_t)(FIELD_MAX_PACKED_FLOATS + 64) * sizeof(float) + 255) / 256 * 256; }
 size_t field_fwd_ws_image_offset() { return fwd_ws_packed_bytes(); }

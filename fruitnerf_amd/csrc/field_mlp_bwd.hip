@@ -21,9 +21,8 @@
 //     of 4 waves x <= 512 registers with all four layers in LDS: SEM_A owns dW of sem0, sem2 and the head (208
 //     registers), SEM_B owns the 128 x 128 layer (256 registers); SEM_B repeats the forward up to s2 and the dX chain
 //     down to Gs2 (1.35x the algorithmic MACs of the branch, no activations through HBM).
-#include <stdlib.h>
-
 #include "field_layers.hpp"
+#include "field_bf16.hpp"
 #include "sequencer.hpp"
 
 namespace fnr {
@@ -825,17 +824,7 @@ __global__ __launch_bounds__(1024) void k_finish_weights(int n_images, RaysDev r
 
 int field_ptrs(const fnr_field_net* net, FieldPtrs& p, int* cfg_id);  // field_mlp.hip
 size_t field_fwd_ws_image_offset();                                     // field_mlp.hip
-size_t field_bf16_image_bytes();                                        // field_mlp_bf16.hip
-int field_mlp_bwd_bf16(int cfg, int mode, int branch, const FieldPtrs& p, bool pack, const float* packed, void* image_ws,
-                       const float* ray_bias, const RaysDev& rd, int S, long long N, const float2* feats,
-                       const float* h_saved, const uint8_t* selector, const float* d_density, const float* d_rgb,
-                       const float* d_logit, float2* d_feats, float* d_h, float* gsum_tile, float* gsum_extra,
-                       float* partials, long long blocks, hipStream_t st, const float2* jac = nullptr,
-                       float4* d_pos = nullptr);
 int position_contract(long long N, int n_levels, const float2* jac, const float2* d_feats, float4* d_pos, hipStream_t st);
-int field_mlp_bwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
-                               const float* h_saved, const float* d_logit, float* partials, long long blocks,
-                               hipStream_t st);
 
 }  // namespace fnr
 
@@ -887,12 +876,7 @@ int field_mlp_bwd_launch(const FieldPtrs& p, const FieldPtrs& gp, const fnr_fiel
   float* gsum_extra = (S % 16 != 0) ? ws.gsum_extra : nullptr;  // only tiles that straddle rays use it
   const float2* f2 = reinterpret_cast<const float2*>(feats);
   float2* df2 = reinterpret_cast<float2*>(d_feats);
-  static const int color_waves = [] {
-    const char* e = getenv("FNR_COLOR_WAVES");
-    return (e && atoi(e) == 4) ? 4 : 8;
-  }();
   void* bf16_image = ws.bf16_image;
-  const bool bf16_pack = !packed_saved;
   if (packed_saved) {
     packed = const_cast<float*>(packed_saved);  // the forward pass's fragment image of the same weights
     bf16_image = reinterpret_cast<char*>(packed) + field_fwd_ws_image_offset();  // ... and its bf16 pieces
@@ -912,18 +896,21 @@ int field_mlp_bwd_launch(const FieldPtrs& p, const FieldPtrs& gp, const fnr_fiel
   if (blocks > max_blocks) blocks = max_blocks;
   const dim3 grid((unsigned)blocks);
   const int mode = net->mlp_mode;
-  // bf16-pipe modes: every branch of both shapes (field_mlp_bf16.hip: cooperative dW; the `fruit_nerf_big` semantic
-  // branch additionally weight-streamed)
+  // bf16-pipe modes: the per-wave kernels (field_mlp_bwd_pw.hip) for every branch of both shapes but the `fruit_nerf_big`
+  // semantic one, which has a weight-streaming kernel with cooperative dW (field_mlp_bf16.hip)
   constexpr int cfg_id = Cfg::NSEM == 2 ? 0 : 1;
   const bool bf_all = mode != FNR_MLP_FP32;
   const bool bf_sem_big = mode != FNR_MLP_FP32 && Cfg::NSEM == 3;
+  // what the branches of the per-wave backward share
+  const pw::BwdArgs bf{packed, reinterpret_cast<const __bf16*>(bf16_image), ray_bias, rd, S, N, f2, h_saved, selector, d_density,
+                       d_rgb, d_logit, df2, ws.d_h, ws.gsum_tile, gsum_extra, partials, blocks, st};
   if (bf_all) {
-    const int rc = field_mlp_bwd_bf16(cfg_id, mode, 0, p, bf16_pack, packed, bf16_image, ray_bias, rd, S, N, f2, h_saved, selector,
-                                      d_density, d_rgb, d_logit, df2, ws.d_h, ws.gsum_tile, gsum_extra, partials, blocks, st);
+    if (!packed_saved) {  // the bf16 pieces of the fragment image, like the fp32 image above
+      launch_pack_field_weights_bf16<Cfg>(p, mode == FNR_MLP_BF16 ? 1 : 3, reinterpret_cast<__bf16*>(bf16_image), st);
+      FNR_LAUNCH_CHECK();
+    }
+    const int rc = field_mlp_bwd_pw(cfg_id, mode, 0, bf, nullptr, nullptr);
     if (rc) return rc;
-  } else if (color_waves == 4) {
-    hipLaunchKernelGGL((k_field_mlp_bwd_color<Cfg, 4>), grid, dim3(256), 0, st, packed, ray_bias, rd, S, N, h_saved, d_rgb,
-                       ws.d_h, ws.gsum_tile, gsum_extra, partials);
   } else {
     hipLaunchKernelGGL((k_field_mlp_bwd_color<Cfg, 8>), grid, dim3(512), 0, st, packed, ray_bias, rd, S, N, h_saved, d_rgb,
                        ws.d_h, ws.gsum_tile, gsum_extra, partials);
@@ -941,16 +928,13 @@ int field_mlp_bwd_launch(const FieldPtrs& p, const FieldPtrs& gp, const fnr_fiel
   if (bf_sem_big) {
     int rc = field_mlp_bwd_sem_big_bf16(mode, p, bf16_image, packed, N, h_saved, d_logit, partials, blocks, st);
     if (rc) return rc;
-    rc = field_mlp_bwd_bf16(cfg_id, mode, 2, p, false, packed, bf16_image, ray_bias, rd, S, N, f2, h_saved, selector, d_density,
-                            d_rgb, d_logit, df2, ws.d_h, ws.gsum_tile, gsum_extra, partials, blocks, st, jac, d_pos);
+    rc = field_mlp_bwd_pw(cfg_id, mode, 2, bf, jac, d_pos);
     if (rc) return rc;
   } else if (bf_all) {
-    for (int branch = 1; branch <= 2; ++branch) {
-      const int rc = field_mlp_bwd_bf16(cfg_id, mode, branch, p, false, packed, bf16_image, ray_bias, rd, S, N, f2, h_saved, selector,
-                                        d_density, d_rgb, d_logit, df2, ws.d_h, ws.gsum_tile, gsum_extra, partials, blocks, st,
-                                        branch == 2 ? jac : nullptr, branch == 2 ? d_pos : nullptr);
-      if (rc) return rc;
-    }
+    int rc = field_mlp_bwd_pw(cfg_id, mode, 1, bf, nullptr, nullptr);
+    if (rc) return rc;
+    rc = field_mlp_bwd_pw(cfg_id, mode, 2, bf, jac, d_pos);
+    if (rc) return rc;
   } else if constexpr (Cfg::NSEM == 2) {
     hipLaunchKernelGGL((k_field_mlp_bwd_sem<Cfg, 8>), grid, dim3(512), 0, st, packed, N, h_saved, d_logit, partials);
     FNR_LAUNCH_CHECK();

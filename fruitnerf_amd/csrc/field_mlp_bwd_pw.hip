@@ -2,10 +2,13 @@
 // shape, the colour and base branches of `fruit_nerf_big` (whose 128-wide semantic branch keeps its weight-streaming kernel).
 // Replaces the same reference code as field_mlp_bf16.hip: fruit_field.py:132-166,187-281 and its autograd.
 //
-// The cooperative kernels (field_mlp_bf16.hip) give every 16 x 16 block of a layer's weight gradient to ONE wave over a
-// 128-sample batch: eight waves meet at 6 - 7 workgroup barriers per batch, exchange their tiles' dY / X columns through a
-// [feature row][128 samples] LDS scratch written with 2-byte stores, and run one 16-sample tile each — MFMA-busy 0.16 - 0.32,
-// more than half the cycles waiting (profiles/r05_kernel_trace_pmc.md).  Here a wave is on its own:
+// History: until round 6 these branches ran COOPERATIVE kernels, the form the `fruit_nerf_big` semantic branch still has
+// (field_mlp_bf16.hip): every 16 x 16 block of a layer's weight gradient belonged to ONE wave over a 128-sample batch, so eight
+// waves met at 6 - 7 workgroup barriers per batch, exchanged their tiles' dY / X columns through a [feature row][128 samples]
+// LDS scratch written with 2-byte stores, and ran one 16-sample tile each — MFMA-busy 0.16 - 0.32, more than half the cycles
+// waiting (profiles/r05_kernel_trace_pmc.md).  The per-wave form took colour / semantic / base from 56.0 / 42.4 / 46.1 to
+// 45.9 / 34.1 / 34.8 us (profiles/r06_raw/per_wave_mlp_bwd.md) and the cooperative kernels were retired.  Here a wave is on
+// its own:
 //   * one wave = NT 16-sample tiles (NT = 2 or 4) through the whole branch: every LDS weight fragment feeds NT MFMA chains,
 //     and 32 samples are exactly one K-block of v_mfma_f32_16x16x32_bf16, so dW[out block][in block] += G^T X is NT/2 MFMAs
 //     per piece product, accumulated in the wave's own registers over its persistent loop (24 / 24 / 12 weight blocks + the
@@ -24,10 +27,8 @@
 //     bit-reproducible), copied out as the workgroup's partial image — same index space as before (field_layers.hpp), so
 //     k_color_ray_grads / k_finish_weights are unchanged;
 //   * the base branch takes the saved h (for trunc_exp') instead of recomputing mlp_base's second layer.
-// Pieces as in the cooperative kernels: NSF = 3 for the forward recompute (the ReLU gates must reproduce the forward
-// pass's signs), NS = 2 for dX / dW in the bf16x3 mode; 1 / 1 in the plain bf16 mode.
-#include <stdlib.h>
-
+// Pieces: NSF = 3 for the forward recompute (the ReLU gates must reproduce the forward pass's signs), NS = 2 for dX / dW in
+// the bf16x3 mode; 1 / 1 in the plain bf16 mode.
 #include <type_traits>
 
 #include "field_bf16.hpp"
@@ -742,8 +743,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_sem_pw(
 }
 
 // ---- base branch -------------------------------------------------------------------------------------------------------
-// POSGRAD: the input gradient of the hash grid rides along (see k_field_mlp_bwd_base_coop): d_pos [N] float4 = dL/dfeats
-// contracted with the encode's saved Jacobian [L][3][N] float2, from the registers that hold dL/dfeats.
+// POSGRAD: the input gradient of the hash grid rides along (camera-pose optimisation, fruit_nerf_config.py:39-43).  The
+// forward encode saved J = d feats / d(unit-cube position) [L][3][N] float2; this kernel holds dL/dfeats of its samples in
+// registers (lane (g, j): levels g, 4 + g, 8 + g, 12 + g of sample j), so it contracts them with J right here — d_pos [N] float4
+// = sum over levels and features of dL/dfeat * J — instead of a separate launch that re-reads d_feats and waits 91 % of its
+// cycles on 64 dependent loads per lane (k_position_from_jacobian: 32 us per 196 608 samples).
 template <class Cfg, int NSF, int NS, int NT, int WAVES, bool POSGRAD>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_base_pw(
     const float* __restrict__ packed, const __bf16* __restrict__ image, int N, const float2* __restrict__ feats,
@@ -848,10 +852,18 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_base_pw
         if (sm.ok[t])
           d_feats[(size_t)(4 * m + g) * N + sm.n[t]] = make_float2(Gx.v[t][m >> 1][2 * (m & 1)], Gx.v[t][m >> 1][2 * (m & 1) + 1]);
     if constexpr (POSGRAD) {
-      // EVERY PARTIAL SUM IS PINNED IN ITS OWN REGISTER (the empty asm statements), as in k_field_mlp_bwd_base_coop: left to
-      // itself hipcc may pair the x / y sums into packed-FP32 instructions threaded through the ds_bpermute shuffles, the
-      // sequence that produced wrong y components there (profiles/r06_raw/nt_hunt.md; tests/test_isa_invariants.py keeps
-      // packed instructions out of this reduction).
+      // EVERY PARTIAL SUM IS PINNED IN ITS OWN REGISTER (the empty asm statements).  Left to itself hipcc may pair the x / y
+      // sums into packed-FP32 instructions with cross-half operand selects and thread the ds_bpermute shuffles through them
+      // (v_pk_add_f32 .. op_sel:[0,1] op_sel_hi:[1,0] ; ds_bpermute_b32 ; v_pk_add_f32 ..).  It did so in this reduction's first
+      // home, the cooperative base-branch kernel this one replaced, in the schedule it picks when the Jacobian's loads are `nt`:
+      // ~10 of 12 288 waves per launch then ended with a WRONG y component — 5 % off, only waves 0..3 (those that reached the
+      // sequence while the others still used the LDS pipe), never d_feats — which is what broke run-to-run reproducibility in
+      // round 5 (NT_JAC_LD).  Not the loads: `nt` and plain accesses complete in issue order and see earlier kernels' stores
+      // (tools/microbench/nt_load_order.hip, nt_visibility.hip: 0 events in 1e11); the same instructions in isolation do not
+      // fail either (pk_forward_hazard.hip) — the defect needed that kernel's context and is not understood beyond that
+      // (profiles/r06_raw/nt_hunt.md has the ISA and the probes).  Pinned, the sums compile to scalar v_fma / v_add in every
+      // build: tests/test_isa_invariants.py keeps packed instructions out of this reduction under either load policy, and
+      // tests/test_gpu_bf16.py checks on the device that repeated calls give identical d_position equal to the contraction.
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         float gp[3] = {0.f, 0.f, 0.f};
@@ -920,33 +932,31 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_base_pw
 #endif
 
 template <class Cfg, int NSF, int NS>
-static int launch(int branch, const float* packed, const __bf16* image, const float* ray_bias, const RaysDev& rd, int S, long long N,
-                  const float2* feats, const float* h_saved, const uint8_t* selector, const float* d_density, const float* d_rgb,
-                  const float* d_logit, float2* d_feats, float* d_h, float* gsum_tile, float* gsum_extra, float* partials,
-                  long long blocks, hipStream_t st, const float2* jac, float4* d_pos) {
+static int launch(int branch, const BwdArgs& a, const float2* jac, float4* d_pos) {
   constexpr int WAVES = FNR_PW_WAVES, THREADS = 64 * WAVES;
-  FNR_CHECK_ARG(N < (1ll << 31) - 64, "field_mlp_bwd: %lld samples exceed the 32-bit sample index of the backward kernels", N);
-  const int n = (int)N;
+  FNR_CHECK_ARG(a.N < (1ll << 31) - 64, "field_mlp_bwd: %lld samples exceed the 32-bit sample index of the backward kernels", a.N);
+  const int n = (int)a.N;
   // exactly `blocks` workgroups: every one of the caller's partial images receives this branch's blocks (a workgroup
   // without samples stores zeros)
+  const dim3 grid((unsigned)a.blocks);
   if (branch == 0) {
     constexpr int NT = FNR_PW_NT_COLOR;
     using L = Lds<Cfg, SegsColF<Cfg>, SegsColT<Cfg>, NSF, NS, NT, WAVES, 80>;
     static_assert(L::BYTES <= 160 * 1024, "colour branch exceeds the LDS");
-    auto kern = k_field_mlp_bwd_color_pw<Cfg, NSF, NS, NT, WAVES>;
-    const int once = ensure_dyn_lds(kern, L::BYTES);
+    constexpr auto kern = k_field_mlp_bwd_color_pw<Cfg, NSF, NS, NT, WAVES>;
+    const int once = ensure_dyn_lds<kern>(L::BYTES);
     if (once) return once;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), L::BYTES, st, packed, image, ray_bias, rd, S, n, h_saved,
-                       d_rgb, d_h, gsum_tile, gsum_extra, partials);
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), L::BYTES, a.st, a.packed, a.image, a.ray_bias, a.rd, a.S, n, a.h_saved, a.d_rgb,
+                       a.d_h, a.gsum_tile, a.gsum_extra, a.partials);
   } else if (branch == 1) {
     if constexpr (Cfg::NSEM == 2) {
       constexpr int NT = NSF == 1 ? 1 : FNR_PW_NT_SEM;  // (plain bf16: hipcc's schedule of the two-tile form spills 8 registers)
       using L = Lds<Cfg, SegsSemF<Cfg>, SegsSemT<Cfg>, NSF, NS, NT, WAVES, 128>;
       static_assert(L::BYTES <= 160 * 1024, "semantic branch exceeds the LDS");
-      auto kern = k_field_mlp_bwd_sem_pw<Cfg, NSF, NS, NT, WAVES>;
-      const int once = ensure_dyn_lds(kern, L::BYTES);
+      constexpr auto kern = k_field_mlp_bwd_sem_pw<Cfg, NSF, NS, NT, WAVES>;
+      const int once = ensure_dyn_lds<kern>(L::BYTES);
       if (once) return once;
-      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), L::BYTES, st, packed, image, n, h_saved, d_logit, partials);
+      hipLaunchKernelGGL(kern, grid, dim3(THREADS), L::BYTES, a.st, a.packed, a.image, n, a.h_saved, a.d_logit, a.partials);
     } else {
       FNR_CHECK_ARG(false, "the fruit_nerf_big semantic branch has its own kernel (field_mlp_bwd_sem_big_bf16)");
     }
@@ -955,17 +965,17 @@ static int launch(int branch, const float* packed, const __bf16* image, const fl
     using L = Lds<Cfg, SegsBaseF<Cfg>, SegsBaseT<Cfg>, NSF, NS, NT, WAVES, 64>;
     static_assert(L::BYTES <= 160 * 1024, "base branch exceeds the LDS");
     if (jac && d_pos) {
-      auto kern = k_field_mlp_bwd_base_pw<Cfg, NSF, NS, NT, WAVES, true>;
-      const int once = ensure_dyn_lds(kern, L::BYTES);
+      constexpr auto kern = k_field_mlp_bwd_base_pw<Cfg, NSF, NS, NT, WAVES, true>;
+      const int once = ensure_dyn_lds<kern>(L::BYTES);
       if (once) return once;
-      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), L::BYTES, st, packed, image, n, feats, h_saved, selector,
-                         d_density, d_h, d_feats, partials, jac, d_pos);
+      hipLaunchKernelGGL(kern, grid, dim3(THREADS), L::BYTES, a.st, a.packed, a.image, n, a.feats, a.h_saved, a.selector,
+                         a.d_density, a.d_h, a.d_feats, a.partials, jac, d_pos);
     } else {
-      auto kern = k_field_mlp_bwd_base_pw<Cfg, NSF, NS, NT, WAVES, false>;
-      const int once = ensure_dyn_lds(kern, L::BYTES);
+      constexpr auto kern = k_field_mlp_bwd_base_pw<Cfg, NSF, NS, NT, WAVES, false>;
+      const int once = ensure_dyn_lds<kern>(L::BYTES);
       if (once) return once;
-      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), L::BYTES, st, packed, image, n, feats, h_saved, selector,
-                         d_density, d_h, d_feats, partials, jac, d_pos);
+      hipLaunchKernelGGL(kern, grid, dim3(THREADS), L::BYTES, a.st, a.packed, a.image, n, a.feats, a.h_saved, a.selector,
+                         a.d_density, a.d_h, a.d_feats, a.partials, jac, d_pos);
     }
   }
   FNR_LAUNCH_CHECK();
@@ -974,17 +984,11 @@ static int launch(int branch, const float* packed, const __bf16* image, const fl
 
 }  // namespace pw
 
-// cfg: 0 `fruit_nerf` (branch: 0 colour, 1 semantic, 2 base), 1 `fruit_nerf_big` (colour and base; its 128-wide semantic branch
-// is field_mlp_bwd_sem_big_bf16) — the backward in the bf16-pipe modes (called by field_mlp_bwd_bf16, which has packed the
-// fragment image)
-int field_mlp_bwd_pw(int cfg, int mode, int branch, const float* packed, const __bf16* image, const float* ray_bias, const RaysDev& rd,
-                     int S, long long N, const float2* feats, const float* h_saved, const uint8_t* selector,
-                     const float* d_density, const float* d_rgb, const float* d_logit, float2* d_feats, float* d_h,
-                     float* gsum_tile, float* gsum_extra, float* partials, long long blocks, hipStream_t st, const float2* jac,
-                     float4* d_pos) {
-#define FNR_PW_LAUNCH(C, A, B)                                                                                                      \
-  pw::launch<C, A, B>(branch, packed, image, ray_bias, rd, S, N, feats, h_saved, selector, d_density, d_rgb, d_logit, d_feats, d_h, \
-                      gsum_tile, gsum_extra, partials, blocks, st, jac, d_pos)
+// The backward of every branch but `fruit_nerf_big`'s semantic one (field_mlp_bwd_sem_big_bf16) in the bf16-pipe modes; the
+// arguments are described at the declaration (field_bf16.hpp).  The bf16x3 mode runs dX / dW with two pieces (three products),
+// the forward recompute with three.
+int field_mlp_bwd_pw(int cfg, int mode, int branch, const pw::BwdArgs& a, const float2* jac, float4* d_pos) {
+#define FNR_PW_LAUNCH(C, A, B) pw::launch<C, A, B>(branch, a, jac, d_pos)
   if (cfg == 0) return mode == MLP_BF16 ? FNR_PW_LAUNCH(FieldCfgBase, 1, 1) : FNR_PW_LAUNCH(FieldCfgBase, 3, 2);
   return mode == MLP_BF16 ? FNR_PW_LAUNCH(FieldCfgBig, 1, 1) : FNR_PW_LAUNCH(FieldCfgBig, 3, 2);
 #undef FNR_PW_LAUNCH

@@ -653,11 +653,11 @@ static int acc_lds_bytes(const AccArgs& a) { return (2 << a.log2_rows) * (int)si
 static int scatter_accumulate(const AccArgs& a, bool adam, hipStream_t st) {
   const int bytes = acc_lds_bytes(a);
   if (adam) {
-    const int rc = ensure_dyn_lds(k_scatter_accumulate<true>, 2 * SC_MAX_ROWS * (int)sizeof(unsigned long long));
+    const int rc = ensure_dyn_lds<k_scatter_accumulate<true>>(2 * SC_MAX_ROWS * (int)sizeof(unsigned long long));
     if (rc) return rc;
     hipLaunchKernelGGL(k_scatter_accumulate<true>, dim3((unsigned)a.nbins), dim3(1024), bytes, st, a);
   } else {
-    const int rc = ensure_dyn_lds(k_scatter_accumulate<false>, 2 * SC_MAX_ROWS * (int)sizeof(unsigned long long));
+    const int rc = ensure_dyn_lds<k_scatter_accumulate<false>>(2 * SC_MAX_ROWS * (int)sizeof(unsigned long long));
     if (rc) return rc;
     hipLaunchKernelGGL(k_scatter_accumulate<false>, dim3((unsigned)a.nbins), dim3(1024), bytes, st, a);
   }
@@ -669,11 +669,11 @@ static int scatter_accumulate(const AccArgs& a, bool adam, hipStream_t st) {
 static int scatter_accumulate2(const AccArgs& a, const AccArgs& b, bool adam, hipStream_t st) {
   const int bytes = acc_lds_bytes(a) > acc_lds_bytes(b) ? acc_lds_bytes(a) : acc_lds_bytes(b);
   if (adam) {
-    const int rc = ensure_dyn_lds(k_scatter_accumulate2<true>, 2 * SC_MAX_ROWS * (int)sizeof(unsigned long long));
+    const int rc = ensure_dyn_lds<k_scatter_accumulate2<true>>(2 * SC_MAX_ROWS * (int)sizeof(unsigned long long));
     if (rc) return rc;
     hipLaunchKernelGGL(k_scatter_accumulate2<true>, dim3((unsigned)(a.nbins + b.nbins)), dim3(1024), bytes, st, a, b);
   } else {
-    const int rc = ensure_dyn_lds(k_scatter_accumulate2<false>, 2 * SC_MAX_ROWS * (int)sizeof(unsigned long long));
+    const int rc = ensure_dyn_lds<k_scatter_accumulate2<false>>(2 * SC_MAX_ROWS * (int)sizeof(unsigned long long));
     if (rc) return rc;
     hipLaunchKernelGGL(k_scatter_accumulate2<false>, dim3((unsigned)(a.nbins + b.nbins)), dim3(1024), bytes, st, a, b);
   }

@@ -1,5 +1,6 @@
 """Which state diverges first between two training runs from one seed?  (Round 6: the hunt for what `nt` loads of the Jacobian
-in k_field_mlp_bwd_base_coop do to run-to-run reproducibility; run with FNR_LIB_PATH pointing at a variant library.)
+did to run-to-run reproducibility in the cooperative base-branch backward of the time, k_field_mlp_bwd_base_coop, retired since;
+the probe runs whole training steps and works on any build: run with FNR_LIB_PATH pointing at a variant library.)
 usage: python tests/diagnostics/nt_jac_probe.py [steps = 60] [runs = 3]"""
 import os
 import sys

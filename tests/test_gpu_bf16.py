@@ -42,7 +42,8 @@ def test_bf16x3_losses_and_all_gradients(dev, monkeypatch, step, n_samples):
 @pytest.mark.parametrize("step,n_samples", [(0, 128), (12, 40)])
 def test_bf16x3_big_shape_losses_and_all_gradients(dev, monkeypatch, step, n_samples):
     """fruit_nerf_big: the bf16x3 mode runs the semantic branch's backward (30 -> 128 -> 128 -> 64 -> head) as the
-    weight-streamed cooperative-dW kernel on the bf16 pipe; forward, colour and base stay on fp32 MFMA."""
+    weight-streamed cooperative-dW kernel on the bf16 pipe (the only cooperative kernel left); colour and base run the
+    per-wave kernels, as in `fruit_nerf`."""
     from tests import test_gpu_training_parity as t
     _rerun(monkeypatch, t.test_losses_and_all_gradients, dev, step, n_samples, "fruit_nerf_big")
 
@@ -189,7 +190,7 @@ def test_transposing_lds_read_returns_what_the_per_wave_backward_assumes(dev, tm
 def test_per_wave_backward_is_reproducible_and_its_position_gradient_is_its_own_contraction(dev, shape):
     """The MLP backward with the hash grid's input gradient (fnr_field_mlp_bwd_rays -> k_field_mlp_bwd_base_pw<.., POSGRAD>) at the
     training size, called repeatedly on identical inputs: d_feats and d_position bit-identical call to call (round 5's
-    irreproducibility sat in exactly this reduction of the cooperative kernel), and every d_position equal to the contraction
+    irreproducibility sat in exactly this reduction, in the cooperative kernel this one replaced), and every d_position equal to the contraction
     of the kernel's own d_feats with the encode's Jacobian recomputed in float64."""
     from fruitnerf_amd import _kernels as K
     from fruitnerf_amd.data.semantics import apple_metadata

@@ -68,11 +68,6 @@ def test_scatter_kernels_use_no_scratch_and_keep_three_emit_workgroups_per_cu(sc
 
 
 
-# ---- round 6: the position-gradient reduction of k_field_mlp_bwd_base_coop (profiles/r06_raw/nt_hunt.md) ----------------
-# With `nt` loads of the Jacobian hipcc chose packed FP32 with cross-half operand selects threaded through the six
-# ds_bpermute shuffles of that reduction, and ~10 of 12 288 waves per launch computed a wrong y component.  The partial sums are
-# pinned in registers since; this keeps every build's reduction free of packed math, for both load policies.
-
 def _compile(src, out, extra=()):
     cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off",
            "-S", "--cuda-device-only", *extra, "-o", str(out), os.path.join(CSRC, src)]
@@ -80,29 +75,14 @@ def _compile(src, out, extra=()):
     return out.read_text().split("\n")
 
 
-@pytest.mark.parametrize("mask", ["0xef", "0xff"])
-def test_position_gradient_reduction_is_free_of_packed_math(tmp_path, mask):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    lines = _compile("field_mlp_bf16.hip", tmp_path / "field_mlp_bf16.s", extra=[f"-DFNR_NT_MASK={mask}"])
-    kernels = [m.group(1) for m in (re.match(r"^(_ZN3fnr25k_field_mlp_bwd_base_coop\w+):", l) for l in lines) if m]
-    posgrad = [k for k in kernels if "Lb1EEE" in k]
-    assert len(posgrad) >= 4, kernels                     # (FieldCfgBase | FieldCfgBig) x (bf16 | bf16x3)
-    for name in posgrad:
-        body = [l for l in _kernel(lines, name) if l and not l.startswith((";", "."))]
-        shuffles = [i for i, l in enumerate(body) if l.startswith("ds_bpermute_b32")]
-        assert len(shuffles) == 6, (name, len(shuffles))   # x, y, z by 16 lanes, then by 32
-        window = body[shuffles[0] - 24:shuffles[-1] + 8]   # the sums that feed the first shuffle .. the adds behind the last
-        packed = [l for l in window if l.startswith("v_pk_")]
-        assert not packed, f"{name}: packed math in the position-gradient reduction (FNR_NT_MASK={mask}): {packed[:3]}"
-        if mask == "0xff":
-            assert any(l.startswith("global_load_dwordx2") and l.endswith(" nt") for l in body), "the variant under test streams the Jacobian"
-
-
 # ---- round 6: the per-wave MLP backward (field_mlp_bwd_pw.hip) ---------------------------------------------------------------
 # Its kernels sit at the register limit of two waves per SIMD by design (116 dW accumulator registers in the colour branch): a
-# spill would put accumulators into scratch memory inside the loop.  And its base branch carries the same position-gradient
-# reduction as k_field_mlp_bwd_base_coop, once per tile.
+# spill would put accumulators into scratch memory inside the loop.
+# Its base branch carries the position-gradient reduction, once per tile (profiles/r06_raw/nt_hunt.md).  In that reduction's first
+# home, the cooperative base-branch kernel retired since, hipcc chose — with `nt` loads of the Jacobian — packed FP32 with
+# cross-half operand selects threaded through the six ds_bpermute shuffles, and ~10 of 12 288 waves per launch computed a wrong y
+# component.  The partial sums are pinned in registers since; this keeps every build's reduction free of packed math, for both
+# load policies.
 
 @pytest.fixture(scope="module")
 def per_wave_asm(tmp_path_factory):
@@ -122,8 +102,11 @@ def test_per_wave_backward_kernels_do_not_spill(per_wave_asm):
         assert scratch == 0 and spill == 0 and vgpr <= 256, (name, scratch, vgpr, spill)
 
 
-def test_per_wave_position_gradient_reduction_is_free_of_packed_math(per_wave_asm):
-    lines = per_wave_asm
+@pytest.mark.parametrize("mask", ["0xef", "0xff"])
+def test_per_wave_position_gradient_reduction_is_free_of_packed_math(tmp_path, mask):
+    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
+        pytest.skip("hipcc not available")
+    lines = _compile("field_mlp_bwd_pw.hip", tmp_path / "field_mlp_bwd_pw.s", extra=[f"-DFNR_NT_MASK={mask}"])
     kernels = [m.group(1) for m in (re.match(r"^(_ZN3fnr2pw23k_field_mlp_bwd_base_pw\w+):", l) for l in lines) if m]
     posgrad = [k for k in kernels if "Lb1EEE" in k]
     assert len(posgrad) == 4, kernels                     # (fruit_nerf | fruit_nerf_big) x (bf16 | bf16x3)
@@ -132,9 +115,11 @@ def test_per_wave_position_gradient_reduction_is_free_of_packed_math(per_wave_as
         shuffles = [i for i, l in enumerate(body) if l.startswith("ds_bpermute_b32")]
         assert len(shuffles) in (6, 12, 24), (name, len(shuffles))   # x, y, z by 16 lanes, then by 32 — per tile of the wave
         for k in range(0, len(shuffles), 6):
-            window = body[shuffles[k] - 24:shuffles[k + 5] + 8]
+            window = body[shuffles[k] - 24:shuffles[k + 5] + 8]   # the sums that feed the first shuffle .. the adds behind the last
             packed = [l for l in window if l.startswith("v_pk_")]
-            assert not packed, f"{name}: packed math in the position-gradient reduction: {packed[:3]}"
+            assert not packed, f"{name}: packed math in the position-gradient reduction (FNR_NT_MASK={mask}): {packed[:3]}"
+        if mask == "0xff":
+            assert any(l.startswith("global_load_dwordx2") and l.endswith(" nt") for l in body), "the variant under test streams the Jacobian"
 
 
 def test_streaming_accesses_share_partial_waits_only_in_known_kernels():

@@ -1,6 +1,7 @@
 """Packed-FP32 results read one NON-VALU instruction later (gfx950).  No GPU needed: hipcc cross-compiles.
 
-Round 6 finding (profiles/r06_raw/nt_hunt.md): in k_field_mlp_bwd_base_coop a `v_pk_add_f32` wrote v[22:23], ONE `ds_bpermute_b32`
+Round 6 finding (profiles/r06_raw/nt_hunt.md): in k_field_mlp_bwd_base_coop (the cooperative base-branch backward, retired since;
+its position-gradient reduction lives on in k_field_mlp_bwd_base_pw) a `v_pk_add_f32` wrote v[22:23], ONE `ds_bpermute_b32`
 followed, and the next `v_pk_add_f32` read v[22:23] — hipcc counts the DS instruction as the wait state the part needs after a
 packed / op_sel VALU result ("dst forwarding"; it puts `s_nop 0` between two such VALU instructions that are adjacent), the
 hardware evidently does not always: ~10 of 12 288 waves per launch computed a wrong sum (timing-dependent: only the waves that

@@ -1,7 +1,7 @@
 // nt_load_order.hip — may a streaming (`nt`) global load and a plain one complete OUT OF ISSUE ORDER on gfx950?
 //
 // Why it matters (round 5, DESIGN 4 "Round 5"): with `nt` loads of the encode's Jacobian in
-// k_field_mlp_bwd_base_coop, training lost its run-to-run bit-reproducibility in 4 of 4 runs.  Those were the only streaming
+// k_field_mlp_bwd_base_coop (retired since), training lost its run-to-run bit-reproducibility in 4 of 4 runs.  Those were the only streaming
 // loads of the library in flight TOGETHER WITH plain loads and stores and consumed behind PARTIAL waits
 // (`s_waitcnt vmcnt(n)`, n > 0).  hipcc's wait counts assume that vector-memory operations of a wave complete in issue
 // order (vmcnt is ONE counter on gfx9-family parts: it can only say "all but the youngest n are done").  If an `nt` access —

@@ -1,7 +1,7 @@
 // nt_visibility.hip — does a streaming (`nt`) load in kernel K2 always see what an EARLIER kernel K1 of the same stream
 // stored (plain or `nt`) — on a part whose eight XCDs have private L2s?
 //
-// Second half of round 6's hunt for what `nt` loads of the encode's Jacobian do to k_field_mlp_bwd_base_coop
+// Second half of round 6's hunt for what `nt` loads of the encode's Jacobian did to k_field_mlp_bwd_base_coop, retired since
 // (tools/microbench/nt_load_order.hip is the first half: completion ORDER is not the problem).  The probe run
 // (tests/diagnostics/nt_jac_probe.py, profiles/r06_raw/nt_jac_probe.log) shows the camera poses — fed by the position
 // gradient, i.e. by the Jacobian values the kernel loads — diverging first, and from step 0 on when the kernel waits for the

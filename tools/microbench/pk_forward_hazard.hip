@@ -1,8 +1,8 @@
 // pk_forward_hazard.hip — is ONE ds_bpermute_b32 enough of a wait state between a packed-FP32 VALU result and the VALU
 // instruction that reads it, on gfx950?
 //
-// The instruction sequence round 6's hunt ended at (k_field_mlp_bwd_base_coop as hipcc schedules it once the Jacobian's loads
-// are `nt`; profiles/r06_raw/nt_hunt.md):
+// The instruction sequence round 6's hunt ended at (k_field_mlp_bwd_base_coop, retired since, as hipcc scheduled it once the
+// Jacobian's loads were `nt`; profiles/r06_raw/nt_hunt.md):
 //     v_pk_add_f32 v[22:23], v[24:25], v[22:23] op_sel:[0,1] op_sel_hi:[1,0]     ; P: packed add, cross-half operand selects
 //     ds_bpermute_b32 v25, v35, v19                                              ; one LDS-crossbar instruction
 //     v_pk_add_f32 v[20:21], v[20:21], v[22:23]                                  ; C: reads P's result
