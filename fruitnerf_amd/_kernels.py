@@ -804,6 +804,38 @@ def adam_step_spans(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: 
                                     L.stream_ptr(params.device)), "adam_step_spans")
 
 
+def adam_step_spans_dev(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, spans, steps: Tensor,
+                        algorithm: str, beta1: float, beta2: float, eps: float, scalars: Tensor,
+                        grad_scale: Optional[Tensor] = None, found_inf: Optional[Tensor] = None, zero_grad: bool = True,
+                        weight_decay: float = 0.0) -> None:
+    """adam_step_spans without a host round trip (fnr_adam_step_spans_dev): spans = [(offset, count, lr), ...], steps =
+    int64 device tensor [len(spans)] of the steps each span has taken (advanced here unless the step is skipped),
+    grad_scale / found_inf = the one-element float device tensors a torch.amp.GradScaler hands an optimiser (or None),
+    scalars = FNR_ADAM_DEV_SCALAR_FLOATS floats of device scratch.  Nothing here reads a device value on the host."""
+    lib = L.load()
+    L.require_gpu_tensor(params, "adam_step_spans_dev: params")
+    for name, t in (("grads", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("steps", steps),
+                    ("scalars", scalars), ("grad_scale", grad_scale), ("found_inf", found_inf)):
+        if t is not None and t.device != params.device:
+            raise RuntimeError(f"adam_step_spans_dev: {name} is on {t.device}, the parameters on {params.device}")
+    if steps.dtype != torch.int64 or steps.numel() < len(spans):
+        raise RuntimeError("adam_step_spans_dev: steps must hold one int64 per span")
+    if scalars.dtype != torch.float32 or scalars.numel() < L.FNR_ADAM_DEV_SCALAR_FLOATS:
+        raise RuntimeError(f"adam_step_spans_dev: scalars must hold {L.FNR_ADAM_DEV_SCALAR_FLOATS} floats")
+    for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1):
+            raise RuntimeError(f"adam_step_spans_dev: {name} must be a one-element float32 tensor")
+    end = max((int(a) + int(n) for a, n, _ in spans), default=0)
+    if end > min(params.numel(), grads.numel(), exp_avg.numel(), exp_avg_sq.numel()):
+        raise RuntimeError("adam_step_spans_dev: a span ends beyond its buffers")
+    arr = (L.fnr_adam_span * len(spans))(*[L.fnr_adam_span(int(a), int(n), 0, float(lr), 0) for a, n, lr in spans])
+    L.check(lib.fnr_adam_step_spans_dev(L.ptr(params), L.ptr(grads), L.ptr(exp_avg), L.ptr(exp_avg_sq), len(spans), arr,
+                                        L.ptr(steps), 0 if algorithm == "adam" else 1, float(beta1), float(beta2),
+                                        float(eps), L.ptr(grad_scale), L.ptr(found_inf), float(weight_decay),
+                                        1 if zero_grad else 0, L.ptr(scalars), L.stream_ptr(params.device)),
+            "adam_step_spans_dev")
+
+
 # ---- point-cloud front-end of the counting stage ------------------------------------------------------
 
 

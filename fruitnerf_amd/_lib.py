@@ -86,6 +86,7 @@ class fnr_adam_span(C.Structure):
 
 
 FNR_MAX_ADAM_SPANS = 8
+FNR_ADAM_DEV_SCALAR_FLOATS = 32      # fnr_adam_step_spans_dev: the caller's scalar block
 FNR_MAX_PROPOSAL_LEVELS = 4
 FNR_MAX_POSITION_SOURCES = 4         # fnr_position_grad_reduce_multi
 FNR_TRAIN_PROLOGUE_MAX_JITTER = 5    # fnr_train_prologue: n_jitter in 1..5
@@ -175,6 +176,8 @@ SIGNATURES = {
     "fnr_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i64, _f, _f, _i, _vp]),
     "fnr_radam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i64, _f, _f, _i, _vp]),
     "fnr_adam_step_spans": (_i, [_vp, _vp, _vp, _vp, _i, P(fnr_adam_span), _i, _f, _f, _f, _f, _f, _i, _vp]),
+    "fnr_adam_step_spans_dev": (_i, [_vp, _vp, _vp, _vp, _i, P(fnr_adam_span), _vp, _i, _f, _f, _f, _vp, _vp, _f, _i, _vp,
+                                     _vp]),
     "fnr_cloud_workspace_bytes": (C.c_size_t, [_i64]),
     "fnr_cloud_bounds": (_i, [_vp, _i64, _vp, _vp, C.c_size_t, _vp]),
     "fnr_cloud_radius_count": (_i, [_vp, _i64, P(C.c_double), P(C.c_double), C.c_double, _i, _vp, _vp, C.c_size_t,

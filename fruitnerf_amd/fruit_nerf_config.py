@@ -13,6 +13,8 @@ module is the drop-in's counterpart:
     reference's datamanager + dataparser when its package is importable); without Nerfstudio they are `MethodSpec`
     stand-ins carrying the same data, so the registration itself is testable here.  They are built on first access
     (module `__getattr__`): importing this module never imports Nerfstudio.
+  * `optimizer_configs(method)` — the `{group: {"optimizer", "scheduler"}}` table a Nerfstudio Trainer builds its
+    `Optimizers` from, with the fused optimiser configs (`engine.optimizers`); the `MethodSpecification`s carry it.
   * `training_setup(method, model, ...)` — the optimisers of a method for this repo's own loop (`training.TrainingSteps`):
     `FusedAdam` over the model's parameter groups and `CameraOptimizer` + `CameraAdam`, configured from `METHODS`.
 
@@ -107,6 +109,29 @@ def group_schedules(method: str) -> Dict[str, dict]:
     return out
 
 
+def fused_optimizer_config(o: dict):
+    """One optimiser entry of METHODS (a group's, or the camera optimiser's) as the engine.optimizers config whose
+    setup(params) builds the fused step (ArenaAdam): what Nerfstudio's Optimizers instantiates per parameter group."""
+    from .engine.optimizers import FusedAdamOptimizerConfig, FusedRAdamOptimizerConfig
+    cls = FusedAdamOptimizerConfig if o["algorithm"] == "adam" else FusedRAdamOptimizerConfig
+    return cls(lr=o["lr"], eps=o["eps"], weight_decay=o.get("weight_decay", 0))
+
+
+def optimizer_configs(method: str) -> Dict[str, dict]:
+    """TrainerConfig.optimizers of a method for its model's parameter groups, on the fused optimiser:
+    {group: {"optimizer": FusedAdamOptimizerConfig | FusedRAdamOptimizerConfig, "scheduler": config | None}} with the
+    values of METHODS.  To opt back to torch.optim, replace an entry's "optimizer" with Nerfstudio's AdamOptimizerConfig /
+    RAdamOptimizerConfig (same lr / eps)."""
+    from .engine.schedulers import ExponentialDecaySchedulerConfig
+    out = {}
+    for name, o in METHODS[method]["optimizers"].items():
+        s = o.get("scheduler")
+        out[name] = {"optimizer": fused_optimizer_config(o),
+                     "scheduler": None if s is None else ExponentialDecaySchedulerConfig(lr_final=s["lr_final"],
+                                                                                        max_steps=s["max_steps"])}
+    return out
+
+
 def camera_optimizer_config(method: str, mode: Optional[str] = None):
     """cameras.camera_optimizers.CameraOptimizerConfig of a method (+ its optimiser algorithm)."""
     from .cameras.camera_optimizers import CameraOptimizerConfig
@@ -153,7 +178,6 @@ def _nerfstudio_spec(name: str):
     (`fruit_nerf.*`, the GPL package this plugin sits next to) when importable, Nerfstudio's vanilla ones otherwise."""
     from nerfstudio.cameras.camera_optimizers import CameraOptimizerConfig
     from nerfstudio.configs.base_config import ViewerConfig
-    from nerfstudio.engine.optimizers import AdamOptimizerConfig, RAdamOptimizerConfig
     from nerfstudio.engine.schedulers import ExponentialDecaySchedulerConfig
     from nerfstudio.engine.trainer import TrainerConfig
     from nerfstudio.plugins.types import MethodSpecification
@@ -167,18 +191,11 @@ def _nerfstudio_spec(name: str):
         from nerfstudio.pipelines.base_pipeline import VanillaPipelineConfig as PipelineConfig
     M = METHODS[name]
 
-    def optimizer(o):
-        cls = AdamOptimizerConfig if o["algorithm"] == "adam" else RAdamOptimizerConfig
-        kw = dict(lr=o["lr"], eps=o["eps"])
-        if o.get("weight_decay"):
-            kw["weight_decay"] = o["weight_decay"]
-        return cls(**kw)
-
-    def scheduler(s):
+    def scheduler(s):   # Nerfstudio's own scheduler objects (its Trainer logs and checkpoints them)
         return None if s is None else ExponentialDecaySchedulerConfig(lr_final=s["lr_final"], max_steps=s["max_steps"])
 
     cam = M["camera_optimizer"]
-    cam_kw = dict(mode=cam["mode"], optimizer=optimizer(cam))
+    cam_kw = dict(mode=cam["mode"], optimizer=fused_optimizer_config(cam))   # the pose table: a launch of its own
     if cam.get("scheduler") is not None:
         cam_kw["scheduler"] = scheduler(cam["scheduler"])
     dm = dict(M["datamanager"])
@@ -192,8 +209,9 @@ def _nerfstudio_spec(name: str):
                 datamanager=DataManagerConfig(dataparser=DataParserConfig(**parser_kw),
                                               camera_optimizer=CameraOptimizerConfig(**cam_kw), **dm),
                 model=model_config(name)),
-            optimizers={g: {"optimizer": optimizer(o), "scheduler": scheduler(o.get("scheduler"))}
-                        for g, o in M["optimizers"].items()},
+            # the fused optimiser step (engine.optimizers.ArenaAdam: GradScaler-driven without a host synchronisation)
+            optimizers={g: {"optimizer": c["optimizer"], "scheduler": scheduler(M["optimizers"][g].get("scheduler"))}
+                        for g, c in optimizer_configs(name).items()},
             viewer=ViewerConfig(num_rays_per_chunk=t["viewer_num_rays_per_chunk"]), vis="viewer"),
         description=M["description"])
 

@@ -14,7 +14,8 @@ parameter of a module tree into ONE contiguous fp32 buffer (plus a same-shaped g
 """
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+import weakref
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -79,6 +80,9 @@ class Embedding(nn.Module):
         return self.embedding.weight.mean(dim)
 
 
+_ARENAS: "weakref.WeakSet[ParamArena]" = weakref.WeakSet()   # every live arena (arena_of)
+
+
 class ParamArena:
     """Flat fp32 parameter + gradient storage for a list of (group_name, parameters)."""
 
@@ -99,6 +103,13 @@ class ParamArena:
                 off += (n + 3) // 4 * 4  # keep every tensor 16-byte aligned
             self.group_ranges[gname] = (start, off)
         self.numel = off
+        # "received gradient" marks, one per group: a count of the backward passes that wrote the group's gradient span
+        # (training.py's autograd Functions and fused_forward_backward).  A torch.optim-style optimiser over arena
+        # parameters (engine.optimizers.ArenaAdam) cannot see "no gradient" in `.grad is None` — the gradients are views
+        # of `grads` and stay attached — so it remembers the count it last consumed and skips a group whose count has not
+        # moved, as torch.optim skips parameters without a gradient.  A count instead of a flag: two optimisers may share
+        # a group.
+        self.grad_marks: Dict[str, int] = {gname: 0 for gname in self.group_ranges}
         self.params = torch.zeros(off, dtype=torch.float32, device=self.device)
         self.grads = torch.zeros(off, dtype=torch.float32, device=self.device)
         for _, p, o, n in self.entries:
@@ -106,6 +117,13 @@ class ParamArena:
             view.copy_(p.data.to(self.device, torch.float32))
             p.data = view
             p.grad = self.grads[o:o + n].view(p.shape)
+        self._slots = {o: (gname, n) for gname, _, o, n in self.entries}
+        _ARENAS.add(self)       # arena_of(): how an optimiser finds a parameter's slot
+
+    def mark_gradient(self, *groups: str) -> None:
+        """A backward pass has written the gradient spans of `groups`."""
+        for g in groups:
+            self.grad_marks[g] += 1
 
     def group_slice(self, name: str) -> slice:
         a, b = self.group_ranges[name]
@@ -119,3 +137,18 @@ class ParamArena:
         for _, p, o, n in self.entries:
             if p.grad is None or p.grad.data_ptr() != self.grads.data_ptr() + 4 * o:
                 p.grad = self.grads[o:o + n].view(p.shape)
+
+
+def arena_of(p: torch.Tensor) -> Optional[Tuple["ParamArena", str, int, int]]:
+    """(arena, group, offset, numel) of a parameter whose storage is a slot of a live ParamArena, None for any other
+    tensor — also for a parameter that has left its arena since (module.to(...) gives it storage of its own)."""
+    if not p.is_cuda or p.dtype != torch.float32:
+        return None
+    ptr = p.data_ptr()
+    for arena in list(_ARENAS):
+        base = arena.params.data_ptr()
+        if arena.params.device == p.device and base <= ptr < base + 4 * arena.numel and (ptr - base) % 4 == 0:
+            slot = arena._slots.get((ptr - base) // 4)
+            if slot is not None and slot[1] == p.numel():
+                return arena, slot[0], (ptr - base) // 4, slot[1]
+    return None

@@ -82,6 +82,7 @@ class _RenderFn(torch.autograd.Function):
         model, rctx = ctx.model, ctx.rctx
         arena = model.arena()
         arena.reattach_grads()
+        arena.mark_gradient("fields")          # (the proposal networks' gradients come from _InterlevelFn.backward)
         rays = rctx.rays
         lv = rctx.levels[-1]
         S = lv["S"]
@@ -136,6 +137,7 @@ class _FieldFn(torch.autograd.Function):
         field, rays, S = ctx.field, ctx.rays, ctx.S
         feats, selector, saved = ctx.saved
         field._arena.reattach_grads()
+        field._arena.mark_gradient("fields")
         N = rays.n * S
         dev = rays.device
         z = lambda g, *shape: (torch.zeros(*shape, device=dev) if g is None else g.reshape(*shape).float().contiguous())  # noqa: E731
@@ -178,6 +180,7 @@ class _InterlevelFn(torch.autograd.Function):
             return None, None, None, None, None, None  # proposal densities were computed under no_grad
         arena = model.arena()
         arena.reattach_grads()
+        arena.mark_gradient("proposal_networks")
         rays = rctx.rays
         up = g.reshape(1).float().contiguous()
         want_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
@@ -527,7 +530,12 @@ class FusedAdam:
 
 
 def scaler_step(optimizer: "FusedAdam", grad_scaler, skip=(), done=()) -> bool:
-    """`grad_scaler.step(optimizer)` for FusedAdam (Nerfstudio's Trainer, mixed_precision=True:
+    """Superseded for Trainer-driven runs: the method configs now build engine.optimizers.ArenaAdam, which a stock
+    `grad_scaler.step(optimizer)` drives without a host synchronisation (`_step_supports_amp_scaling`, scale and inf flag
+    read on the device).  This function remains for this repo's own loops over FusedAdam (train_iteration) and behaves
+    as before:
+
+    `grad_scaler.step(optimizer)` for FusedAdam (Nerfstudio's Trainer, mixed_precision=True:
     `grad_scaler.scale(loss).backward()` -> `optimizers.optimizer_scaler_step_all(grad_scaler)` -> `grad_scaler.update()`,
     fruit_nerf_config.py:33, fruit_pipeline.py:109).  A scaled loss reaches the arena as scaled gradients (the autograd
     Functions multiply by their upstream gradient), so the step unscales inside the Adam kernel (grad_scale = 1 / scale)
@@ -973,6 +981,9 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
         # ---- backward (what loss.backward() runs through _LossFn, _RenderFn, _InterlevelFn) ----
         arena = model.arena()
         arena.reattach_grads()
+        # (ParamArena.grad_marks: what an engine.optimizers.ArenaAdam over the same arena goes by — kept current here too,
+        #  so that a caller may mix this loop with loss.backward())
+        arena.mark_gradient(*(("fields", "proposal_networks") if prop_bwd else ("fields",)))
         d_o = d_d = None
         ray_sources = [] if ray_grads is not None else None     # (warp, euclid, S, partial) of every chain, in order
         if ray_grads is not None:

@@ -558,6 +558,30 @@ int fnr_adam_step_spans(float* params, float* grads, float* exp_avg, float* exp_
                         const fnr_adam_span* spans, int algorithm, float beta1, float beta2, float eps,
                         float grad_scale, float weight_decay, int zero_grad, void* stream);
 
+/* fnr_adam_step_spans for an optimiser that a torch.amp.GradScaler drives (torch.optim's `_step_supports_amp_scaling`
+ * protocol): what that scaler decides per step, and the spans' step counts, stay in DEVICE memory — the call contains no
+ * stream synchronisation and no copy to the host.  Per element the arithmetic of fnr_adam_step_spans, in the same order.
+ *   spans       host memory, n_spans <= FNR_MAX_ADAM_SPANS; offset / count multiples of 4, lr per span (schedulers run on
+ *               the host); the `step` field is ignored.
+ *   steps       device, int64 [n_spans], in/out: optimiser steps span k has actually TAKEN.  Advanced by 1 iff the step
+ *               is not skipped; the bias corrections (and RAdam's rho_t / rectification, "not rectified" for
+ *               rho_t <= 5) are computed on the device from the post-increment count in double and rounded to float
+ *               where fnr_adam_step_spans rounds them.
+ *   grad_scale  device float or NULL (= 1): every gradient is multiplied by (float)(1.0 / (double)*grad_scale), the
+ *               factor of GradScaler.unscale_.
+ *   found_inf   device float or NULL (= 0): when *found_inf != 0 parameters, moments and counters stay untouched bit for
+ *               bit; with zero_grad != 0 the gradient spans are zeroed all the same.
+ *   scalars     device, FNR_ADAM_DEV_SCALAR_FLOATS floats of scratch owned by the caller, consumed in stream order: calls
+ *               that share a block must be enqueued on one stream.
+ * Two launches: a one-workgroup prologue (thread k owns counter k: reads the flags and its counter, writes the span's
+ * scalars to `scalars`, bumps the counter), then the sweep, which reads `scalars` and never a counter.  All argument
+ * checks run on the host before the first launch. */
+#define FNR_ADAM_DEV_SCALAR_FLOATS 32
+int fnr_adam_step_spans_dev(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int n_spans,
+                            const fnr_adam_span* spans, int64_t* steps, int algorithm, float beta1, float beta2,
+                            float eps, const float* grad_scale, const float* found_inf, float weight_decay,
+                            int zero_grad, float* scalars, void* stream);
+
 /* ---- step programs: a training step's launch sequence, recorded once and replayed natively (ABI 12) ------------- */
 /* The reference's loop is nerfstudio's Python Trainer (fruit_pipeline.py:120-146 under Trainer.train_iteration); ours
  * (fruitnerf_amd/training.py::TrainingSteps) is ~30 calls of this ABI per step on two HIP streams.  Every pointer of a
