@@ -663,6 +663,13 @@ def hash_encode_bwd_adam(grid_grad: L.fnr_grid, warp: L.fnr_warp, rays: RaysArg,
                    "hash_encode_bwd_adam", rays.device)
 
 
+def _prop_bwd_buffers(net: L.fnr_prop_net, rays: RaysArg, S: int, want_position_grad: bool, tag: str):
+    """One proposal level's backward -> (workspace, its size, clean flag, d_position [N,4] | None)."""
+    nbytes = L.load().fnr_prop_density_bwd_workspace_bytes(rays.n * S, net.grid.n_levels, net.grid.log2_hashmap_size)
+    ws, clean = _scatter_workspace(rays.device, nbytes, tag)
+    return ws, nbytes, clean, (_empty(rays.n * S, 4, device=rays.device) if want_position_grad else None)
+
+
 def prop_density_bwd(net: L.fnr_prop_net, grads: L.fnr_prop_net, warp: L.fnr_warp, rays: RaysArg, euclid: Tensor,
                      S: int, feats: Tensor, d_density: Tensor, want_position_grad: bool = False,
                      adam=None) -> Optional[Tensor]:
@@ -670,20 +677,15 @@ def prop_density_bwd(net: L.fnr_prop_net, grads: L.fnr_prop_net, warp: L.fnr_war
     adam = (table fnr_table_adam, weight fnr_table_adam, gradient arena): the network's optimiser step is taken by the
     kernels that finish its gradients (fnr_prop_density_bwd_adam)."""
     lib = L.load()
-    nbytes = lib.fnr_prop_density_bwd_workspace_bytes(rays.n * S, net.grid.n_levels, net.grid.log2_hashmap_size)
-    ws, clean = _scatter_workspace(rays.device, nbytes, "prop")
-    d_pos = _empty(rays.n * S, 4, device=rays.device) if want_position_grad else None
+    ws, nbytes, clean, d_pos = _prop_bwd_buffers(net, rays, S, want_position_grad, "prop")
+    head = (C.byref(net), C.byref(grads), C.byref(warp), rays.ref, L.ptr(euclid), S, L.ptr(feats), L.ptr(d_density), L.ptr(d_pos))
+    tail = (L.ptr(ws), nbytes, clean, L.stream_ptr(rays.device))
     if adam is not None:
         t_adam, w_adam, grad_arena = adam
-        _scatter_check(lib.fnr_prop_density_bwd_adam(C.byref(net), C.byref(grads), C.byref(warp), rays.ref, L.ptr(euclid), S,
-                                                     L.ptr(feats), L.ptr(d_density), L.ptr(d_pos), C.byref(t_adam),
-                                                     C.byref(w_adam), L.ptr(grad_arena), L.ptr(ws), nbytes, clean,
-                                                     L.stream_ptr(rays.device)), "prop_density_bwd_adam", rays.device)
-        return d_pos
-    _scatter_check(lib.fnr_prop_density_bwd(C.byref(net), C.byref(grads), C.byref(warp), rays.ref, L.ptr(euclid), S,
-                                            L.ptr(feats), L.ptr(d_density), L.ptr(d_pos), L.ptr(ws), nbytes, clean,
-                                            L.stream_ptr(rays.device)),
-                   "prop_density_bwd", rays.device)
+        _scatter_check(lib.fnr_prop_density_bwd_adam(*head, C.byref(t_adam), C.byref(w_adam), L.ptr(grad_arena), *tail),
+                       "prop_density_bwd_adam", rays.device)
+    else:
+        _scatter_check(lib.fnr_prop_density_bwd(*head, *tail), "prop_density_bwd", rays.device)
     return d_pos
 
 
@@ -695,12 +697,7 @@ def prop_density_bwd_pair(nets, grads, warps, rays: RaysArg, euclids, S, feats, 
     the current stream once the d_position tensors are final, then the scatter."""
     lib = L.load()
     dev = rays.device
-    ws, nbytes, clean, d_pos = [], [], [], []
-    for q in range(2):
-        nb = lib.fnr_prop_density_bwd_workspace_bytes(rays.n * S[q], nets[q].grid.n_levels, nets[q].grid.log2_hashmap_size)
-        w, c = _scatter_workspace(dev, nb, f"prop{q}")
-        ws.append(w), nbytes.append(nb), clean.append(c)
-        d_pos.append(_empty(rays.n * S[q], 4, device=dev) if want_position_grad else None)
+    ws, nbytes, clean, d_pos = zip(*[_prop_bwd_buffers(nets[q], rays, S[q], want_position_grad, f"prop{q}") for q in range(2)])
     PN, PW, PT = C.POINTER(L.fnr_prop_net), C.POINTER(L.fnr_warp), C.POINTER(L.fnr_table_adam)
     vp = lambda ts: (C.c_void_p * 2)(*[L.ptr(t) for t in ts])   # noqa: E731
     t_adams = w_adam = grad_arena = None
@@ -717,7 +714,7 @@ def prop_density_bwd_pair(nets, grads, warps, rays: RaysArg, euclids, S, feats, 
                        "prop_density_bwd_pair_split", dev)
     else:
         _scatter_check(lib.fnr_prop_density_bwd_pair(*args), "prop_density_bwd_pair", dev)
-    return d_pos
+    return list(d_pos)
 
 
 def hash_encode_input_grad(grid: L.fnr_grid, warp: L.fnr_warp, rays: RaysArg, euclid: Tensor, S: int,

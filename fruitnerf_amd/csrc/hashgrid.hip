@@ -1,5 +1,6 @@
 // hashgrid.hip — multiresolution hash-grid encode (HashEncoding torch semantics) and the fused
-// proposal-network density kernel, for gfx950 (forward; the backward lives in hash_scatter.hip).
+// proposal-network density kernel, for gfx950 (forward; the backward: hash_scatter.hip for the
+// encode, prop_bwd.hip for the proposal networks).
 //
 // Roofline: HBM/L2-bound random 8-byte gathers (8 corners x L levels per sample, 64 B/level
 // algorithmic).  Layout decisions:

@@ -191,32 +191,20 @@ class _InterlevelFn(torch.autograd.Function):
 
 
 def _proposal_backward(model, rctx, d_wps, upstream: Optional[Tensor], d_origins: Optional[Tensor],
-                       d_directions: Optional[Tensor], level_streams: bool = False,
-                       collect: Optional[list] = None, optimizer: Optional["FusedAdam"] = None,
-                       position_ready=None) -> bool:
+                       d_directions: Optional[Tensor], collect: Optional[list] = None,
+                       optimizer: Optional["FusedAdam"] = None, position_ready=None) -> bool:
     """Backward of the interlevel loss into the proposal networks (and, when asked, into the rays).
     position_ready (torch.cuda.Event, with collect): recorded as soon as the collected d_position tensors are final,
     ahead of the levels' scatter (fnr_prop_density_bwd_pair_split) -> True when it was (the paired path), else False.
     upstream None: d_wps already holds d(loss)/d(density) per level (train_losses(fuse_weights_bwd=True)).
-    level_streams: the levels' chains (MLP backward -> weight reduce -> scatter emit -> accumulate; they share nothing when
-    every level has its own network) run side by side, level 0 on the current stream and the others on side streams;
-    their ray-gradient sums (+= into the same [R,3] buffers) follow on the current stream after the join.
     collect: a list that receives the levels' ray-gradient sources (warp, euclid, S, d_position) INSTEAD of their
     reduction into d_origins / d_directions — the caller reduces all sources of the step in one launch.
     optimizer: the networks' optimiser steps are taken by the kernels that finish their gradients
     (fnr_prop_density_bwd_adam; single process, one network per level)."""
     cfg = model.config
     rays = rctx.rays
-    dev = rays.device
     levels = list(zip(rctx.levels[:-1], d_wps))
-    side_by_side = level_streams and len(levels) > 1 and not cfg.use_same_proposal_network
-    main = torch.cuda.current_stream(dev) if side_by_side else None
-    pool = model.__dict__.setdefault("_level_streams", []) if side_by_side else []
-    while side_by_side and len(pool) < len(levels) - 1:
-        pool.append(torch.cuda.Stream(device=dev))
-    pending = []
-    if PAIR_PROPOSAL_LEVELS and len(levels) == 2 and not cfg.use_same_proposal_network and not side_by_side \
-            and upstream is None:
+    if PAIR_PROPOSAL_LEVELS and len(levels) == 2 and not cfg.use_same_proposal_network and upstream is None:
         # both levels through one entry point: their accumulate launches run as one (fnr_prop_density_bwd_pair)
         nets = [model.proposal_networks[0], model.proposal_networks[1]]
         adam = None
@@ -239,42 +227,23 @@ def _proposal_backward(model, rctx, d_wps, upstream: Optional[Tensor], d_origins
         return position_ready is not None and collect is not None
     for i, (lv, d_wp) in enumerate(levels):
         net = model.proposal_networks[0 if cfg.use_same_proposal_network else i]
-        stream = pool[i - 1] if side_by_side and i > 0 else None
-        if stream is not None:
-            stream.wait_stream(main)
-        with torch.cuda.stream(stream) if stream is not None else _null_context():
-            d_density = d_wp if upstream is None else \
-                K.weights_bwd(lv["S"], lv["euclid"], lv["density"], lv["weights"], d_wp, upstream)
-            adam = None
-            if optimizer is not None:
-                t_adam, _ = optimizer.table_adam_args(net.encoding.hash_table, "proposal_networks")
-                (w_adam, grad_arena), _ = optimizer.weight_adam_args("proposal_networks")
-                adam = (t_adam, w_adam, grad_arena)
-            d_pos = K.prop_density_bwd(net.prop_struct(), net.prop_struct(grads=True), net.warp_struct(), rays,
-                                       lv["euclid"], lv["S"], lv["feats"], d_density,
-                                       want_position_grad=d_origins is not None, adam=adam)
+        d_density = d_wp if upstream is None else \
+            K.weights_bwd(lv["S"], lv["euclid"], lv["density"], lv["weights"], d_wp, upstream)
+        adam = None
+        if optimizer is not None:
+            t_adam, _ = optimizer.table_adam_args(net.encoding.hash_table, "proposal_networks")
+            (w_adam, grad_arena), _ = optimizer.weight_adam_args("proposal_networks")
+            adam = (t_adam, w_adam, grad_arena)
+        d_pos = K.prop_density_bwd(net.prop_struct(), net.prop_struct(grads=True), net.warp_struct(), rays,
+                                   lv["euclid"], lv["S"], lv["feats"], d_density,
+                                   want_position_grad=d_origins is not None, adam=adam)
         if d_origins is None:
             continue
         if collect is not None:
             collect.append((net.warp_struct(), lv["euclid"], lv["S"], d_pos))
-        elif side_by_side:
-            pending.append((net, lv, d_pos, stream))
         else:
             K.position_grad_reduce(net.warp_struct(), rays, lv["euclid"], lv["S"], d_pos, d_origins, d_directions)
-    for stream in pool[:len(levels) - 1] if side_by_side else ():
-        main.wait_stream(stream)
-    for net, lv, d_pos, stream in pending:
-        if stream is not None:
-            d_pos.record_stream(main)
-        K.position_grad_reduce(net.warp_struct(), rays, lv["euclid"], lv["S"], d_pos, d_origins, d_directions)
-
-
-class _null_context:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
+    return False
 
 
 class _LossFn(torch.autograd.Function):
@@ -1130,8 +1099,7 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
             for src in ray_sources or ():
                 src[3].record_stream(main)
         elif prop_bwd:
-            _proposal_backward(model, rctx, d_wps, up, d_o, d_d, level_streams=PROPOSAL_LEVEL_STREAMS,
-                               collect=ray_sources, optimizer=proposal_optimizer)
+            _proposal_backward(model, rctx, d_wps, up, d_o, d_d, collect=ray_sources, optimizer=proposal_optimizer)
         if ray_grads is not None:
             # one launch: proposal levels first, the field last (the order the separate launches added them in)
             K.position_grad_reduce_multi(ray_sources + [field_source], rays, d_o, d_d, accumulate=False)
@@ -1187,11 +1155,6 @@ OVERLAP_PROPOSAL_BACKWARD = os.environ.get("FNR_OVERLAP_PROPOSAL_BACKWARD", "1")
 # pools between steps (one-stream and two-stream steps alternating made the caching allocator grow both pools: hipMalloc
 # calls inside bench.py's timed window)
 SERIALIZE_STREAMS = os.environ.get("FNR_SERIALIZE_STREAMS") == "1"   # (profiling runs: tools/gpu_call.sh, legs kt / pmc)
-# The proposal levels' backward chains next to each other (level 0 on the launch stream, level 1 on a side stream; they
-# share no buffers).  OFF: measured on MI355X (round 3, A/B on one box) the step gets 4 % SLOWER (0.908 -> 0.943 ms) — a
-# cross-stream fork + join costs ~12 us of GPU time per handshake on this stack and the two chains of latency-bound
-# kernels slow each other in the XCDs' L2s (each network's 5 MB tables fit one L2, two do not).  Kept for measurements.
-PROPOSAL_LEVEL_STREAMS = os.environ.get("FNR_PROPOSAL_LEVEL_STREAMS", "0") == "1"
 PAIR_PROPOSAL_LEVELS = os.environ.get("FNR_PAIR_PROPOSAL_LEVELS", "1") != "0"   # see _proposal_backward
 # The losses launch on the second stream, the composite backward forming its own per-ray loss gradients (see
 # fused_forward_backward).  FNR_LOSSES_ON_SIDE=0: losses on the launch stream ahead of the backward, as before (A/B).

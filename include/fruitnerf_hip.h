@@ -431,7 +431,8 @@ int fnr_camera_pose_grad_adam(const fnr_image_set* set, const int64_t* train_ids
 /* Backward of fnr_prop_density_fwd: d_density [R,S] -> += into grads (table, w0, b0, w1, b1).
  * d_position (optional) [N,4]: gradient w.r.t. each sample's unit-cube position (xyz, w = 0) for
  * fnr_position_grad_reduce(n_levels = 1) — only needed when the rays carry gradients (camera-pose optimiser).
- * workspace >= fnr_prop_density_bwd_workspace_bytes(N, L, log2_hashmap_size). */
+ * workspace >= fnr_prop_density_bwd_workspace_bytes(N, L, log2_hashmap_size).  (prop_bwd.hip: these four entry points
+ * compose the same launches; the table's part goes through the binned scatter of hash_scatter.hip.) */
 size_t fnr_prop_density_bwd_workspace_bytes(int64_t n_samples, int n_levels, int log2_hashmap_size);
 int fnr_prop_density_bwd(const fnr_prop_net* net, const fnr_prop_net* grads, const fnr_warp* warp,
                          const fnr_rays* rays, const float* euclid_bins, int S, const float* feat_save,

@@ -110,6 +110,99 @@ def test_paired_proposal_levels_are_the_separate_calls(dev):
         assert torch.equal(x, y)
 
 
+def test_the_four_proposal_backward_exports_agree_bit_for_bit(dev):
+    """fnr_prop_density_bwd(_adam) once per level, fnr_prop_density_bwd_pair, fnr_prop_density_bwd_pair_split (with its
+    event) and fnr_prop_density_bwd_pair with the levels in the other order — so that either level is the 'longer' one of
+    the joint accumulate launch — on ONE input: the contract of include/fruitnerf_hip.h, bit for bit.  The launches are
+    the same, the weight sums have one writer that adds the workgroups' partial vectors in workgroup order, the workgroup
+    count depends on N alone, and the scatter sums in 64-bit fixed point.
+    The two proposal networks of `fruit_nerf` (5 levels, 2^17 rows, hidden 16) on 37 rays at the model's sample counts:
+    37 x 256 and 37 x 96 samples, both more than one pass of a workgroup, different, the second a multiple of neither
+    256 nor 512.  Without optimiser descriptors the d_position tensors and the networks' gradients are compared, with
+    them (from identical starting states) d_position and the networks' parameters and both moments."""
+    from fruitnerf_amd import _kernels as K
+    from fruitnerf_amd.data.semantics import apple_metadata
+    from fruitnerf_amd.fruit_nerf import FruitModel, FruitNerfModelConfig
+    from fruitnerf_amd.training import FusedAdam
+    R = 37
+    torch.manual_seed(0)
+    model = FruitModel(FruitNerfModelConfig(), apple_metadata(), num_train_data=16, device=dev)
+    model.train()
+    nets = list(model.proposal_networks)
+    S = [int(s) for s in model.config.num_proposal_samples_per_ray]
+    assert len(nets) == 2 and all(n.encoding.num_levels == 5 and n.encoding.log2_hashmap_size == 17 and n.hidden_dim == 16
+                                  for n in nets)
+    assert S[0] != S[1] and min(R * s for s in S) > 256 and any((R * s) % 256 for s in S)
+    g = torch.Generator(device=dev).manual_seed(7)
+    with torch.no_grad():     # trained-like tables: O(1) features, densities that are not all alike
+        for net in nets:
+            net.encoding.hash_table.copy_((torch.rand(net.encoding.hash_table.shape, device=dev, generator=g) * 2 - 1) * 0.8)
+    arena = model.arena()
+    arena.reattach_grads()
+    opt = FusedAdam(model)
+    opt.begin_step()
+    o, d, _, cam = util.random_rays(R, 16, seed=3)
+    rays = K.RaysArg(o.to(dev), d.to(dev), torch.full((R, 1), 0.05, device=dev), torch.full((R, 1), 1000.0, device=dev),
+                     cam.to(dev))
+    spacing, euclid0 = K.sample_spaced(rays, 1, S[0], torch.rand(R, device=dev, generator=g))
+    dens0, feats0 = K.prop_density_fwd(nets[0].prop_struct(), nets[0].warp_struct(), rays, euclid0, S[0], save_feats=True)
+    _, _, _, euclid1 = K.weights_pdf(rays, 1, S[0], S[1], dens0, spacing, euclid0, 1.0, torch.rand(R, device=dev, generator=g))
+    _, feats1 = K.prop_density_fwd(nets[1].prop_struct(), nets[1].warp_struct(), rays, euclid1, S[1], save_feats=True)
+    euclid, feats = [euclid0, euclid1], [feats0, feats1]
+    dd = [1e-2 * torch.randn(R, s, device=dev, generator=g) for s in S]
+    a, b = arena.group_ranges["proposal_networks"]
+    start = (arena.params[a:b].clone(), opt.exp_avg[a:b].clone(), opt.exp_avg_sq[a:b].clone())
+
+    def run(variant, fused):
+        arena.params[a:b].copy_(start[0])
+        opt.exp_avg[a:b].copy_(start[1])
+        opt.exp_avg_sq[a:b].copy_(start[2])
+        arena.grads[a:b].zero_()
+        opt.rebuild_touched()
+        t_adams = w_adam = grad_arena = None
+        if fused:
+            t_adams = [opt.table_adam_args(n.encoding.hash_table, "proposal_networks")[0] for n in nets]
+            (w_adam, grad_arena), _ = opt.weight_adam_args("proposal_networks")
+        order = [1, 0] if variant == "pair, levels swapped" else [0, 1]
+        if variant == "one call per level":
+            d_pos = [K.prop_density_bwd(nets[q].prop_struct(), nets[q].prop_struct(grads=True), nets[q].warp_struct(), rays,
+                                        euclid[q], S[q], feats[q], dd[q], want_position_grad=True,
+                                        adam=(t_adams[q], w_adam, grad_arena) if fused else None) for q in order]
+        else:
+            pick = lambda xs: [xs[q] for q in order]   # noqa: E731
+            d_pos = K.prop_density_bwd_pair(pick([n.prop_struct() for n in nets]), pick([n.prop_struct(grads=True) for n in nets]),
+                                            pick([n.warp_struct() for n in nets]), rays, pick(euclid), pick(S), pick(feats),
+                                            pick(dd), want_position_grad=True,
+                                            adam=(pick(t_adams), w_adam, grad_arena) if fused else None,
+                                            position_ready=K.Event() if variant == "pair_split" else None)
+        torch.cuda.synchronize()
+        out = {f"d_position[{q}]": dp.clone() for q, dp in zip(order, d_pos)}
+        if fused:
+            out.update(parameters=arena.params[a:b].clone(), exp_avg=opt.exp_avg[a:b].clone(),
+                       exp_avg_sq=opt.exp_avg_sq[a:b].clone())
+        else:
+            for q, n in enumerate(nets):
+                lyr = n.mlp_base[1].layers
+                for name, p in (("table", n.encoding.hash_table), ("w0", lyr[0].weight), ("b0", lyr[0].bias),
+                                ("w1", lyr[1].weight), ("b1", lyr[1].bias)):
+                    out[f"grad of {name}[{q}]"] = p.grad.clone()
+        return out
+
+    for fused in (False, True):
+        ref = run("one call per level", fused)
+        moved = [k for k, v in ref.items() if k not in ("parameters", "exp_avg_sq") and bool((v != 0).any())]
+        assert len(moved) == len(ref) - (2 if fused else 0), f"the reference run left something at zero: {sorted(ref)} vs {moved}"
+        if fused:
+            assert not torch.equal(ref["parameters"], start[0]) and bool((ref["exp_avg_sq"] != 0).any())
+        for variant in ("pair", "pair_split", "pair, levels swapped"):
+            got = run(variant, fused)
+            assert sorted(got) == sorted(ref)
+            for k in ref:
+                n_diff = int((got[k] != ref[k]).sum())
+                assert torch.equal(got[k], ref[k]), \
+                    f"{variant} ({'fused optimiser' if fused else 'gradients'}): {k} differs from one call per level in {n_diff} entries"
+
+
 @pytest.mark.parametrize("mlp_precision", ["bf16x3", "fp32"])
 def test_losses_on_the_second_stream_change_nothing(dev, mlp_precision):
     """training.LOSSES_ON_SIDE (round 5): the losses launch heads the second stream's segment and the composite backward

@@ -20,13 +20,19 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 @pytest.fixture(scope="module")
 def scatter_asm(tmp_path_factory):
+    """The binned scatter (hash_scatter.hip: emit and accumulate kernels) and the proposal networks' backward that feeds it
+    (prop_bwd.hip) -> {source: lines of its assembly}."""
     if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
         pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("isa") / "hash_scatter.s"
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off",
-           "-S", "--cuda-device-only", "-o", str(out), os.path.join(CSRC, "hash_scatter.hip")]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    return out.read_text().split("\n")
+    tmp = tmp_path_factory.mktemp("isa")
+    asm = {}
+    for src in ("hash_scatter.hip", "prop_bwd.hip"):
+        out = tmp / (src[:-4] + ".s")
+        cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off",
+               "-S", "--cuda-device-only", "-o", str(out), os.path.join(CSRC, src)]
+        subprocess.run(cmd, check=True, capture_output=True, timeout=600)
+        asm[src] = out.read_text().split("\n")
+    return asm
 
 
 def _kernel(lines, mangled_prefix):
@@ -39,7 +45,7 @@ def _kernel(lines, mangled_prefix):
 @pytest.mark.parametrize("name,copies", [("_ZN3fnr20k_scatter_accumulateILb1EEE", 1), ("_ZN3fnr20k_scatter_accumulateILb0EEE", 1),
                                          ("_ZN3fnr21k_scatter_accumulate2ILb1EEE", 2), ("_ZN3fnr21k_scatter_accumulate2ILb0EEE", 2)])
 def test_counter_loads_are_waited_for_ahead_of_the_reset_barrier(scatter_asm, name, copies):
-    body = _kernel(scatter_asm, name)
+    body = _kernel(scatter_asm["hash_scatter.hip"], name)   # the file that instantiates the accumulate kernels
     waits = [i for i, l in enumerate(body) if l.startswith("s_waitcnt vmcnt(0) lgkmcnt(0)") and body[i - 1].startswith(";;#ASMSTART")]
     assert len(waits) == copies, f"{name}: {len(waits)} explicit counter waits for {copies} inlined copies of accumulate_bin"
     for w in waits:
@@ -56,11 +62,16 @@ def test_counter_loads_are_waited_for_ahead_of_the_reset_barrier(scatter_asm, na
 def test_scatter_kernels_use_no_scratch_and_keep_three_emit_workgroups_per_cu(scatter_asm):
     """Resource facts DESIGN 4 relies on: no scatter kernel spills (scratch would also make them the only scratch users of the
     `fruit_nerf` step), and the emit kernel's static LDS lets three workgroups share a CU's 160 KiB."""
-    text = "\n".join(scatter_asm)
-    meta = re.findall(r"\.group_segment_fixed_size:\s*(\d+)\s*\n(?:.*\n)*?\s*\.name:\s*(\S+)\s*\n(?:.*\n)*?\s*\.private_segment_fixed_size:\s*(\d+)"
-                      r"(?:.*\n)*?\s*\.vgpr_spill_count:\s*(\d+)", text)
-    kernels = {name: (int(lds), int(scratch), int(spill)) for lds, name, scratch, spill in meta if name.startswith("_ZN3fnr")}
+    kernels = {}
+    for src, lines in scatter_asm.items():
+        meta = re.findall(r"\.group_segment_fixed_size:\s*(\d+)\s*\n(?:.*\n)*?\s*\.name:\s*(\S+)\s*\n(?:.*\n)*?\s*\.private_segment_fixed_size:\s*(\d+)"
+                          r"(?:.*\n)*?\s*\.vgpr_spill_count:\s*(\d+)", "\n".join(lines))
+        for lds, name, scratch, spill in meta:
+            if name.startswith("_ZN3fnr"):
+                assert name not in kernels, f"{name} is instantiated in both files"
+                kernels[name] = (int(lds), int(scratch), int(spill))
     assert len(kernels) >= 20, sorted(kernels)
+    assert sum("k_scatter_emit" in name for name in kernels) == 2
     for name, (lds, scratch, spill) in kernels.items():
         assert scratch == 0 and spill == 0, (name, scratch, spill)
         if "k_scatter_emit" in name:
@@ -132,7 +143,7 @@ def test_streaming_accesses_share_partial_waits_only_in_known_kernels():
     import isa_nt_scan
     known = ("k_scatter_accumulate", "k_prop_bwd", "k_scatter_emit", "k_hash_encode", "k_prop_density", "k_adam", "k_radam")
     seen = set()
-    for src in ("hash_scatter.hip", "hashgrid.hip", "field_mlp_bf16.hip", "field_mlp_bwd_pw.hip", "position_grad.hip", "train.hip"):
+    for src in ("hash_scatter.hip", "prop_bwd.hip", "hashgrid.hip", "field_mlp_bf16.hip", "field_mlp_bwd_pw.hip", "position_grad.hip", "train.hip"):
         for k, r in isa_nt_scan.scan_source(os.path.join(CSRC, src)).items():
             if r["mixed"]:
                 fam = [f for f in known if f in k]
