@@ -949,6 +949,32 @@ class ImageSetArg:
                                  float(cx), float(cy))
 
 
+class CameraTableArg:
+    """fnr_camera_table: per-image intrinsics [M,4] (fx, fy, cx, cy) and optional OpenCV distortion [M,6] (k1, k2, k3, k4,
+    p1, p2 — nerfstudio's distortion_params order), rows indexed by dataset image like c2w.  Selects the _cams entry
+    points wherever an image set is passed (the set's own fx..cy are then ignored)."""
+
+    def __init__(self, intrinsics: Tensor, distortion: Optional[Tensor] = None):
+        L.require_gpu_tensor(intrinsics, "intrinsics")
+        assert intrinsics.dim() == 2 and intrinsics.shape[1] == 4, "intrinsics is [M,4] (fx, fy, cx, cy)"
+        self.intrinsics = _f32c(intrinsics)
+        self.distortion = None
+        if distortion is not None:
+            assert distortion.shape == (intrinsics.shape[0], 6), "distortion is [M,6] (k1, k2, k3, k4, p1, p2)"
+            self.distortion = _f32c(distortion.to(intrinsics.device))
+        self.c = L.fnr_camera_table(self.intrinsics.data_ptr(),
+                                    None if self.distortion is None else self.distortion.data_ptr())
+
+    def pointers(self) -> tuple:
+        return (self.intrinsics.data_ptr(), None if self.distortion is None else self.distortion.data_ptr())
+
+    def ref(self, image_set: "ImageSetArg"):
+        """byref() of the struct for a call next to `image_set`: the kernels index the rows by dataset image."""
+        if self.intrinsics.shape[0] != image_set.c.n_images:
+            raise ValueError(f"camera table of {self.intrinsics.shape[0]} rows for an image set of {image_set.c.n_images}")
+        return C.byref(self.c)
+
+
 def camera_adjust(image_set: ImageSetArg, train_ids: Tensor, pose_adjustment: Tensor) -> Tensor:
     """c2w' [n_train,3,4] = multiply(c2w[train_ids], exp_map_SO3xR3(pose_adjustment))."""
     lib = L.load()
@@ -960,31 +986,41 @@ def camera_adjust(image_set: ImageSetArg, train_ids: Tensor, pose_adjustment: Te
 
 
 def camera_pose_grad(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, cam: Tensor, pose_adjustment: Tensor,
-                     c2w_adjusted: Tensor, d_origins: Tensor, d_directions: Tensor, pose_grad: Tensor) -> None:
-    """pose_grad [n_train,6] += d(loss)/d(pose_adjustment) from the ray gradients of the rays drawn with `u`."""
+                     c2w_adjusted: Tensor, d_origins: Tensor, d_directions: Tensor, pose_grad: Tensor,
+                     cams: Optional[CameraTableArg] = None) -> None:
+    """pose_grad [n_train,6] += d(loss)/d(pose_adjustment) from the ray gradients of the rays drawn with `u`
+    (cams: through that camera table, fnr_camera_pose_grad_cams)."""
     lib = L.load()
     ids = train_ids.to(torch.int64).contiguous()
-    L.check(lib.fnr_camera_pose_grad(C.byref(image_set.c), L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)),
-                                     L.ptr(cam), L.ptr(_f32c(pose_adjustment)), L.ptr(c2w_adjusted), L.ptr(d_origins),
-                                     L.ptr(d_directions), L.ptr(pose_grad), L.stream_ptr(u.device)), "camera_pose_grad")
+    rest = (L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)), L.ptr(cam), L.ptr(_f32c(pose_adjustment)),
+            L.ptr(c2w_adjusted), L.ptr(d_origins), L.ptr(d_directions), L.ptr(pose_grad), L.stream_ptr(u.device))
+    if cams is None:
+        L.check(lib.fnr_camera_pose_grad(C.byref(image_set.c), *rest), "camera_pose_grad")
+    else:
+        L.check(lib.fnr_camera_pose_grad_cams(C.byref(image_set.c), cams.ref(image_set), *rest), "camera_pose_grad_cams")
 
 
 def camera_pose_grad_adam(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, cam: Tensor, c2w_adjusted: Tensor,
-                          d_origins: Tensor, d_directions: Tensor, pose_grad: Tensor, adam: L.fnr_table_adam) -> None:
+                          d_origins: Tensor, d_directions: Tensor, pose_grad: Tensor, adam: L.fnr_table_adam,
+                          cams: Optional[CameraTableArg] = None) -> None:
     """camera_pose_grad + the pose table's Adam / RAdam step (adam.params = pose_adjustment) in one launch; pose_grad
     is consumed and left zero."""
     lib = L.load()
     ids = train_ids.to(torch.int64).contiguous()
-    L.check(lib.fnr_camera_pose_grad_adam(C.byref(image_set.c), L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)),
-                                          L.ptr(cam), L.ptr(c2w_adjusted), L.ptr(d_origins), L.ptr(d_directions),
-                                          L.ptr(pose_grad), C.byref(adam), L.stream_ptr(u.device)),
-            "camera_pose_grad_adam")
+    rest = (L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)), L.ptr(cam), L.ptr(c2w_adjusted), L.ptr(d_origins),
+            L.ptr(d_directions), L.ptr(pose_grad), C.byref(adam), L.stream_ptr(u.device))
+    if cams is None:
+        L.check(lib.fnr_camera_pose_grad_adam(C.byref(image_set.c), *rest), "camera_pose_grad_adam")
+    else:
+        L.check(lib.fnr_camera_pose_grad_adam_cams(C.byref(image_set.c), cams.ref(image_set), *rest),
+                "camera_pose_grad_adam_cams")
 
 
 def train_prologue(image_set: ImageSetArg, train_ids: Tensor, n_rays: int, seed: int, offset: int,
                    pose_adjustment: Optional[Tensor], near: float, far: float, S0: int, n_jitter: int = 3,
-                   spacing_kind: int = 1) -> dict:
-    """fnr_train_prologue: random numbers + camera adjust + pixel sampling + level-0 spaced sampling in one launch."""
+                   spacing_kind: int = 1, cams: Optional[CameraTableArg] = None) -> dict:
+    """fnr_train_prologue: random numbers + camera adjust + pixel sampling + level-0 spaced sampling in one launch
+    (cams: rays through that camera table, fnr_train_prologue_cams)."""
     lib = L.load()
     dev = image_set.images.device
     R = int(n_rays)
@@ -1000,17 +1036,21 @@ def train_prologue(image_set: ImageSetArg, train_ids: Tensor, n_rays: int, seed:
         "S0": S0, "near": float(near), "far": float(far), "spacing_kind": spacing_kind,
     }
     base = host_linspace(0.0, 1.0, S0 + 1, dev)
-    L.check(lib.fnr_train_prologue(C.byref(image_set.c), L.ptr(ids), n_train, R, int(seed) & (2 ** 64 - 1),
-                                   int(offset) & (2 ** 64 - 1),
-                                   L.ptr(_f32c(pose_adjustment)) if pose_adjustment is not None else None,
-                                   L.ptr(out["c2w_adjusted"]), L.ptr(out["u"]), L.ptr(out["jitter"]), n_jitter,
-                                   L.ptr(out["origins"]), L.ptr(out["directions"]), L.ptr(out["cam"]), L.ptr(out["image"]),
-                                   L.ptr(out["mask"]), float(near), float(far), spacing_kind, S0, L.ptr(base),
-                                   L.ptr(out["spacing"]), L.ptr(out["euclid"]), L.stream_ptr(dev)), "train_prologue")
+    rest = (L.ptr(ids), n_train, R, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+            L.ptr(_f32c(pose_adjustment)) if pose_adjustment is not None else None,
+            L.ptr(out["c2w_adjusted"]), L.ptr(out["u"]), L.ptr(out["jitter"]), n_jitter,
+            L.ptr(out["origins"]), L.ptr(out["directions"]), L.ptr(out["cam"]), L.ptr(out["image"]),
+            L.ptr(out["mask"]), float(near), float(far), spacing_kind, S0, L.ptr(base),
+            L.ptr(out["spacing"]), L.ptr(out["euclid"]), L.stream_ptr(dev))
+    if cams is None:
+        L.check(lib.fnr_train_prologue(C.byref(image_set.c), *rest), "train_prologue")
+    else:
+        L.check(lib.fnr_train_prologue_cams(C.byref(image_set.c), cams.ref(image_set), *rest), "train_prologue_cams")
     return out
 
 
-def sample_pixels(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, c2w_adjusted: Optional[Tensor] = None):
+def sample_pixels(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, c2w_adjusted: Optional[Tensor] = None,
+                  cams: Optional[CameraTableArg] = None):
     lib = L.load()
     dev = u.device
     R = u.shape[0]
@@ -1020,7 +1060,27 @@ def sample_pixels(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, c2w_adju
     cam = _empty(R, dtype=torch.int32, device=dev)
     image = _empty(R, 3, device=dev)
     mask = _empty(R, device=dev)
-    L.check(lib.fnr_sample_pixels(C.byref(image_set.c), L.ptr(ids), ids.numel(), R, L.ptr(_f32c(u)),
-                                  L.ptr(c2w_adjusted), L.ptr(origins), L.ptr(directions), L.ptr(cam), L.ptr(image), L.ptr(mask), L.stream_ptr(dev)),
-            "sample_pixels")
+    rest = (L.ptr(ids), ids.numel(), R, L.ptr(_f32c(u)), L.ptr(c2w_adjusted), L.ptr(origins), L.ptr(directions),
+            L.ptr(cam), L.ptr(image), L.ptr(mask), L.stream_ptr(dev))
+    if cams is None:
+        L.check(lib.fnr_sample_pixels(C.byref(image_set.c), *rest), "sample_pixels")
+    else:
+        L.check(lib.fnr_sample_pixels_cams(C.byref(image_set.c), cams.ref(image_set), *rest), "sample_pixels_cams")
     return origins, directions, cam, image, mask
+
+
+def camera_rays(c2w: Tensor, intrinsics_row: Tensor, distortion_row: Optional[Tensor], H: int, W: int, y0: int = 0,
+                y1: Optional[int] = None):
+    """fnr_camera_rays: origins / directions [(y1 - y0) * W, 3] of the pixel rows [y0, y1) of ONE camera (c2w [3,4],
+    its intrinsics row [4] and distortion row [6] or None), row-major."""
+    lib = L.load()
+    L.require_gpu_tensor(c2w, "c2w")
+    dev = c2w.device
+    y1 = int(H) if y1 is None else int(y1)
+    n = max(y1 - int(y0), 0) * int(W)
+    origins = _empty(n, 3, device=dev)
+    directions = _empty(n, 3, device=dev)
+    dist = None if distortion_row is None else _f32c(distortion_row.to(dev))
+    L.check(lib.fnr_camera_rays(L.ptr(_f32c(c2w)), L.ptr(_f32c(intrinsics_row.to(dev))), L.ptr(dist), int(H), int(W),
+                                int(y0), y1, L.ptr(origins), L.ptr(directions), L.stream_ptr(dev)), "camera_rays")
+    return origins, directions

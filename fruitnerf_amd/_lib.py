@@ -104,6 +104,10 @@ class fnr_image_set(C.Structure):
                 ("cx", C.c_float), ("cy", C.c_float)]
 
 
+class fnr_camera_table(C.Structure):
+    _fields_ = [("intrinsics", C.c_void_p), ("distortion", C.c_void_p)]
+
+
 P = C.POINTER
 _vp = C.c_void_p
 _i = C.c_int
@@ -123,6 +127,11 @@ SIGNATURES = {
     "fnr_sample_pixels": (_i, [P(fnr_image_set), _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fnr_train_prologue": (_i, [P(fnr_image_set), _vp, _i, _i64, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _i, _vp, _vp,
                                 _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    "fnr_sample_pixels_cams": (_i, [P(fnr_image_set), P(fnr_camera_table), _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "fnr_train_prologue_cams": (_i, [P(fnr_image_set), P(fnr_camera_table), _vp, _i, _i64, C.c_uint64, C.c_uint64, _vp, _vp,
+                                     _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    "fnr_camera_rays": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "fnr_sample_spaced": (_i, [P(fnr_rays), _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "fnr_weights_pdf": (_i, [P(fnr_rays), _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fnr_prop_density_fwd": (_i, [P(fnr_prop_net), P(fnr_warp), P(fnr_rays), _vp, _i, _vp, _vp, _vp]),
@@ -190,6 +199,10 @@ SIGNATURES = {
     "fnr_camera_pose_grad": (_i, [P(fnr_image_set), _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fnr_camera_pose_grad_adam": (_i, [P(fnr_image_set), _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, P(fnr_table_adam),
                                        _vp]),
+    "fnr_camera_pose_grad_cams": (_i, [P(fnr_image_set), P(fnr_camera_table), _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
+    "fnr_camera_pose_grad_adam_cams": (_i, [P(fnr_image_set), P(fnr_camera_table), _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, P(fnr_table_adam), _vp]),
     "fnr_image_metrics_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fnr_image_metrics": (_i, [_i, _i, _vp, _vp, _vp, _vp, P(C.c_float), _vp, _vp, C.c_size_t, _vp]),
     "fnr_program_create": (_i, [P(_vp)]),

@@ -37,8 +37,10 @@ struct PinholeDev {
 // camera's workgroup then takes the optimiser step of its 6 pose parameters itself (the gradient it has just finished
 // + whatever pose_grad held) and leaves pose_grad zero — fnr_camera_pose_grad + fnr_adam_step / fnr_radam_step with
 // zero_grad, one launch less per step.
-template <bool ADAM>
-__global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, const float* __restrict__ c2w,
+// CAMS: the rays' camera-frame directions are recomputed through the camera table (pixel_direction) instead of the pinhole;
+// they do not depend on the pose, so the gradient formulas are the same.
+template <bool ADAM, bool CAMS>
+__global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, CameraTableDev cams, const float* __restrict__ c2w,
                                                           const long long* __restrict__ train_ids, long long n_rays,
                                                           const float* __restrict__ u, const int* __restrict__ cam_idx,
                                                           const float* __restrict__ pose,
@@ -57,8 +59,16 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, const 
   // what the single-thread tail needs (all workgroup-uniform) is fetched NOW: the kernel is a chain of dependent
   // memory round trips (~1.5 us each), and these were four more of them at its end
   float Mk[12], wk[3], g_old[6], Pk[6], Mm[6], Vk[6];
+  float Kk[4], Dk[6];   // CAMS: the camera's intrinsics and distortion rows
+  const bool distorted = CAMS && cams.distortion != nullptr;
   {
     const float* Msrc = c2w + train_ids[k] * 12;
+    if constexpr (CAMS) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) Kk[i] = cams.intrinsics[train_ids[k] * 4 + i];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) Dk[i] = distorted ? cams.distortion[train_ids[k] * 6 + i] : 0.0f;
+    }
 #pragma unroll
     for (int i = 0; i < 12; ++i) Mk[i] = Msrc[i];
 #pragma unroll
@@ -112,7 +122,12 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, const 
       int x = (int)(u[3 * r + 2] * (float)cam.W);
       y = min(y, cam.H - 1);
       x = min(x, cam.W - 1);
-      const float dc[3] = {((float)x + 0.5f - cam.cx) / cam.fx, -(((float)y + 0.5f - cam.cy) / cam.fy), -1.0f};
+      float dc[3];
+      if constexpr (CAMS) {
+        pixel_direction(Kk, distorted ? Dk : nullptr, x, y, dc);
+      } else {
+        dc[0] = ((float)x + 0.5f - cam.cx) / cam.fx, dc[1] = -(((float)y + 0.5f - cam.cy) / cam.fy), dc[2] = -1.0f;
+      }
       float v[3];
 #pragma unroll
       for (int a = 0; a < 3; ++a) v[a] = Ma[4 * a] * dc[0] + Ma[4 * a + 1] * dc[1] + Ma[4 * a + 2] * dc[2];
@@ -211,19 +226,70 @@ extern "C" int fnr_camera_adjust(const float* c2w, const int64_t* train_ids, int
   return FNR_OK;
 }
 
-extern "C" int fnr_camera_pose_grad(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
-                                    const float* u, const int32_t* camera_indices, const float* pose_adjustment,
-                                    const float* c2w_adjusted, const float* d_origins, const float* d_directions,
-                                    float* pose_grad, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_camera_pose_grad");
+static int camera_pose_grad(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
+                            const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
+                            const int32_t* camera_indices, const float* pose_adjustment, const float* c2w_adjusted,
+                            const float* d_origins, const float* d_directions, float* pose_grad, void* stream) {
+  FNR_SEQ_UNRECORDABLE(name);
+  FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "camera_pose_grad_cams: null camera table");
   FNR_CHECK_ARG(set && set->c2w && train_ids && u && camera_indices && pose_adjustment && c2w_adjusted && d_origins &&
                     d_directions && pose_grad && n_train > 0,
                 "camera_pose_grad: null argument");
   if (n_rays == 0) return FNR_OK;
   PinholeDev cam{set->H, set->W, set->fx, set->fy, set->cx, set->cy};
-  hipLaunchKernelGGL(k_camera_pose_grad<false>, dim3((unsigned)n_train), dim3(256), 0, as_stream(stream), cam, set->c2w,
+  const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
+  const auto kernel = use_cams ? k_camera_pose_grad<false, true> : k_camera_pose_grad<false, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_train), dim3(256), 0, as_stream(stream), cam, t, set->c2w,
                      reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices, pose_adjustment,
                      c2w_adjusted, d_origins, d_directions, pose_grad, TableAdam{});
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+extern "C" int fnr_camera_pose_grad(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
+                                    const float* u, const int32_t* camera_indices, const float* pose_adjustment,
+                                    const float* c2w_adjusted, const float* d_origins, const float* d_directions,
+                                    float* pose_grad, void* stream) {
+  return camera_pose_grad("fnr_camera_pose_grad", set, nullptr, false, train_ids, n_train, n_rays, u, camera_indices,
+                          pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
+}
+
+extern "C" int fnr_camera_pose_grad_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
+                                         int n_train, int64_t n_rays, const float* u, const int32_t* camera_indices,
+                                         const float* pose_adjustment, const float* c2w_adjusted, const float* d_origins,
+                                         const float* d_directions, float* pose_grad, void* stream) {
+  return camera_pose_grad("fnr_camera_pose_grad_cams", set, cams, true, train_ids, n_train, n_rays, u, camera_indices,
+                          pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
+}
+
+static int camera_pose_grad_adam(const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
+                                 const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
+                                 const int32_t* camera_indices, const float* c2w_adjusted, const float* d_origins,
+                                 const float* d_directions, float* pose_grad, const fnr_table_adam* adam, void* stream) {
+  if (seq::recording() && set && adam && (!use_cams || cams)) {
+    const fnr_image_set set_ = *set;
+    const fnr_camera_table cams_ = use_cams ? *cams : fnr_camera_table{nullptr, nullptr};
+    const fnr_table_adam adam_ = *adam;
+    seq::push(use_cams ? "fnr_camera_pose_grad_adam_cams" : "fnr_camera_pose_grad_adam", [=](const fnr_step_scalars* sc) {
+      const fnr_table_adam a = seq::patched(adam_, sc);
+      return camera_pose_grad_adam(&set_, &cams_, use_cams, train_ids, n_train, n_rays, u, camera_indices, c2w_adjusted,
+                                   d_origins, d_directions, pose_grad, &a, stream);
+    });
+  }
+  FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "camera_pose_grad_adam_cams: null camera table");
+  FNR_CHECK_ARG(set && set->c2w && train_ids && u && camera_indices && c2w_adjusted && d_origins && d_directions &&
+                    pose_grad && adam && n_train > 0,
+                "camera_pose_grad_adam: null argument");
+  TableAdam t;
+  const int rc = make_table_adam(adam, t);
+  if (rc) return rc;
+  PinholeDev cam{set->H, set->W, set->fx, set->fy, set->cx, set->cy};
+  const CameraTableDev ct = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
+  const auto kernel = use_cams ? k_camera_pose_grad<true, true> : k_camera_pose_grad<true, false>;
+  // n_rays == 0 still takes the step (every pose parameter decays its moments)
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_train), dim3(256), 0, as_stream(stream), cam, ct, set->c2w,
+                     reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices, adam->params,
+                     c2w_adjusted, d_origins, d_directions, pose_grad, t);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -232,26 +298,15 @@ extern "C" int fnr_camera_pose_grad_adam(const fnr_image_set* set, const int64_t
                                          const float* u, const int32_t* camera_indices, const float* c2w_adjusted,
                                          const float* d_origins, const float* d_directions, float* pose_grad,
                                          const fnr_table_adam* adam, void* stream) {
-  if (seq::recording() && set && adam) {
-    const fnr_image_set set_ = *set;
-    const fnr_table_adam adam_ = *adam;
-    seq::push("fnr_camera_pose_grad_adam", [=](const fnr_step_scalars* sc) {
-      const fnr_table_adam a = seq::patched(adam_, sc);
-      return fnr_camera_pose_grad_adam(&set_, train_ids, n_train, n_rays, u, camera_indices, c2w_adjusted, d_origins,
-                                       d_directions, pose_grad, &a, stream);
-    });
-  }
-  FNR_CHECK_ARG(set && set->c2w && train_ids && u && camera_indices && c2w_adjusted && d_origins && d_directions &&
-                    pose_grad && adam && n_train > 0,
-                "camera_pose_grad_adam: null argument");
-  TableAdam t;
-  const int rc = make_table_adam(adam, t);
-  if (rc) return rc;
-  PinholeDev cam{set->H, set->W, set->fx, set->fy, set->cx, set->cy};
-  // n_rays == 0 still takes the step (every pose parameter decays its moments)
-  hipLaunchKernelGGL(k_camera_pose_grad<true>, dim3((unsigned)n_train), dim3(256), 0, as_stream(stream), cam, set->c2w,
-                     reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices, adam->params,
-                     c2w_adjusted, d_origins, d_directions, pose_grad, t);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
+  return camera_pose_grad_adam(set, nullptr, false, train_ids, n_train, n_rays, u, camera_indices, c2w_adjusted, d_origins,
+                               d_directions, pose_grad, adam, stream);
+}
+
+extern "C" int fnr_camera_pose_grad_adam_cams(const fnr_image_set* set, const fnr_camera_table* cams,
+                                              const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
+                                              const int32_t* camera_indices, const float* c2w_adjusted,
+                                              const float* d_origins, const float* d_directions, float* pose_grad,
+                                              const fnr_table_adam* adam, void* stream) {
+  return camera_pose_grad_adam(set, cams, true, train_ids, n_train, n_rays, u, camera_indices, c2w_adjusted, d_origins,
+                               d_directions, pose_grad, adam, stream);
 }

@@ -17,7 +17,11 @@ struct ImageSetDev {
   float fx, fy, cx, cy;
 };
 
-__global__ __launch_bounds__(256) void k_sample_pixels(ImageSetDev s, const long long* __restrict__ train_ids,
+// CAMS: the camera-frame direction comes from the per-image camera table (camera_math.hpp::pixel_direction) instead of
+// the set-wide pinhole; everything after it is the same code.
+template <bool CAMS>
+__global__ __launch_bounds__(256) void k_sample_pixels(ImageSetDev s, CameraTableDev cams,
+                                                       const long long* __restrict__ train_ids,
                                                        int n_train, long long n_rays, const float* __restrict__ u,
                                                        const float* __restrict__ c2w_adjusted,
                                                        float* __restrict__ origins, float* __restrict__ directions,
@@ -33,9 +37,16 @@ __global__ __launch_bounds__(256) void k_sample_pixels(ImageSetDev s, const long
   y = min(y, s.H - 1);
   x = min(x, s.W - 1);
   const long long img = train_ids[k];
-  const float dx = fdiv(fsub(fadd((float)x, 0.5f), s.cx), s.fx);
-  const float dy = -fdiv(fsub(fadd((float)y, 0.5f), s.cy), s.fy);
-  const float dz = -1.0f;
+  float dx, dy, dz;
+  if constexpr (CAMS) {
+    float dc[3];
+    pixel_direction(cams.intrinsics + 4 * img, cams.distortion ? cams.distortion + 6 * img : nullptr, x, y, dc);
+    dx = dc[0], dy = dc[1], dz = dc[2];
+  } else {
+    dx = fdiv(fsub(fadd((float)x, 0.5f), s.cx), s.fx);
+    dy = -fdiv(fsub(fadd((float)y, 0.5f), s.cy), s.fy);
+    dz = -1.0f;
+  }
   // camera-pose optimisation: the slot's corrected camera (fnr_camera_adjust) replaces the dataset's
   const float* M = c2w_adjusted ? c2w_adjusted + (size_t)k * 12 : s.c2w + img * 12;
   float d[3];
@@ -100,7 +111,8 @@ struct PrologueArgs {
   int nb_rays;              // workgroups of the per-ray role
 };
 
-__global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a) {
+template <bool CAMS>
+__global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a, CameraTableDev cams) {
   if ((int)blockIdx.x < a.nb_rays) {
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
     // corrected cameras for the pose-gradient kernel: camera k by thread k of the launch (same arithmetic as per ray)
@@ -126,9 +138,16 @@ __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a) {
     y = min(y, a.set.H - 1);
     x = min(x, a.set.W - 1);
     const long long img = a.train_ids[k];
-    const float dx = fdiv(fsub(fadd((float)x, 0.5f), a.set.cx), a.set.fx);
-    const float dy = -fdiv(fsub(fadd((float)y, 0.5f), a.set.cy), a.set.fy);
-    const float dz = -1.0f;
+    float dx, dy, dz;
+    if constexpr (CAMS) {
+      float dc[3];
+      pixel_direction(cams.intrinsics + 4 * img, cams.distortion ? cams.distortion + 6 * img : nullptr, x, y, dc);
+      dx = dc[0], dy = dc[1], dz = dc[2];
+    } else {
+      dx = fdiv(fsub(fadd((float)x, 0.5f), a.set.cx), a.set.fx);
+      dy = -fdiv(fsub(fadd((float)y, 0.5f), a.set.cy), a.set.fy);
+      dz = -1.0f;
+    }
     float M[12];
     if (a.pose) {
       adjusted_camera(a.set.c2w + img * 12, a.pose + 6 * k, M);
@@ -166,41 +185,101 @@ __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a) {
   a.euclid0[idx] = spacing_to_euclid(a.kind, b, s_near, s_far);
 }
 
+// ---- full-image rays of ONE camera (fnr_camera_rays): rows [y0, y1) of its H x W pixels, one thread per pixel ----------
+// Same arithmetic as k_sample_pixels<true> on the `u` that selects the pixel (tests/test_gpu_camera_models.py).
+__global__ __launch_bounds__(256) void k_camera_rays(const float* __restrict__ c2w, const float* __restrict__ K,
+                                                     const float* __restrict__ D, int W, int y0, long long n_pix,
+                                                     float* __restrict__ origins, float* __restrict__ directions) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_pix) return;
+  const int row = (int)(r / W);
+  const int x = (int)(r - (long long)row * W), y = y0 + row;
+  float dc[3];
+  pixel_direction(K, D, x, y, dc);
+  const float* M = c2w;
+  float d[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    d[a] = fadd(fadd(fmul(M[4 * a], dc[0]), fmul(M[4 * a + 1], dc[1])), fmul(M[4 * a + 2], dc[2]));
+  const float nrm = fmaxf(sqrtf(fadd(fadd(fmul(d[0], d[0]), fmul(d[1], d[1])), fmul(d[2], d[2]))), 1e-12f);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    directions[3 * r + a] = fdiv(d[a], nrm);
+    origins[3 * r + a] = M[4 * a + 3];
+  }
+}
+
 }  // namespace fnr
 
 using namespace fnr;
 
-extern "C" int fnr_sample_pixels(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
-                                 const float* u, const float* c2w_adjusted, float* origins, float* directions,
-                                 int32_t* camera_indices, float* image, float* fruit_mask, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_sample_pixels");
+// cams: NULL for the set-wide pinhole (fnr_sample_pixels), the camera table of the _cams variant otherwise
+static int sample_pixels(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
+                         const int64_t* train_ids, int n_train, int64_t n_rays, const float* u, const float* c2w_adjusted,
+                         float* origins, float* directions, int32_t* camera_indices, float* image, float* fruit_mask,
+                         void* stream) {
+  FNR_SEQ_UNRECORDABLE(name);
+  FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "sample_pixels_cams: null camera table");
   FNR_CHECK_ARG(set && train_ids && u && origins && directions && camera_indices && image && fruit_mask,
                 "sample_pixels: null argument");
   FNR_CHECK_ARG(set->images && set->masks && set->c2w && set->n_images > 0 && set->H > 0 && set->W > 0 && n_train > 0,
                 "sample_pixels: bad image set");
   if (n_rays == 0) return FNR_OK;
   ImageSetDev s{set->n_images, set->H, set->W, set->images, set->masks, set->c2w, set->fx, set->fy, set->cx, set->cy};
-  hipLaunchKernelGGL(k_sample_pixels, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream), s,
-                     reinterpret_cast<const long long*>(train_ids), n_train, (long long)n_rays, u, c2w_adjusted, origins, directions,
-                     camera_indices, image, fruit_mask);
+  const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
+  const auto kernel = use_cams ? k_sample_pixels<true> : k_sample_pixels<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream), s, t,
+                     reinterpret_cast<const long long*>(train_ids), n_train, (long long)n_rays, u, c2w_adjusted, origins,
+                     directions, camera_indices, image, fruit_mask);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
 
-extern "C" int fnr_train_prologue(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
-                                  uint64_t seed, uint64_t offset, const float* pose_adjustment, float* c2w_adjusted,
-                                  float* u, float* jitter, int n_jitter, float* origins, float* directions,
-                                  int32_t* camera_indices, float* image, float* fruit_mask, float near_plane,
-                                  float far_plane, int spacing_kind, int S0, const float* base_bins, float* spacing0,
-                                  float* euclid0, void* stream) {
-  if (seq::recording() && set) {
+extern "C" int fnr_sample_pixels(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
+                                 const float* u, const float* c2w_adjusted, float* origins, float* directions,
+                                 int32_t* camera_indices, float* image, float* fruit_mask, void* stream) {
+  return sample_pixels("fnr_sample_pixels", set, nullptr, false, train_ids, n_train, n_rays, u, c2w_adjusted, origins,
+                       directions, camera_indices, image, fruit_mask, stream);
+}
+
+extern "C" int fnr_sample_pixels_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
+                                      int n_train, int64_t n_rays, const float* u, const float* c2w_adjusted,
+                                      float* origins, float* directions, int32_t* camera_indices, float* image,
+                                      float* fruit_mask, void* stream) {
+  return sample_pixels("fnr_sample_pixels_cams", set, cams, true, train_ids, n_train, n_rays, u, c2w_adjusted, origins,
+                       directions, camera_indices, image, fruit_mask, stream);
+}
+
+extern "C" int fnr_camera_rays(const float* c2w, const float* intrinsics, const float* distortion, int H, int W, int y0,
+                               int y1, float* origins, float* directions, void* stream) {
+  FNR_SEQ_UNRECORDABLE("fnr_camera_rays");
+  FNR_CHECK_ARG(c2w && intrinsics && origins && directions, "camera_rays: null argument");
+  FNR_CHECK_ARG(H > 0 && W > 0 && y0 >= 0 && y0 <= y1 && y1 <= H, "camera_rays: rows [%d, %d) of a %d x %d image", y0, y1,
+                H, W);
+  const long long n_pix = (long long)(y1 - y0) * W;
+  if (n_pix == 0) return FNR_OK;
+  hipLaunchKernelGGL(k_camera_rays, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, as_stream(stream), c2w, intrinsics,
+                     distortion, W, y0, n_pix, origins, directions);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+static int train_prologue(const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams, const int64_t* train_ids,
+                          int n_train, int64_t n_rays, uint64_t seed, uint64_t offset, const float* pose_adjustment,
+                          float* c2w_adjusted, float* u, float* jitter, int n_jitter, float* origins, float* directions,
+                          int32_t* camera_indices, float* image, float* fruit_mask, float near_plane, float far_plane,
+                          int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
+                          void* stream) {
+  if (seq::recording() && set && (!use_cams || cams)) {
     const fnr_image_set set_ = *set;
-    seq::push("fnr_train_prologue", [=](const fnr_step_scalars* sc) {
-      return fnr_train_prologue(&set_, train_ids, n_train, n_rays, seed, sc ? sc->prologue_offset : offset, pose_adjustment,
-                                c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image, fruit_mask,
-                                near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+    const fnr_camera_table cams_ = use_cams ? *cams : fnr_camera_table{nullptr, nullptr};
+    seq::push(use_cams ? "fnr_train_prologue_cams" : "fnr_train_prologue", [=](const fnr_step_scalars* sc) {
+      return train_prologue(&set_, &cams_, use_cams, train_ids, n_train, n_rays, seed, sc ? sc->prologue_offset : offset,
+                            pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
+                            fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
     });
   }
+  FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "train_prologue_cams: null camera table");
   FNR_CHECK_ARG(set && train_ids && u && jitter && origins && directions && camera_indices && image && fruit_mask &&
                     base_bins && spacing0 && euclid0,
                 "train_prologue: null argument");
@@ -222,7 +301,32 @@ extern "C" int fnr_train_prologue(const fnr_image_set* set, const int64_t* train
   a.nb_rays = (int)((n_rays + 255) / 256);
   const long long nb_bins = (n_rays * (long long)(S0 + 1) + 255) / 256;
   FNR_PROF(OP_SAMPLE_SPACED, n_rays * (long long)(S0 + 1));
-  hipLaunchKernelGGL(k_train_prologue, dim3((unsigned)(a.nb_rays + nb_bins)), dim3(256), 0, as_stream(stream), a);
+  const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
+  const auto kernel = use_cams ? k_train_prologue<true> : k_train_prologue<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(a.nb_rays + nb_bins)), dim3(256), 0, as_stream(stream), a, t);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
+}
+
+extern "C" int fnr_train_prologue(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
+                                  uint64_t seed, uint64_t offset, const float* pose_adjustment, float* c2w_adjusted,
+                                  float* u, float* jitter, int n_jitter, float* origins, float* directions,
+                                  int32_t* camera_indices, float* image, float* fruit_mask, float near_plane,
+                                  float far_plane, int spacing_kind, int S0, const float* base_bins, float* spacing0,
+                                  float* euclid0, void* stream) {
+  return train_prologue(set, nullptr, false, train_ids, n_train, n_rays, seed, offset, pose_adjustment, c2w_adjusted, u,
+                        jitter, n_jitter, origins, directions, camera_indices, image, fruit_mask, near_plane, far_plane,
+                        spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+}
+
+extern "C" int fnr_train_prologue_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
+                                       int n_train, int64_t n_rays, uint64_t seed, uint64_t offset,
+                                       const float* pose_adjustment, float* c2w_adjusted, float* u, float* jitter,
+                                       int n_jitter, float* origins, float* directions, int32_t* camera_indices,
+                                       float* image, float* fruit_mask, float near_plane, float far_plane,
+                                       int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
+                                       void* stream) {
+  return train_prologue(set, cams, true, train_ids, n_train, n_rays, seed, offset, pose_adjustment, c2w_adjusted, u, jitter,
+                        n_jitter, origins, directions, camera_indices, image, fruit_mask, near_plane, far_plane,
+                        spacing_kind, S0, base_bins, spacing0, euclid0, stream);
 }

@@ -85,6 +85,44 @@ def pixel_rays(c2w: Tensor, cam_idx: Tensor, y: Tensor, x: Tensor, fx: float, fy
     return o, d
 
 
+def undistort_opencv(xd: Tensor, yd: Tensor, dist: Tensor) -> Tuple[Tensor, Tensor]:
+    """Inverse of the OpenCV radial / tangential model (dist [..., 6] = k1, k2, k3, k4, p1, p2, broadcast against xd, yd):
+    10 Newton steps from (xd, yd), a step zero where |det| <= 1e-9 — the contract of include/fruitnerf_hip.h
+    (fnr_camera_table) restated in torch for data generation; not in the product path."""
+    k1, k2, k3, k4, p1, p2 = dist.unbind(-1)
+    x, y = xd.clone(), yd.clone()
+    for _ in range(10):
+        r = x * x + y * y
+        d = 1.0 + r * (k1 + r * (k2 + r * (k3 + r * k4)))
+        fx = d * x + 2.0 * p1 * x * y + p2 * (r + 2.0 * x * x) - xd
+        fy = d * y + 2.0 * p2 * x * y + p1 * (r + 2.0 * y * y) - yd
+        d_r = k1 + r * (2.0 * k2 + r * (3.0 * k3 + r * 4.0 * k4))
+        d_x, d_y = 2.0 * x * d_r, 2.0 * y * d_r
+        fx_x = d + d_x * x + 2.0 * p1 * y + 6.0 * p2 * x
+        fx_y = d_y * x + 2.0 * p1 * x + 2.0 * p2 * y
+        fy_x = d_x * y + 2.0 * p2 * y + 2.0 * p1 * x
+        fy_y = d + d_y * y + 2.0 * p2 * x + 6.0 * p1 * y
+        det = fx_x * fy_y - fx_y * fy_x
+        ok = det.abs() > 1e-9
+        inv = 1.0 / torch.where(ok, det, torch.ones_like(det))
+        x = x - torch.where(ok, (fx * fy_y - fy * fx_y) * inv, torch.zeros_like(det))
+        y = y - torch.where(ok, (fy * fx_x - fx * fy_x) * inv, torch.zeros_like(det))
+    return x, y
+
+
+def camera_rays(c2w_i: Tensor, y: Tensor, x: Tensor, intrinsics_i: Tensor, distortion_i: Optional[Tensor]
+                ) -> Tuple[Tensor, Tensor]:
+    """pixel_rays for ONE camera with its own intrinsics row (fx, fy, cx, cy) and optional OpenCV distortion row."""
+    fx, fy, cx, cy = intrinsics_i.unbind(-1)
+    xd, yd = (x.float() + 0.5 - cx) / fx, (y.float() + 0.5 - cy) / fy
+    if distortion_i is not None:
+        xd, yd = undistort_opencv(xd, yd, distortion_i)
+    R = c2w_i[:, :3]
+    d = R[None, :, 0] * xd[:, None] + R[None, :, 1] * (-yd)[:, None] + R[None, :, 2] * (-torch.ones_like(xd))[:, None]
+    d = torch.nn.functional.normalize(d, dim=-1)
+    return c2w_i[None, :, 3].expand_as(d), d
+
+
 def shade_rays(scene: SyntheticScene, o: Tensor, d: Tensor, chunk: int = 1 << 18) -> Tuple[Tensor, Tensor]:
     """Analytic render: rgb [N,3] in [0,1] and fruit mask [N] (float 0/1)."""
     light = torch.nn.functional.normalize(torch.tensor([0.4, 0.3, 0.85], device=o.device), dim=0)
@@ -111,33 +149,60 @@ def shade_rays(scene: SyntheticScene, o: Tensor, d: Tensor, chunk: int = 1 << 18
 
 
 def render_dataset(scene: SyntheticScene, c2w: Tensor, H: int = 800, W: int = 800, fx: float = 1111.0,
-                   fy: float = 1111.0) -> Dict[str, Tensor]:
-    """uint8 images [M,H,W,3] and masks [M,H,W] (the on-device 'image batch' a datamanager would hold)."""
+                   fy: float = 1111.0, intrinsics: Optional[Tensor] = None, distortion: Optional[Tensor] = None
+                   ) -> Dict[str, Tensor]:
+    """uint8 images [M,H,W,3] and masks [M,H,W] (the on-device 'image batch' a datamanager would hold).
+    intrinsics [M,4] (fx, fy, cx, cy per image) / distortion [M,6] (k1, k2, k3, k4, p1, p2): render through per-image,
+    distorted cameras (what a real capture looks like); both then come back in the dictionary."""
     dev = c2w.device
     cx, cy = W / 2.0, H / 2.0
     ys, xs = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
     ys, xs = ys.reshape(-1), xs.reshape(-1)
     imgs = torch.empty(c2w.shape[0], H, W, 3, dtype=torch.uint8, device=dev)
     msks = torch.empty(c2w.shape[0], H, W, dtype=torch.uint8, device=dev)
+    per_image = intrinsics is not None or distortion is not None
+    if per_image:
+        if intrinsics is None:
+            intrinsics = torch.tensor([fx, fy, cx, cy], dtype=torch.float32, device=dev).expand(c2w.shape[0], 4)
+        intrinsics = intrinsics.to(dev, torch.float32)
+        distortion = None if distortion is None else distortion.to(dev, torch.float32)
     for i in range(c2w.shape[0]):
         ci = torch.full_like(ys, i)
-        o, d = pixel_rays(c2w, ci, ys, xs, fx, fy, cx, cy)
+        if per_image:
+            o, d = camera_rays(c2w[i], ys, xs, intrinsics[i], None if distortion is None else distortion[i])
+        else:
+            o, d = pixel_rays(c2w, ci, ys, xs, fx, fy, cx, cy)
         rgb, m = shade_rays(scene, o, d)
         imgs[i] = (rgb.view(H, W, 3) * 255.0 + 0.5).clamp(0, 255).to(torch.uint8)
         msks[i] = m.view(H, W).to(torch.uint8)
-    return {"images": imgs, "masks": msks, "H": H, "W": W, "fx": fx, "fy": fy, "cx": cx, "cy": cy, "c2w": c2w}
+    out = {"images": imgs, "masks": msks, "H": H, "W": W, "fx": fx, "fy": fy, "cx": cx, "cy": cy, "c2w": c2w}
+    if per_image:
+        out["intrinsics"], out["distortion"] = intrinsics, distortion
+    return out
 
 
 class PixelBatcher:
     """PixelSampler + RayGenerator of the train datamanager (data/fruit_datamanager.py:188-197) on the device:
     uniform random (image, y, x) triples -> RayBundle tensors + {"image", "fruit_mask"} batch."""
 
-    def __init__(self, data: Dict[str, Tensor], image_ids: Tensor, seed: int):
+    def __init__(self, data: Dict[str, Tensor], image_ids: Tensor, seed: int, cameras=None):
+        """cameras (cameras.cameras.Cameras or a nerfstudio Cameras, rows indexed like data["c2w"]): rays go through its
+        per-image intrinsics and distortion (the _cams entry points) instead of the set-wide pinhole of `data`."""
         self.data = data
+        self.cameras = cameras
+        self._cams = None
         self.image_ids = image_ids          # dataset indices used for training (camera_indices = position here)
         self.gen = torch.Generator(device=data["images"].device)
         self.gen.manual_seed(seed)
         self._set = None
+
+    def camera_table(self):
+        """K.CameraTableArg of `cameras` on the image batch's device (None without cameras): what every launch that takes
+        the image set gets next to it."""
+        if self.cameras is not None and self._cams is None:
+            from ..cameras.cameras import camera_table_of
+            self._cams = camera_table_of(self.cameras, self.data["images"].device)
+        return self._cams
 
     def sample(self, n_rays: int, camera_optimizer=None, level0: Optional[dict] = None):
         """One fused kernel on the HIP device (fnr_sample_pixels / fnr_train_prologue); a batch on the CPU raises.
@@ -155,7 +220,8 @@ class PixelBatcher:
             pose = camera_optimizer.pose_adjustment.data if (camera_optimizer is not None and camera_optimizer.enabled) else None
             self._offset = getattr(self, "_offset", 0) + 1
             out = K.train_prologue(self._set, self.image_ids, n_rays, self.gen.initial_seed(), self._offset, pose,
-                                   level0["near"], level0["far"], level0["S"], n_jitter=level0.get("n_jitter", 3))
+                                   level0["near"], level0["far"], level0["S"], n_jitter=level0.get("n_jitter", 3),
+                                   cams=self.camera_table())
             self.last_draw = {"u": out["u"], "cam": out["cam"], "c2w_adjusted": out["c2w_adjusted"]}
             self.last_presample = {"S0": out["S0"], "near": out["near"], "far": out["far"], "spacing": out["spacing"],
                                    "euclid": out["euclid"], "jitter": [out["jitter"][i] for i in range(out["jitter"].shape[0])]}
@@ -167,7 +233,7 @@ class PixelBatcher:
             if self._set is None:
                 self._set = K.ImageSetArg(d["images"], d["masks"], d["c2w"], d["fx"], d["fy"], d["cx"], d["cy"])
             c2w_adj = camera_optimizer.adjusted_cameras(self._set, self.image_ids) if camera_optimizer is not None else None
-            o, dirs, cam, image, mask = K.sample_pixels(self._set, self.image_ids, u, c2w_adj)
+            o, dirs, cam, image, mask = K.sample_pixels(self._set, self.image_ids, u, c2w_adj, cams=self.camera_table())
             self.last_draw = {"u": u, "cam": cam, "c2w_adjusted": c2w_adj}
             self.last_presample = None
             return o, dirs, cam[:, None], {"image": image, "fruit_mask": mask[:, None]}

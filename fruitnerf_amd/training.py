@@ -1113,6 +1113,12 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
     return loss_dict, metrics_dict
 
 
+def _camera_table(batcher):
+    """The batcher's per-image camera table (K.CameraTableArg) or None: the rays were drawn through it, so is the backward."""
+    table = getattr(batcher, "camera_table", None)
+    return table() if table is not None else None
+
+
 def camera_backward(camera_optimizer, batcher, ray_grads: dict, world_size: int = 1):
     """The datamanager side of loss.backward() for the camera-pose optimiser (fruit_nerf_config.py:39-43): ray
     gradients -> pose_adjustment.grad (camera_opt.hip).  With several ranks the 6 x num_cameras gradient is averaged
@@ -1121,7 +1127,7 @@ def camera_backward(camera_optimizer, batcher, ray_grads: dict, world_size: int 
     d = batcher.last_draw
     pose = camera_optimizer.pose_adjustment
     K.camera_pose_grad(batcher._set, batcher.image_ids, d["u"], d["cam"], pose.data, d["c2w_adjusted"],
-                       ray_grads["origins"], ray_grads["directions"], pose.grad)
+                       ray_grads["origins"], ray_grads["directions"], pose.grad, cams=_camera_table(batcher))
     if world_size >= EXCHANGE_MIN_WORLD:
         import torch.distributed as dist
         return _issued(dist.all_reduce(pose.grad, op=dist.ReduceOp.SUM, async_op=True), "all_reduce(poses)",
@@ -1137,7 +1143,8 @@ def camera_backward_and_step(camera_optimizer, camera_adam, batcher, ray_grads: 
         d = batcher.last_draw
         pose = camera_optimizer.pose_adjustment
         K.camera_pose_grad_adam(batcher._set, batcher.image_ids, d["u"], d["cam"], d["c2w_adjusted"],
-                                ray_grads["origins"], ray_grads["directions"], pose.grad, camera_adam.fused_step_args())
+                                ray_grads["origins"], ray_grads["directions"], pose.grad, camera_adam.fused_step_args(),
+                                cams=_camera_table(batcher))
         return
     work, scale = camera_backward(camera_optimizer, batcher, ray_grads, world_size)
     if work is not None:
@@ -1430,7 +1437,8 @@ class TrainingSteps:
         cfg = model.config
         dev = model.device
         side = model.__dict__.get("_side_stream")
-        return (self._arena_version, parity, start_offset, updated, updated_next, bool(want_metrics), self.camera is not None,
+        cams = _camera_table(self.batcher)      # recorded by value: another table is another program
+        return (None if cams is None else cams.pointers(), self._arena_version, parity, start_offset, updated, updated_next, bool(want_metrics), self.camera is not None,
                 getattr(fld, "mlp_precision", None), model.arena().params.data_ptr(), id(self.optimizer),
                 L.stream_ptr(dev), None if side is None else side.cuda_stream,
                 OVERLAP_PROPOSAL_BACKWARD, SERIALIZE_STREAMS, LOSSES_ON_SIDE, PAIR_PROPOSAL_LEVELS, FUSE_CAMERA_OPTIMIZER,

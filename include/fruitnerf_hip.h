@@ -27,6 +27,8 @@
 extern "C" {
 #endif
 
+/* 13 also covers the per-image camera table (fnr_camera_table, the fnr_*_cams entry points and fnr_camera_rays): pure
+ * additions — no existing symbol or struct changed, so a caller built against the earlier 13 runs unchanged. */
 #define FNR_ABI_VERSION 13
 #define FNR_MAX_LEVELS 16
 #define FNR_MAX_SEM_LAYERS 4
@@ -187,6 +189,41 @@ int fnr_train_prologue(const fnr_image_set* set, const int64_t* train_ids, int n
                        float* fruit_mask, float near_plane, float far_plane, int spacing_kind, int S0,
                        const float* base_bins, float* spacing0, float* euclid0, void* stream);
 
+/* Per-image cameras of a real dataset: what the dataparser reads per dataset or per frame (fl_x, fl_y, cx, cy and the
+ * OPENCV coefficients k1..k4, p1, p2; data/fruitnerf_dataparser.py:86-131, 226-273) and hands to
+ * Cameras(..., distortion_params=...).  Rows are indexed by DATASET image, like c2w.  The camera-frame direction of pixel
+ * (x, y) of image i:  xd = (x + 0.5 - cx_i) / fx_i,  yd = (y + 0.5 - cy_i) / fy_i (OpenCV image coordinates, y down);
+ * (xu, yu) = the solution of the OpenCV forward model
+ *   r = xu^2 + yu^2,  d = 1 + r (k1 + r (k2 + r (k3 + r k4))),
+ *   xd = d xu + 2 p1 xu yu + p2 (r + 2 xu^2),  yd = d yu + 2 p2 xu yu + p1 (r + 2 yu^2)
+ * by exactly 10 Newton steps from (xd, yd) (analytic Jacobian, a step is zero where |det| <= 1e-9, no early exit);
+ * direction = (xu, -yu, -1).  distortion == NULL or an all-zero row gives the pinhole direction bit for bit. */
+typedef struct fnr_camera_table {
+  const float* intrinsics;   /* [M,4] fx, fy, cx, cy per DATASET image (indexed like c2w), never NULL */
+  const float* distortion;   /* [M,6] k1, k2, k3, k4, p1, p2 (nerfstudio's distortion_params order), or NULL = none */
+} fnr_camera_table;
+
+/* fnr_sample_pixels through per-image cameras (the RayGenerator over Cameras with distortion_params that
+ * data/fruitnerf_dataparser.py:226-273 builds): set->fx..cy are ignored, H and W stay set-wide. */
+int fnr_sample_pixels_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids, int n_train,
+                           int64_t n_rays, const float* u, const float* c2w_adjusted, float* origins, float* directions,
+                           int32_t* camera_indices, float* image, float* fruit_mask, void* stream);
+/* fnr_train_prologue through per-image cameras (data/fruit_datamanager.py:188-197 on a real dataset's Cameras): given u
+ * and jitter, every output is bit-identical to fnr_camera_adjust + fnr_sample_pixels_cams + fnr_sample_spaced
+ * (tests/test_gpu_camera_models.py).  Recorded into step programs like fnr_train_prologue (the table by value). */
+int fnr_train_prologue_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids, int n_train,
+                            int64_t n_rays, uint64_t seed, uint64_t offset, const float* pose_adjustment,
+                            float* c2w_adjusted, float* u, float* jitter, int n_jitter, float* origins, float* directions,
+                            int32_t* camera_indices, float* image, float* fruit_mask, float near_plane, float far_plane,
+                            int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
+                            void* stream);
+/* Full-image rays of ONE camera (Cameras.generate_rays(camera_indices=i), what FruitModel.get_outputs_for_camera_ray_bundle
+ * is fed, fruit_nerf.py:382-383): c2w [3,4], intrinsics [4] and distortion [6] (or NULL) are that camera's rows; writes
+ * origins / directions [(y1 - y0) W, 3] of the pixel rows [y0, y1), row-major — the same bits fnr_sample_pixels_cams gives
+ * for those pixels.  0 <= y0 <= y1 <= H. */
+int fnr_camera_rays(const float* c2w, const float* intrinsics, const float* distortion, int H, int W, int y0, int y1,
+                    float* origins, float* directions, void* stream);
+
 /* nerfstudio CameraOptimizer(mode="SO3xR3") (fruit_nerf_config.py:39-43): c2w_adjusted[k] =
  * pose_utils.multiply(c2w[train_ids[k]], exp_map_SO3xR3(pose_adjustment[k])), pose_adjustment [n_train,6] =
  * (translation, so3 log-rotation) per training camera. */
@@ -198,6 +235,12 @@ int fnr_camera_pose_grad(const fnr_image_set* set, const int64_t* train_ids, int
                          const float* u, const int32_t* camera_indices, const float* pose_adjustment,
                          const float* c2w_adjusted, const float* d_origins, const float* d_directions,
                          float* pose_grad, void* stream);
+/* fnr_camera_pose_grad for rays drawn through per-image cameras (fnr_sample_pixels_cams / fnr_train_prologue_cams): the
+ * undistorted camera-frame direction is recomputed from u; it does not depend on the pose, nothing more is read. */
+int fnr_camera_pose_grad_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
+                              int n_train, int64_t n_rays, const float* u, const int32_t* camera_indices,
+                              const float* pose_adjustment, const float* c2w_adjusted, const float* d_origins,
+                              const float* d_directions, float* pose_grad, void* stream);
 
 /* ---- samplers ------------------------------------------------------------------------------- */
 /* SpacedSampler.generate_ray_samples (components/ray_samplers.py:54-104; nerfstudio
@@ -427,6 +470,13 @@ int fnr_camera_pose_grad_adam(const fnr_image_set* set, const int64_t* train_ids
                               const float* u, const int32_t* camera_indices, const float* c2w_adjusted,
                               const float* d_origins, const float* d_directions, float* pose_grad,
                               const fnr_table_adam* adam, void* stream);
+/* fnr_camera_pose_grad_adam for rays drawn through per-image cameras (camera_optimizer group, fruit_nerf_config.py:39-43,
+ * on a dataset with per-frame intrinsics / distortion): bit-identical to fnr_camera_pose_grad_cams followed by the
+ * optimiser step; recorded into step programs like fnr_camera_pose_grad_adam (the table by value, the Adam slot patched). */
+int fnr_camera_pose_grad_adam_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
+                                   int n_train, int64_t n_rays, const float* u, const int32_t* camera_indices,
+                                   const float* c2w_adjusted, const float* d_origins, const float* d_directions,
+                                   float* pose_grad, const fnr_table_adam* adam, void* stream);
 
 /* Backward of fnr_prop_density_fwd: d_density [R,S] -> += into grads (table, w0, b0, w1, b1).
  * d_position (optional) [N,4]: gradient w.r.t. each sample's unit-cube position (xyz, w = 0) for
