@@ -975,26 +975,41 @@ class CameraTableArg:
         return C.byref(self.c)
 
 
-def camera_adjust(image_set: ImageSetArg, train_ids: Tensor, pose_adjustment: Tensor) -> Tensor:
-    """c2w' [n_train,3,4] = multiply(c2w[train_ids], exp_map_SO3xR3(pose_adjustment))."""
+def _table_ref(cams: Optional["CameraTableArg"], image_set: "ImageSetArg"):
+    """The nullable camera-table argument of the fnr_*_mode entry points."""
+    return None if cams is None else cams.ref(image_set)
+
+
+def camera_adjust(image_set: ImageSetArg, train_ids: Tensor, pose_adjustment: Tensor,
+                  pose_mode: int = L.FNR_POSE_SO3XR3) -> Tensor:
+    """c2w' [n_train,3,4] = multiply(c2w[train_ids], exp_map(pose_adjustment)), the exponential map of pose_mode
+    (L.FNR_POSE_SO3XR3 | L.FNR_POSE_SE3; anything but SO3xR3 goes through the fnr_*_mode entry points)."""
     lib = L.load()
     ids = train_ids.to(torch.int64).contiguous()
     out = torch.empty(ids.numel(), 3, 4, device=pose_adjustment.device)
-    L.check(lib.fnr_camera_adjust(L.ptr(image_set.c2w), L.ptr(ids), ids.numel(), L.ptr(_f32c(pose_adjustment)), L.ptr(out),
-                                  L.stream_ptr(out.device)), "camera_adjust")
+    if pose_mode == L.FNR_POSE_SO3XR3:
+        L.check(lib.fnr_camera_adjust(L.ptr(image_set.c2w), L.ptr(ids), ids.numel(), L.ptr(_f32c(pose_adjustment)),
+                                      L.ptr(out), L.stream_ptr(out.device)), "camera_adjust")
+    else:
+        L.check(lib.fnr_camera_adjust_mode(L.ptr(image_set.c2w), L.ptr(ids), ids.numel(), L.ptr(_f32c(pose_adjustment)),
+                                           pose_mode, L.ptr(out), L.stream_ptr(out.device)), "camera_adjust_mode")
     return out
 
 
 def camera_pose_grad(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, cam: Tensor, pose_adjustment: Tensor,
                      c2w_adjusted: Tensor, d_origins: Tensor, d_directions: Tensor, pose_grad: Tensor,
-                     cams: Optional[CameraTableArg] = None) -> None:
+                     cams: Optional[CameraTableArg] = None, pose_mode: int = L.FNR_POSE_SO3XR3) -> None:
     """pose_grad [n_train,6] += d(loss)/d(pose_adjustment) from the ray gradients of the rays drawn with `u`
-    (cams: through that camera table, fnr_camera_pose_grad_cams)."""
+    (cams: through that camera table, fnr_camera_pose_grad_cams; pose_mode: the exponential map the cameras were
+    adjusted with)."""
     lib = L.load()
     ids = train_ids.to(torch.int64).contiguous()
     rest = (L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)), L.ptr(cam), L.ptr(_f32c(pose_adjustment)),
             L.ptr(c2w_adjusted), L.ptr(d_origins), L.ptr(d_directions), L.ptr(pose_grad), L.stream_ptr(u.device))
-    if cams is None:
+    if pose_mode != L.FNR_POSE_SO3XR3:
+        L.check(lib.fnr_camera_pose_grad_mode(C.byref(image_set.c), _table_ref(cams, image_set), pose_mode, *rest),
+                "camera_pose_grad_mode")
+    elif cams is None:
         L.check(lib.fnr_camera_pose_grad(C.byref(image_set.c), *rest), "camera_pose_grad")
     else:
         L.check(lib.fnr_camera_pose_grad_cams(C.byref(image_set.c), cams.ref(image_set), *rest), "camera_pose_grad_cams")
@@ -1002,14 +1017,17 @@ def camera_pose_grad(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, cam: 
 
 def camera_pose_grad_adam(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, cam: Tensor, c2w_adjusted: Tensor,
                           d_origins: Tensor, d_directions: Tensor, pose_grad: Tensor, adam: L.fnr_table_adam,
-                          cams: Optional[CameraTableArg] = None) -> None:
+                          cams: Optional[CameraTableArg] = None, pose_mode: int = L.FNR_POSE_SO3XR3) -> None:
     """camera_pose_grad + the pose table's Adam / RAdam step (adam.params = pose_adjustment) in one launch; pose_grad
     is consumed and left zero."""
     lib = L.load()
     ids = train_ids.to(torch.int64).contiguous()
     rest = (L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)), L.ptr(cam), L.ptr(c2w_adjusted), L.ptr(d_origins),
             L.ptr(d_directions), L.ptr(pose_grad), C.byref(adam), L.stream_ptr(u.device))
-    if cams is None:
+    if pose_mode != L.FNR_POSE_SO3XR3:
+        L.check(lib.fnr_camera_pose_grad_adam_mode(C.byref(image_set.c), _table_ref(cams, image_set), pose_mode, *rest),
+                "camera_pose_grad_adam_mode")
+    elif cams is None:
         L.check(lib.fnr_camera_pose_grad_adam(C.byref(image_set.c), *rest), "camera_pose_grad_adam")
     else:
         L.check(lib.fnr_camera_pose_grad_adam_cams(C.byref(image_set.c), cams.ref(image_set), *rest),
@@ -1018,9 +1036,10 @@ def camera_pose_grad_adam(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, 
 
 def train_prologue(image_set: ImageSetArg, train_ids: Tensor, n_rays: int, seed: int, offset: int,
                    pose_adjustment: Optional[Tensor], near: float, far: float, S0: int, n_jitter: int = 3,
-                   spacing_kind: int = 1, cams: Optional[CameraTableArg] = None) -> dict:
+                   spacing_kind: int = 1, cams: Optional[CameraTableArg] = None,
+                   pose_mode: int = L.FNR_POSE_SO3XR3) -> dict:
     """fnr_train_prologue: random numbers + camera adjust + pixel sampling + level-0 spaced sampling in one launch
-    (cams: rays through that camera table, fnr_train_prologue_cams)."""
+    (cams: rays through that camera table, fnr_train_prologue_cams; pose_mode: the exponential map of pose_adjustment)."""
     lib = L.load()
     dev = image_set.images.device
     R = int(n_rays)
@@ -1042,7 +1061,10 @@ def train_prologue(image_set: ImageSetArg, train_ids: Tensor, n_rays: int, seed:
             L.ptr(out["origins"]), L.ptr(out["directions"]), L.ptr(out["cam"]), L.ptr(out["image"]),
             L.ptr(out["mask"]), float(near), float(far), spacing_kind, S0, L.ptr(base),
             L.ptr(out["spacing"]), L.ptr(out["euclid"]), L.stream_ptr(dev))
-    if cams is None:
+    if pose_mode != L.FNR_POSE_SO3XR3:
+        L.check(lib.fnr_train_prologue_mode(C.byref(image_set.c), _table_ref(cams, image_set), pose_mode, *rest),
+                "train_prologue_mode")
+    elif cams is None:
         L.check(lib.fnr_train_prologue(C.byref(image_set.c), *rest), "train_prologue")
     else:
         L.check(lib.fnr_train_prologue_cams(C.byref(image_set.c), cams.ref(image_set), *rest), "train_prologue_cams")

@@ -89,6 +89,8 @@ FNR_MAX_ADAM_SPANS = 8
 FNR_ADAM_DEV_SCALAR_FLOATS = 32      # fnr_adam_step_spans_dev: the caller's scalar block
 FNR_MAX_PROPOSAL_LEVELS = 4
 FNR_MAX_POSITION_SOURCES = 4         # fnr_position_grad_reduce_multi
+FNR_POSE_SO3XR3, FNR_POSE_SE3 = 0, 1     # pose_mode of the fnr_*_mode entry points (CameraOptimizerConfig.mode)
+POSE_MODES = {"SO3xR3": FNR_POSE_SO3XR3, "SE3": FNR_POSE_SE3}
 FNR_TRAIN_PROLOGUE_MAX_JITTER = 5    # fnr_train_prologue: n_jitter in 1..5
 FNR_TRAIN_LOSSES_ACCUM_FLOATS = 4 * FNR_LOSS_SLOTS + 33 * 32
 
@@ -203,6 +205,13 @@ SIGNATURES = {
                                        _vp, _vp]),
     "fnr_camera_pose_grad_adam_cams": (_i, [P(fnr_image_set), P(fnr_camera_table), _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp,
                                             _vp, P(fnr_table_adam), _vp]),
+    "fnr_camera_adjust_mode": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "fnr_train_prologue_mode": (_i, [P(fnr_image_set), P(fnr_camera_table), _i, _vp, _i, _i64, C.c_uint64, C.c_uint64, _vp,
+                                     _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    "fnr_camera_pose_grad_mode": (_i, [P(fnr_image_set), P(fnr_camera_table), _i, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp]),
+    "fnr_camera_pose_grad_adam_mode": (_i, [P(fnr_image_set), P(fnr_camera_table), _i, _vp, _i, _i64, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, P(fnr_table_adam), _vp]),
     "fnr_image_metrics_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fnr_image_metrics": (_i, [_i, _i, _vp, _vp, _vp, _vp, P(C.c_float), _vp, _vp, C.c_size_t, _vp]),
     "fnr_program_create": (_i, [P(_vp)]),

@@ -13,11 +13,30 @@ import torch
 from torch import Tensor, nn
 
 from .. import _kernels as K
+from .. import _lib as L
+
+
+def _padded_rows(num_cameras: int, device) -> Tensor:
+    """Zeros [num_cameras, 6] at the start of a storage padded to a multiple of 4 floats: the optimiser kernel of
+    CameraAdam.step() works on float4 chunks, and an odd camera count ends in the middle of one."""
+    n = 6 * num_cameras
+    return torch.zeros((n + 3) // 4 * 4, device=device)[:n].view(num_cameras, 6)
+
+
+def _padded_flat(rows: Tensor) -> Tensor:
+    """The whole padded storage of a _padded_rows() tensor, flat (its padding lanes included)."""
+    n = (rows.numel() + 3) // 4 * 4
+    if n == rows.numel() and rows.is_contiguous():
+        return rows.view(-1)
+    if not rows.is_contiguous() or rows.untyped_storage().nbytes() < 4 * (rows.storage_offset() + n):
+        raise RuntimeError("the pose table, its .grad or a moment was replaced by a tensor without the padding to a multiple "
+                           "of 4 floats (copy into the tensors CameraOptimizer / CameraAdam allocated instead)")
+    return rows.as_strided((n,), (1,), rows.storage_offset())
 
 
 @dataclass
 class CameraOptimizerConfig:
-    mode: str = "off"                      # "off" | "SO3xR3"  ("SE3" is not built)
+    mode: str = "off"                      # "off" | "SO3xR3" | "SE3"  (nerfstudio's three values)
     position_noise_std: float = 0.0        # nerfstudio fields kept for config compatibility; noise is not built
     orientation_noise_std: float = 0.0
     lr: float = 6e-4                       # AdamOptimizerConfig(lr=6e-4, eps=1e-8, weight_decay=1e-2)
@@ -36,17 +55,20 @@ class CameraOptimizer(nn.Module):
 
     def __init__(self, config: CameraOptimizerConfig, num_cameras: int, device) -> None:
         super().__init__()
-        if config.mode not in ("off", "SO3xR3"):
-            raise NotImplementedError(f"camera optimizer mode {config.mode!r} is not built (off | SO3xR3)")
+        if config.mode != "off" and config.mode not in L.POSE_MODES:
+            raise ValueError(f"camera optimizer mode {config.mode!r} (off | SO3xR3 | SE3)")
         if config.position_noise_std != 0.0 or config.orientation_noise_std != 0.0:
             raise NotImplementedError("pose noise is not built")
         self.config = config
         self.num_cameras = num_cameras
         self.device = torch.device(device)
-        if config.mode == "SO3xR3":
-            # padded to a multiple of 4 floats for the fused Adam kernel (540 floats for 90 cameras already are)
-            self.pose_adjustment = nn.Parameter(torch.zeros(num_cameras, 6, device=self.device))
-            self.pose_adjustment.grad = torch.zeros_like(self.pose_adjustment)
+        # the exponential map of the pose rows: pose_mode of the fnr_*_mode entry points
+        self.pose_mode = L.POSE_MODES.get(config.mode, L.FNR_POSE_SO3XR3)
+        if config.mode != "off":
+            # [num_cameras, 6] views of storages padded to a multiple of 4 floats for the float4 optimiser kernel (540
+            # floats for 90 cameras already are); the padding lanes are zero and stay zero (p = g = 0 under L2 decay)
+            self.pose_adjustment = nn.Parameter(_padded_rows(num_cameras, self.device))
+            self.pose_adjustment.grad = _padded_rows(num_cameras, self.device)
         self._identity = None
 
     @property
@@ -54,7 +76,8 @@ class CameraOptimizer(nn.Module):
         return self.config.mode != "off"
 
     def forward(self, indices: Tensor) -> Tensor:
-        """[N,3,4] camera-to-camera corrections exp_map_SO3xR3(pose_adjustment[indices]) (identity when off)."""
+        """[N,3,4] camera-to-camera corrections exp_map_SO3xR3 | exp_map_SE3 (pose_adjustment[indices]) (identity when
+        off)."""
         n = indices.shape[0]
         if not self.enabled:
             return torch.eye(4, device=self.device)[None, :3, :4].tile(n, 1, 1)
@@ -63,13 +86,21 @@ class CameraOptimizer(nn.Module):
             self._identity = K.ImageSetArg(torch.zeros(1, 1, 1, 3, dtype=torch.uint8, device=self.device),
                                            torch.zeros(1, 1, 1, dtype=torch.uint8, device=self.device), eye, 1, 1, 0, 0)
             self._all = torch.arange(self.num_cameras, device=self.device)
-        return K.camera_adjust(self._identity, self._all, self.pose_adjustment.data)[indices.long()]
+        return K.camera_adjust(self._identity, self._all, self.pose_adjustment.data, pose_mode=self.pose_mode)[indices.long()]
 
     def adjusted_cameras(self, image_set: "K.ImageSetArg", train_ids: Tensor) -> Optional[Tensor]:
         """c2w' [n_train,3,4] = pose_utils.multiply(c2w[train_ids], forward(arange(n_train))); None when off."""
         if not self.enabled:
             return None
-        return K.camera_adjust(image_set, train_ids, self.pose_adjustment.data)
+        return K.camera_adjust(image_set, train_ids, self.pose_adjustment.data, pose_mode=self.pose_mode)
+
+    def get_metrics_dict(self) -> dict:
+        """nerfstudio's camera_opt_translation / camera_opt_rotation (fruit_pipeline.py:133-142): the norms of the two
+        halves of the pose table, as device scalars; {} when off."""
+        if not self.enabled:
+            return {}
+        pose = self.pose_adjustment.data
+        return {"camera_opt_translation": pose[:, :3].norm(), "camera_opt_rotation": pose[:, 3:].norm()}
 
     def get_param_groups(self) -> dict:
         return {self.config.param_group: list(self.parameters())} if self.enabled else {}
@@ -90,10 +121,8 @@ class CameraAdam:
         self.betas = betas
         self.step_count = 0
         p = camera_optimizer.pose_adjustment
-        if p.numel() % 4 != 0:
-            raise NotImplementedError("pose table size must be a multiple of 4 floats (num_cameras even)")
-        self.exp_avg = torch.zeros_like(p.data)
-        self.exp_avg_sq = torch.zeros_like(p.data)
+        self.exp_avg = _padded_rows(p.shape[0], p.device)     # padded like the table: step() runs on the whole storages
+        self.exp_avg_sq = _padded_rows(p.shape[0], p.device)
 
     def fused_step_args(self, grad_scale: float = 1.0):
         """Advance the step count and return the fnr_table_adam of THIS update for a kernel that applies it itself
@@ -123,5 +152,5 @@ class CameraAdam:
         lr = c.lr if c.lr_final is None else exponential_decay_lr(self.step_count - 1, c.lr, c.lr_final, c.max_steps)
         p = self.opt.pose_adjustment
         fn = K.adam_step if self.algorithm == "adam" else K.radam_step
-        fn(p.data.view(-1), p.grad.view(-1), self.exp_avg.view(-1), self.exp_avg_sq.view(-1), lr,
+        fn(_padded_flat(p.data), _padded_flat(p.grad), _padded_flat(self.exp_avg), _padded_flat(self.exp_avg_sq), lr,
            self.betas[0], self.betas[1], c.eps, self.step_count, grad_scale, True, weight_decay=c.weight_decay)

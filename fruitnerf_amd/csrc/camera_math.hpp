@@ -1,6 +1,6 @@
-// camera_math.hpp — SO3xR3 exponential map and pose composition shared by camera_opt.hip (k_camera_adjust,
+// camera_math.hpp — SO3xR3 and SE3 exponential maps and pose composition shared by camera_opt.hip (k_camera_adjust,
 // k_camera_pose_grad) and pixel_sampler.hip (fnr_train_prologue computes a ray's corrected camera in place).
-// nerfstudio 0.3.2 CameraOptimizer(mode="SO3xR3") semantics, see camera_opt.hip.
+// nerfstudio 0.3.2 CameraOptimizer(mode="SO3xR3" | "SE3") semantics, see camera_opt.hip.
 // pixel_direction: a pixel's camera-frame direction through a per-image camera table (fnr_camera_table: intrinsics +
 // OpenCV distortion), shared by every kernel of the _cams entry points.
 #pragma once
@@ -30,15 +30,119 @@ __device__ __forceinline__ SO3 so3_exp(const float* w) {
   return s;
 }
 
-// out [3,4] = multiply(M [3,4], exp_map_SO3xR3(tv [6])):  R' = R1 R,  t' = t1 + R1 t
+// ---- SE3 (nerfstudio 0.3.2 lie_groups.exp_map_SE3, restated) ---------------------------------------------------------------
+// tv = (v, w): theta = |w| (no clamp), s = theta^2;
+//   R = c I + b_r w w^T + a_r K(w),   t = a_t v + b_t (w x v) + c_t w (w . v)
+// theta >= 1e-2:  c = cos, a_r = a_t = sin / theta, b_r = b_t = (1 - cos) / s, c_t = (theta - sin) / theta^3
+// theta <  1e-2:  c = 8 / (4 + s) - 1, a_r = c / 2 + 1 / 2, b_r = a_r / 2;  a_t = 1 - s / 6, b_t = 1 / 2 - s / 24,
+//                 c_t = 1 / 6 - s / 120   (the library's two different polynomials; threshold and polynomials are semantics)
+// The derivatives are in the branch's variable x (theta above the threshold, s below); D = dx/dw without the factor w
+// (1 / theta, or 2).  Host-callable: the arithmetic is checked on the CPU as well.
+struct SE3Coef {
+  float c, ar, br, at, bt, ct;
+  float dc, dar, dbr, dat, dbt, dct, D;
+};
+
+__host__ __device__ __forceinline__ SE3Coef se3_coef(const float* w) {
+  SE3Coef k;
+  const float s = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  const float th = sqrtf(s);
+  if (th < 1e-2f) {
+    const float q = 4.0f + s;
+    k.c = 8.0f / q - 1.0f;
+    k.ar = 0.5f * k.c + 0.5f;
+    k.br = 0.5f * k.ar;
+    k.at = 1.0f - s / 6.0f;
+    k.bt = 0.5f - s / 24.0f;
+    k.ct = 1.0f / 6.0f - s / 120.0f;
+    k.dc = -8.0f / (q * q);
+    k.dar = 0.5f * k.dc;
+    k.dbr = 0.25f * k.dc;
+    k.dat = -1.0f / 6.0f;
+    k.dbt = -1.0f / 24.0f;
+    k.dct = -1.0f / 120.0f;
+    k.D = 2.0f;
+  } else {
+    const float inv = 1.0f / th, sn = sinf(th), sh = sinf(0.5f * th);
+    k.c = cosf(th);
+    k.ar = k.at = sn * inv;
+    k.br = k.bt = 2.0f * sh * sh / s;       // (1 - cos) / theta^2 without the cancellation
+    k.ct = (th - sn) / (th * s);
+    k.dc = -sn;
+    k.dar = k.dat = (k.c - k.ar) * inv;     // d(sin t / t)/dt
+    k.dbr = k.dbt = (k.ar - 2.0f * k.br) * inv;   // d((1 - cos t) / t^2)/dt
+    k.dct = (k.br - 3.0f * k.ct) * inv;     // d((t - sin t) / t^3)/dt
+    k.D = inv;
+  }
+  return k;
+}
+
+// exp_map_SE3(tv [6]) -> R [9] row-major, t [3]
+__host__ __device__ __forceinline__ void se3_exp(const float* __restrict__ tv, float (&R)[9], float (&t)[3]) {
+  const float* v = tv;
+  const float* w = tv + 3;
+  const SE3Coef k = se3_coef(w);
+  const float x = w[0], y = w[1], z = w[2];
+  const float K[9] = {0.f, -z, y, z, 0.f, -x, -y, x, 0.f};
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) R[3 * a + b] = ((a == b) ? k.c : 0.0f) + k.br * (w[a] * w[b]) + k.ar * K[3 * a + b];
+  const float wv = x * v[0] + y * v[1] + z * v[2];
+  const float cr[3] = {y * v[2] - z * v[1], z * v[0] - x * v[2], x * v[1] - y * v[0]};  // w x v
+#pragma unroll
+  for (int a = 0; a < 3; ++a) t[a] = k.at * v[a] + k.bt * cr[a] + k.ct * (w[a] * wv);
+}
+
+// Backward of se3_exp: GR [9] = dL/dR, gt [3] = dL/dt  ->  gv [3] = dL/dv, gw [3] = dL/dw.  Finite at w = 0, where
+// dL/dw = gK + (v x gt) / 2: a pose table that starts at zero trains.
+__host__ __device__ __forceinline__ void se3_exp_bwd(const float* __restrict__ tv, const float (&GR)[9], const float (&gt)[3],
+                                                     float (&gv)[3], float (&gw)[3]) {
+  const float* v = tv;
+  const float* w = tv + 3;
+  const SE3Coef k = se3_coef(w);
+  const float x = w[0], y = w[1], z = w[2];
+  const float wg = x * gt[0] + y * gt[1] + z * gt[2], wv = x * v[0] + y * v[1] + z * v[2];
+  const float gv_ = gt[0] * v[0] + gt[1] * v[1] + gt[2] * v[2];
+  const float gxw[3] = {gt[1] * z - gt[2] * y, gt[2] * x - gt[0] * z, gt[0] * y - gt[1] * x};              // gt x w
+  const float vxg[3] = {v[1] * gt[2] - v[2] * gt[1], v[2] * gt[0] - v[0] * gt[2], v[0] * gt[1] - v[1] * gt[0]};  // v x gt
+  // <GR, K(e_i)>;  (GR + GR^T) w;  tr GR;  w^T GR w;  <GR, K(w)> = w . gK;  gt . (w x v) = w . (v x gt)
+  const float gK[3] = {GR[7] - GR[5], GR[2] - GR[6], GR[3] - GR[1]};
+  const float Sw[3] = {(GR[0] + GR[0]) * x + (GR[1] + GR[3]) * y + (GR[2] + GR[6]) * z,
+                       (GR[3] + GR[1]) * x + (GR[4] + GR[4]) * y + (GR[5] + GR[7]) * z,
+                       (GR[6] + GR[2]) * x + (GR[7] + GR[5]) * y + (GR[8] + GR[8]) * z};
+  const float tr = GR[0] + GR[4] + GR[8];
+  const float wGw = 0.5f * (x * Sw[0] + y * Sw[1] + z * Sw[2]);
+  const float gkw = x * gK[0] + y * gK[1] + z * gK[2];
+  const float gwv = x * vxg[0] + y * vxg[1] + z * vxg[2];
+  const float through = k.D * ((k.dc * tr + k.dbr * wGw + k.dar * gkw) + (k.dat * gv_ + k.dbt * gwv + k.dct * (wg * wv)));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    gv[i] = k.at * gt[i] + k.bt * gxw[i] + k.ct * (w[i] * wg);
+    gw[i] = (k.ar * gK[i] + k.br * Sw[i]) + (k.bt * vxg[i] + k.ct * (wv * gt[i] + wg * v[i])) + w[i] * through;
+  }
+}
+
+// out [3,4] = multiply(M [3,4], exp_map(tv [6])):  R' = R1 R,  t' = t1 + R1 t;  MODE: FNR_POSE_SO3XR3 (t = tv[:3]) or
+// FNR_POSE_SE3
+template <int MODE = FNR_POSE_SO3XR3>
 __device__ __forceinline__ void adjusted_camera(const float* __restrict__ M, const float* __restrict__ tv, float (&out)[12]) {
-  const SO3 s = so3_exp(tv + 3);
+  float R[9], t[3];
+  if constexpr (MODE == FNR_POSE_SE3) {
+    se3_exp(tv, R, t);
+  } else {
+    const SO3 s = so3_exp(tv + 3);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = s.R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = tv[i];
+  }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
 #pragma unroll
     for (int b = 0; b < 3; ++b)
-      out[4 * a + b] = M[4 * a] * s.R[b] + M[4 * a + 1] * s.R[3 + b] + M[4 * a + 2] * s.R[6 + b];
-    out[4 * a + 3] = M[4 * a + 3] + (M[4 * a] * tv[0] + M[4 * a + 1] * tv[1] + M[4 * a + 2] * tv[2]);
+      out[4 * a + b] = M[4 * a] * R[b] + M[4 * a + 1] * R[3 + b] + M[4 * a + 2] * R[6 + b];
+    out[4 * a + 3] = M[4 * a + 3] + (M[4 * a] * t[0] + M[4 * a + 1] * t[1] + M[4 * a + 2] * t[2]);
   }
 }
 

@@ -1,4 +1,4 @@
-// camera_opt.hip — nerfstudio CameraOptimizer(mode="SO3xR3") on the device: the pose corrections the reference's
+// camera_opt.hip — nerfstudio CameraOptimizer(mode="SO3xR3" | "SE3") on the device: the pose corrections the reference's
 // datamanager applies to the training cameras and learns from the ray gradients
 // (/root/reference/fruit_nerf/fruit_nerf_config.py:39-43; metrics camera_opt_translation / camera_opt_rotation at
 // fruit_pipeline.py:133-142).  nerfstudio 0.3.2 semantics (restated):
@@ -9,19 +9,22 @@
 // k_camera_adjust builds c2w' (thread = camera); k_camera_pose_grad maps d(loss)/d(origins, directions) back to the
 // [n_train, 6] tangent vectors: one workgroup per camera gathers its rays (ballot), so there are no atomics on the
 // shared rows.
+// mode="SE3" (MODE = FNR_POSE_SE3): delta[k] = exp_map_SE3(pose_adjustment[k]) — camera_math.hpp::se3_exp, whose translation
+// depends on the rotation part; composition, ray generation and the ray gradients that feed the tail are the same.
 #include "camera_math.hpp"
 #include "sequencer.hpp"
 
 namespace fnr {
 
-// c2w' = multiply(c2w[train_ids[k]], exp_map_SO3xR3(pose[k]))
+// c2w' = multiply(c2w[train_ids[k]], exp_map_SO3xR3 | exp_map_SE3 (pose[k]))
+template <int MODE>
 __global__ __launch_bounds__(64) void k_camera_adjust(const float* __restrict__ c2w, const long long* __restrict__ train_ids,
                                                       int n_train, const float* __restrict__ pose,
                                                       float* __restrict__ c2w_adj) {
   const int k = blockIdx.x * 64 + threadIdx.x;
   if (k >= n_train) return;
   float out[12];
-  adjusted_camera(c2w + train_ids[k] * 12, pose + 6 * k, out);
+  adjusted_camera<MODE>(c2w + train_ids[k] * 12, pose + 6 * k, out);
 #pragma unroll
   for (int i = 0; i < 12; ++i) c2w_adj[12 * k + i] = out[i];
 }
@@ -39,7 +42,8 @@ struct PinholeDev {
 // zero_grad, one launch less per step.
 // CAMS: the rays' camera-frame directions are recomputed through the camera table (pixel_direction) instead of the pinhole;
 // they do not depend on the pose, so the gradient formulas are the same.
-template <bool ADAM, bool CAMS>
+// MODE: the single-thread tail maps dL/dR', dL/dt' to the six tangent components of that exponential map.
+template <bool ADAM, bool CAMS, int MODE>
 __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, CameraTableDev cams, const float* __restrict__ c2w,
                                                           const long long* __restrict__ train_ids, long long n_rays,
                                                           const float* __restrict__ u, const int* __restrict__ cam_idx,
@@ -59,6 +63,7 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, Camera
   // what the single-thread tail needs (all workgroup-uniform) is fetched NOW: the kernel is a chain of dependent
   // memory round trips (~1.5 us each), and these were four more of them at its end
   float Mk[12], wk[3], g_old[6], Pk[6], Mm[6], Vk[6];
+  float tvk[6];         // SE3: the whole tangent row (the translation's gradient needs v and w)
   float Kk[4], Dk[6];   // CAMS: the camera's intrinsics and distortion rows
   const bool distorted = CAMS && cams.distortion != nullptr;
   {
@@ -73,6 +78,10 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, Camera
     for (int i = 0; i < 12; ++i) Mk[i] = Msrc[i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) wk[i] = pose[6 * k + 3 + i];
+    if constexpr (MODE == FNR_POSE_SE3) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) tvk[i] = pose[6 * k + i], tvk[3 + i] = wk[i];
+    }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       g_old[i] = pose_grad[6 * k + i];
@@ -166,42 +175,51 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, Camera
     for (int b = 0; b < 3; ++b) GR[3 * a + b] = M[a] * G[b] + M[4 + a] * G[3 + b] + M[8 + a] * G[6 + b];
     gtt[a] = M[a] * gt[0] + M[4 + a] * gt[1] + M[8 + a] * gt[2];
   }
-  const float* w = wk;
-  const SO3 s = so3_exp(w);
-  // dR/dw_i = f1 K_i + f2 (K_i K + K K_i) + (df1/dw_i) K + (df2/dw_i) K^2;  d theta/d w_i = w_i / theta above the clamp
-  const float th = s.theta, sn = sinf(th), cs = cosf(th);
-  const float df1 = (th * cs - sn) / (th * th);                    // d(sin t / t)/dt
-  const float df2 = (th * sn - 2.0f * (1.0f - cs)) / (th * th * th);  // d((1 - cos t)/t^2)/dt
-  const bool above = s.theta2_raw > 1e-4f;  // clamp(nrms, 1e-4): zero gradient through theta below the threshold
-  const float x = w[0], y = w[1], z = w[2];
-  const float K[9] = {0.f, -z, y, z, 0.f, -x, -y, x, 0.f};
-  const float K2[9] = {-(y * y + z * z), x * y, x * z, x * y, -(x * x + z * z), y * z, x * z, y * z, -(x * x + y * y)};
-  float gk = 0.0f, gk2 = 0.0f;  // <GR, K>, <GR, K^2>
+  float gv[3], gw[3];   // dL/d(tangent[:3]), dL/d(tangent[3:])
+  if constexpr (MODE == FNR_POSE_SE3) {
+    se3_exp_bwd(tvk, GR, gtt, gv, gw);
+  } else {
+    const float* w = wk;
+    const SO3 s = so3_exp(w);
+    // dR/dw_i = f1 K_i + f2 (K_i K + K K_i) + (df1/dw_i) K + (df2/dw_i) K^2;  d theta/d w_i = w_i / theta above the clamp
+    const float th = s.theta, sn = sinf(th), cs = cosf(th);
+    const float df1 = (th * cs - sn) / (th * th);                    // d(sin t / t)/dt
+    const float df2 = (th * sn - 2.0f * (1.0f - cs)) / (th * th * th);  // d((1 - cos t)/t^2)/dt
+    const bool above = s.theta2_raw > 1e-4f;  // clamp(nrms, 1e-4): zero gradient through theta below the threshold
+    const float x = w[0], y = w[1], z = w[2];
+    const float K[9] = {0.f, -z, y, z, 0.f, -x, -y, x, 0.f};
+    const float K2[9] = {-(y * y + z * z), x * y, x * z, x * y, -(x * x + z * z), y * z, x * z, y * z, -(x * x + y * y)};
+    float gk = 0.0f, gk2 = 0.0f;  // <GR, K>, <GR, K^2>
 #pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    gk += GR[i] * K[i];
-    gk2 += GR[i] * K2[i];
+    for (int i = 0; i < 9; ++i) {
+      gk += GR[i] * K[i];
+      gk2 += GR[i] * K2[i];
+    }
+    // <GR, K_i> with K_0 = skew(e_x) etc.;  <GR, K_i K + K K_i> = d<GR, K^2>/dw_i with K^2 = w w^T - |w|^2 I
+    const float gK[3] = {GR[7] - GR[5], GR[2] - GR[6], GR[3] - GR[1]};
+    const float tr = GR[0] + GR[4] + GR[8];
+    const float Sw[3] = {(GR[0] + GR[0]) * x + (GR[1] + GR[3]) * y + (GR[2] + GR[6]) * z,
+                         (GR[3] + GR[1]) * x + (GR[4] + GR[4]) * y + (GR[5] + GR[7]) * z,
+                         (GR[6] + GR[2]) * x + (GR[7] + GR[5]) * y + (GR[8] + GR[8]) * z};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float wi = (i == 0) ? x : (i == 1) ? y : z;
+      const float dth = above ? wi / th : 0.0f;
+      gw[i] = s.f1 * gK[i] + s.f2 * (Sw[i] - 2.0f * wi * tr) + dth * (df1 * gk + df2 * gk2);
+      gv[i] = gtt[i];
+    }
   }
-  // <GR, K_i> with K_0 = skew(e_x) etc.;  <GR, K_i K + K K_i> = d<GR, K^2>/dw_i with K^2 = w w^T - |w|^2 I
-  const float gK[3] = {GR[7] - GR[5], GR[2] - GR[6], GR[3] - GR[1]};
-  const float tr = GR[0] + GR[4] + GR[8];
-  const float Sw[3] = {(GR[0] + GR[0]) * x + (GR[1] + GR[3]) * y + (GR[2] + GR[6]) * z,
-                       (GR[3] + GR[1]) * x + (GR[4] + GR[4]) * y + (GR[5] + GR[7]) * z,
-                       (GR[6] + GR[2]) * x + (GR[7] + GR[5]) * y + (GR[8] + GR[8]) * z};
   float* out = pose_grad + 6 * k;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    const float wi = (i == 0) ? x : (i == 1) ? y : z;
-    const float dth = above ? wi / th : 0.0f;
-    const float g = s.f1 * gK[i] + s.f2 * (Sw[i] - 2.0f * wi * tr) + dth * (df1 * gk + df2 * gk2);
     if constexpr (!ADAM) {
-      out[3 + i] = g_old[3 + i] + g;
-      out[i] = g_old[i] + gtt[i];
+      out[3 + i] = g_old[3 + i] + gw[i];
+      out[i] = g_old[i] + gv[i];
     } else {
       float* P = reinterpret_cast<float*>(adam.p) + 6 * k;
       float* M2 = reinterpret_cast<float*>(adam.m) + 6 * k;
       float* V = reinterpret_cast<float*>(adam.v) + 6 * k;
-      const float gr = g_old[3 + i] + g, gtr = g_old[i] + gtt[i];
+      const float gr = g_old[3 + i] + gw[i], gtr = g_old[i] + gv[i];
       table_adam_update(adam, gr, Pk[3 + i], Mm[3 + i], Vk[3 + i]);
       table_adam_update(adam, gtr, Pk[i], Mm[i], Vk[i]);
       P[3 + i] = Pk[3 + i], M2[3 + i] = Mm[3 + i], V[3 + i] = Vk[3 + i];
@@ -216,21 +234,42 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, Camera
 
 using namespace fnr;
 
-extern "C" int fnr_camera_adjust(const float* c2w, const int64_t* train_ids, int n_train, const float* pose_adjustment,
-                                 float* c2w_adjusted, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_camera_adjust");
+static bool pose_mode_ok(int pose_mode) { return pose_mode == FNR_POSE_SO3XR3 || pose_mode == FNR_POSE_SE3; }
+
+static int camera_adjust(const char* name, const float* c2w, const int64_t* train_ids, int n_train,
+                         const float* pose_adjustment, int pose_mode, float* c2w_adjusted, void* stream) {
+  FNR_SEQ_UNRECORDABLE(name);
+  FNR_CHECK_ARG(pose_mode_ok(pose_mode), "camera_adjust: pose_mode %d (0 = SO3xR3, 1 = SE3)", pose_mode);
   FNR_CHECK_ARG(c2w && train_ids && pose_adjustment && c2w_adjusted && n_train > 0, "camera_adjust: null argument");
-  hipLaunchKernelGGL(k_camera_adjust, dim3((unsigned)((n_train + 63) / 64)), dim3(64), 0, as_stream(stream), c2w,
+  const auto kernel = pose_mode == FNR_POSE_SE3 ? k_camera_adjust<FNR_POSE_SE3> : k_camera_adjust<FNR_POSE_SO3XR3>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_train + 63) / 64)), dim3(64), 0, as_stream(stream), c2w,
                      reinterpret_cast<const long long*>(train_ids), n_train, pose_adjustment, c2w_adjusted);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
 
+extern "C" int fnr_camera_adjust(const float* c2w, const int64_t* train_ids, int n_train, const float* pose_adjustment,
+                                 float* c2w_adjusted, void* stream) {
+  return camera_adjust("fnr_camera_adjust", c2w, train_ids, n_train, pose_adjustment, FNR_POSE_SO3XR3, c2w_adjusted, stream);
+}
+
+extern "C" int fnr_camera_adjust_mode(const float* c2w, const int64_t* train_ids, int n_train, const float* pose_adjustment,
+                                      int pose_mode, float* c2w_adjusted, void* stream) {
+  return camera_adjust("fnr_camera_adjust_mode", c2w, train_ids, n_train, pose_adjustment, pose_mode, c2w_adjusted, stream);
+}
+
+template <bool ADAM>
+static auto pose_grad_kernel(bool use_cams, int pose_mode) {
+  if (pose_mode == FNR_POSE_SE3) return use_cams ? k_camera_pose_grad<ADAM, true, FNR_POSE_SE3> : k_camera_pose_grad<ADAM, false, FNR_POSE_SE3>;
+  return use_cams ? k_camera_pose_grad<ADAM, true, FNR_POSE_SO3XR3> : k_camera_pose_grad<ADAM, false, FNR_POSE_SO3XR3>;
+}
+
 static int camera_pose_grad(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
-                            const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
+                            int pose_mode, const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
                             const int32_t* camera_indices, const float* pose_adjustment, const float* c2w_adjusted,
                             const float* d_origins, const float* d_directions, float* pose_grad, void* stream) {
   FNR_SEQ_UNRECORDABLE(name);
+  FNR_CHECK_ARG(pose_mode_ok(pose_mode), "camera_pose_grad: pose_mode %d (0 = SO3xR3, 1 = SE3)", pose_mode);
   FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "camera_pose_grad_cams: null camera table");
   FNR_CHECK_ARG(set && set->c2w && train_ids && u && camera_indices && pose_adjustment && c2w_adjusted && d_origins &&
                     d_directions && pose_grad && n_train > 0,
@@ -238,10 +277,9 @@ static int camera_pose_grad(const char* name, const fnr_image_set* set, const fn
   if (n_rays == 0) return FNR_OK;
   PinholeDev cam{set->H, set->W, set->fx, set->fy, set->cx, set->cy};
   const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
-  const auto kernel = use_cams ? k_camera_pose_grad<false, true> : k_camera_pose_grad<false, false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n_train), dim3(256), 0, as_stream(stream), cam, t, set->c2w,
-                     reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices, pose_adjustment,
-                     c2w_adjusted, d_origins, d_directions, pose_grad, TableAdam{});
+  hipLaunchKernelGGL(pose_grad_kernel<false>(use_cams, pose_mode), dim3((unsigned)n_train), dim3(256), 0, as_stream(stream),
+                     cam, t, set->c2w, reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices,
+                     pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, TableAdam{});
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -250,32 +288,43 @@ extern "C" int fnr_camera_pose_grad(const fnr_image_set* set, const int64_t* tra
                                     const float* u, const int32_t* camera_indices, const float* pose_adjustment,
                                     const float* c2w_adjusted, const float* d_origins, const float* d_directions,
                                     float* pose_grad, void* stream) {
-  return camera_pose_grad("fnr_camera_pose_grad", set, nullptr, false, train_ids, n_train, n_rays, u, camera_indices,
-                          pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
+  return camera_pose_grad("fnr_camera_pose_grad", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, u,
+                          camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
 }
 
 extern "C" int fnr_camera_pose_grad_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
                                          int n_train, int64_t n_rays, const float* u, const int32_t* camera_indices,
                                          const float* pose_adjustment, const float* c2w_adjusted, const float* d_origins,
                                          const float* d_directions, float* pose_grad, void* stream) {
-  return camera_pose_grad("fnr_camera_pose_grad_cams", set, cams, true, train_ids, n_train, n_rays, u, camera_indices,
-                          pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
+  return camera_pose_grad("fnr_camera_pose_grad_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, u,
+                          camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
 }
 
-static int camera_pose_grad_adam(const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
-                                 const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
+extern "C" int fnr_camera_pose_grad_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
+                                         const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
+                                         const int32_t* camera_indices, const float* pose_adjustment,
+                                         const float* c2w_adjusted, const float* d_origins, const float* d_directions,
+                                         float* pose_grad, void* stream) {
+  return camera_pose_grad("fnr_camera_pose_grad_mode", set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, u,
+                          camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
+}
+
+// name: the entry point that was called, which is what a step program lists for the recorded call
+static int camera_pose_grad_adam(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
+                                 int pose_mode, const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
                                  const int32_t* camera_indices, const float* c2w_adjusted, const float* d_origins,
                                  const float* d_directions, float* pose_grad, const fnr_table_adam* adam, void* stream) {
   if (seq::recording() && set && adam && (!use_cams || cams)) {
     const fnr_image_set set_ = *set;
     const fnr_camera_table cams_ = use_cams ? *cams : fnr_camera_table{nullptr, nullptr};
     const fnr_table_adam adam_ = *adam;
-    seq::push(use_cams ? "fnr_camera_pose_grad_adam_cams" : "fnr_camera_pose_grad_adam", [=](const fnr_step_scalars* sc) {
+    seq::push(name, [=](const fnr_step_scalars* sc) {
       const fnr_table_adam a = seq::patched(adam_, sc);
-      return camera_pose_grad_adam(&set_, &cams_, use_cams, train_ids, n_train, n_rays, u, camera_indices, c2w_adjusted,
-                                   d_origins, d_directions, pose_grad, &a, stream);
+      return camera_pose_grad_adam(name, &set_, &cams_, use_cams, pose_mode, train_ids, n_train, n_rays, u, camera_indices,
+                                   c2w_adjusted, d_origins, d_directions, pose_grad, &a, stream);
     });
   }
+  FNR_CHECK_ARG(pose_mode_ok(pose_mode), "camera_pose_grad_adam: pose_mode %d (0 = SO3xR3, 1 = SE3)", pose_mode);
   FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "camera_pose_grad_adam_cams: null camera table");
   FNR_CHECK_ARG(set && set->c2w && train_ids && u && camera_indices && c2w_adjusted && d_origins && d_directions &&
                     pose_grad && adam && n_train > 0,
@@ -285,11 +334,10 @@ static int camera_pose_grad_adam(const fnr_image_set* set, const fnr_camera_tabl
   if (rc) return rc;
   PinholeDev cam{set->H, set->W, set->fx, set->fy, set->cx, set->cy};
   const CameraTableDev ct = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
-  const auto kernel = use_cams ? k_camera_pose_grad<true, true> : k_camera_pose_grad<true, false>;
   // n_rays == 0 still takes the step (every pose parameter decays its moments)
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n_train), dim3(256), 0, as_stream(stream), cam, ct, set->c2w,
-                     reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices, adam->params,
-                     c2w_adjusted, d_origins, d_directions, pose_grad, t);
+  hipLaunchKernelGGL(pose_grad_kernel<true>(use_cams, pose_mode), dim3((unsigned)n_train), dim3(256), 0, as_stream(stream),
+                     cam, ct, set->c2w, reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices,
+                     adam->params, c2w_adjusted, d_origins, d_directions, pose_grad, t);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -298,8 +346,8 @@ extern "C" int fnr_camera_pose_grad_adam(const fnr_image_set* set, const int64_t
                                          const float* u, const int32_t* camera_indices, const float* c2w_adjusted,
                                          const float* d_origins, const float* d_directions, float* pose_grad,
                                          const fnr_table_adam* adam, void* stream) {
-  return camera_pose_grad_adam(set, nullptr, false, train_ids, n_train, n_rays, u, camera_indices, c2w_adjusted, d_origins,
-                               d_directions, pose_grad, adam, stream);
+  return camera_pose_grad_adam("fnr_camera_pose_grad_adam", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays,
+                               u, camera_indices, c2w_adjusted, d_origins, d_directions, pose_grad, adam, stream);
 }
 
 extern "C" int fnr_camera_pose_grad_adam_cams(const fnr_image_set* set, const fnr_camera_table* cams,
@@ -307,6 +355,15 @@ extern "C" int fnr_camera_pose_grad_adam_cams(const fnr_image_set* set, const fn
                                               const int32_t* camera_indices, const float* c2w_adjusted,
                                               const float* d_origins, const float* d_directions, float* pose_grad,
                                               const fnr_table_adam* adam, void* stream) {
-  return camera_pose_grad_adam(set, cams, true, train_ids, n_train, n_rays, u, camera_indices, c2w_adjusted, d_origins,
-                               d_directions, pose_grad, adam, stream);
+  return camera_pose_grad_adam("fnr_camera_pose_grad_adam_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train,
+                               n_rays, u, camera_indices, c2w_adjusted, d_origins, d_directions, pose_grad, adam, stream);
+}
+
+extern "C" int fnr_camera_pose_grad_adam_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
+                                              const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
+                                              const int32_t* camera_indices, const float* c2w_adjusted,
+                                              const float* d_origins, const float* d_directions, float* pose_grad,
+                                              const fnr_table_adam* adam, void* stream) {
+  return camera_pose_grad_adam("fnr_camera_pose_grad_adam_mode", set, cams, cams != nullptr, pose_mode, train_ids, n_train,
+                               n_rays, u, camera_indices, c2w_adjusted, d_origins, d_directions, pose_grad, adam, stream);
 }

@@ -97,7 +97,7 @@ struct PrologueArgs {
   int n_train;
   long long n_rays;
   unsigned long long seed, offset;
-  const float* pose;        // [n_train, 6] SO3xR3 tangents, or NULL (cameras as they are)
+  const float* pose;        // [n_train, 6] tangents of the kernel's MODE, or NULL (cameras as they are)
   float* c2w_adjusted;      // [n_train, 3, 4] out (with pose)
   float *u, *jitter;        // [R, 3], [n_jitter, R] out
   int n_jitter;             // <= 5
@@ -111,14 +111,14 @@ struct PrologueArgs {
   int nb_rays;              // workgroups of the per-ray role
 };
 
-template <bool CAMS>
+template <bool CAMS, int MODE>
 __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a, CameraTableDev cams) {
   if ((int)blockIdx.x < a.nb_rays) {
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
     // corrected cameras for the pose-gradient kernel: camera k by thread k of the launch (same arithmetic as per ray)
     if (a.pose && r < a.n_train) {
       float adj[12];
-      adjusted_camera(a.set.c2w + a.train_ids[r] * 12, a.pose + 6 * r, adj);
+      adjusted_camera<MODE>(a.set.c2w + a.train_ids[r] * 12, a.pose + 6 * r, adj);
 #pragma unroll
       for (int i = 0; i < 12; ++i) a.c2w_adjusted[12 * r + i] = adj[i];
     }
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a, CameraTa
     }
     float M[12];
     if (a.pose) {
-      adjusted_camera(a.set.c2w + img * 12, a.pose + 6 * k, M);
+      adjusted_camera<MODE>(a.set.c2w + img * 12, a.pose + 6 * k, M);
     } else {
 #pragma unroll
       for (int i = 0; i < 12; ++i) M[i] = a.set.c2w[img * 12 + i];
@@ -264,7 +264,9 @@ extern "C" int fnr_camera_rays(const float* c2w, const float* intrinsics, const 
   return FNR_OK;
 }
 
-static int train_prologue(const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams, const int64_t* train_ids,
+// name: the entry point that was called, which is what a step program lists for the recorded call
+static int train_prologue(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
+                          int pose_mode, const int64_t* train_ids,
                           int n_train, int64_t n_rays, uint64_t seed, uint64_t offset, const float* pose_adjustment,
                           float* c2w_adjusted, float* u, float* jitter, int n_jitter, float* origins, float* directions,
                           int32_t* camera_indices, float* image, float* fruit_mask, float near_plane, float far_plane,
@@ -273,12 +275,15 @@ static int train_prologue(const fnr_image_set* set, const fnr_camera_table* cams
   if (seq::recording() && set && (!use_cams || cams)) {
     const fnr_image_set set_ = *set;
     const fnr_camera_table cams_ = use_cams ? *cams : fnr_camera_table{nullptr, nullptr};
-    seq::push(use_cams ? "fnr_train_prologue_cams" : "fnr_train_prologue", [=](const fnr_step_scalars* sc) {
-      return train_prologue(&set_, &cams_, use_cams, train_ids, n_train, n_rays, seed, sc ? sc->prologue_offset : offset,
+    seq::push(name, [=](const fnr_step_scalars* sc) {
+      return train_prologue(name, &set_, &cams_, use_cams, pose_mode, train_ids, n_train, n_rays, seed,
+                            sc ? sc->prologue_offset : offset,
                             pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
                             fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
     });
   }
+  FNR_CHECK_ARG(pose_mode == FNR_POSE_SO3XR3 || pose_mode == FNR_POSE_SE3, "train_prologue: pose_mode %d (0 = SO3xR3, 1 = SE3)",
+                pose_mode);
   FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "train_prologue_cams: null camera table");
   FNR_CHECK_ARG(set && train_ids && u && jitter && origins && directions && camera_indices && image && fruit_mask &&
                     base_bins && spacing0 && euclid0,
@@ -302,7 +307,9 @@ static int train_prologue(const fnr_image_set* set, const fnr_camera_table* cams
   const long long nb_bins = (n_rays * (long long)(S0 + 1) + 255) / 256;
   FNR_PROF(OP_SAMPLE_SPACED, n_rays * (long long)(S0 + 1));
   const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
-  const auto kernel = use_cams ? k_train_prologue<true> : k_train_prologue<false>;
+  const auto kernel = pose_mode == FNR_POSE_SE3
+                          ? (use_cams ? k_train_prologue<true, FNR_POSE_SE3> : k_train_prologue<false, FNR_POSE_SE3>)
+                          : (use_cams ? k_train_prologue<true, FNR_POSE_SO3XR3> : k_train_prologue<false, FNR_POSE_SO3XR3>);
   hipLaunchKernelGGL(kernel, dim3((unsigned)(a.nb_rays + nb_bins)), dim3(256), 0, as_stream(stream), a, t);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
@@ -314,9 +321,9 @@ extern "C" int fnr_train_prologue(const fnr_image_set* set, const int64_t* train
                                   int32_t* camera_indices, float* image, float* fruit_mask, float near_plane,
                                   float far_plane, int spacing_kind, int S0, const float* base_bins, float* spacing0,
                                   float* euclid0, void* stream) {
-  return train_prologue(set, nullptr, false, train_ids, n_train, n_rays, seed, offset, pose_adjustment, c2w_adjusted, u,
-                        jitter, n_jitter, origins, directions, camera_indices, image, fruit_mask, near_plane, far_plane,
-                        spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+  return train_prologue("fnr_train_prologue", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, seed, offset,
+                        pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
+                        fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
 }
 
 extern "C" int fnr_train_prologue_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
@@ -326,7 +333,19 @@ extern "C" int fnr_train_prologue_cams(const fnr_image_set* set, const fnr_camer
                                        float* image, float* fruit_mask, float near_plane, float far_plane,
                                        int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
                                        void* stream) {
-  return train_prologue(set, cams, true, train_ids, n_train, n_rays, seed, offset, pose_adjustment, c2w_adjusted, u, jitter,
-                        n_jitter, origins, directions, camera_indices, image, fruit_mask, near_plane, far_plane,
-                        spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+  return train_prologue("fnr_train_prologue_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, seed, offset,
+                        pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
+                        fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+}
+
+extern "C" int fnr_train_prologue_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
+                                       const int64_t* train_ids, int n_train, int64_t n_rays, uint64_t seed, uint64_t offset,
+                                       const float* pose_adjustment, float* c2w_adjusted, float* u, float* jitter,
+                                       int n_jitter, float* origins, float* directions, int32_t* camera_indices,
+                                       float* image, float* fruit_mask, float near_plane, float far_plane,
+                                       int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
+                                       void* stream) {
+  return train_prologue("fnr_train_prologue_mode", set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, seed,
+                        offset, pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices,
+                        image, fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
 }

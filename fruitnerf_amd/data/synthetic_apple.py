@@ -206,7 +206,7 @@ class PixelBatcher:
 
     def sample(self, n_rays: int, camera_optimizer=None, level0: Optional[dict] = None):
         """One fused kernel on the HIP device (fnr_sample_pixels / fnr_train_prologue); a batch on the CPU raises.
-        camera_optimizer (cameras.camera_optimizers.CameraOptimizer, mode SO3xR3): rays come from the pose-corrected
+        camera_optimizer (cameras.camera_optimizers.CameraOptimizer, mode SO3xR3 or SE3): rays come from the pose-corrected
         cameras; `last_draw` keeps what training.camera_backward_and_step needs to back-propagate into the poses.
         level0 (FruitModel.level0_spec(): S, near, far, n_jitter): the whole start of the step in ONE launch
         (fnr_train_prologue: counter-based random numbers, camera adjust, pixel sampling and the proposal sampler's
@@ -218,10 +218,11 @@ class PixelBatcher:
             if self._set is None:
                 self._set = K.ImageSetArg(d["images"], d["masks"], d["c2w"], d["fx"], d["fy"], d["cx"], d["cy"])
             pose = camera_optimizer.pose_adjustment.data if (camera_optimizer is not None and camera_optimizer.enabled) else None
+            pose_mode = camera_optimizer.pose_mode if pose is not None else 0     # (without poses the mode reads nothing)
             self._offset = getattr(self, "_offset", 0) + 1
             out = K.train_prologue(self._set, self.image_ids, n_rays, self.gen.initial_seed(), self._offset, pose,
                                    level0["near"], level0["far"], level0["S"], n_jitter=level0.get("n_jitter", 3),
-                                   cams=self.camera_table())
+                                   cams=self.camera_table(), pose_mode=pose_mode)
             self.last_draw = {"u": out["u"], "cam": out["cam"], "c2w_adjusted": out["c2w_adjusted"]}
             self.last_presample = {"S0": out["S0"], "near": out["near"], "far": out["far"], "spacing": out["spacing"],
                                    "euclid": out["euclid"], "jitter": [out["jitter"][i] for i in range(out["jitter"].shape[0])]}

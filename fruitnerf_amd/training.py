@@ -1127,7 +1127,8 @@ def camera_backward(camera_optimizer, batcher, ray_grads: dict, world_size: int 
     d = batcher.last_draw
     pose = camera_optimizer.pose_adjustment
     K.camera_pose_grad(batcher._set, batcher.image_ids, d["u"], d["cam"], pose.data, d["c2w_adjusted"],
-                       ray_grads["origins"], ray_grads["directions"], pose.grad, cams=_camera_table(batcher))
+                       ray_grads["origins"], ray_grads["directions"], pose.grad, cams=_camera_table(batcher),
+                       pose_mode=camera_optimizer.pose_mode)
     if world_size >= EXCHANGE_MIN_WORLD:
         import torch.distributed as dist
         return _issued(dist.all_reduce(pose.grad, op=dist.ReduceOp.SUM, async_op=True), "all_reduce(poses)",
@@ -1144,7 +1145,7 @@ def camera_backward_and_step(camera_optimizer, camera_adam, batcher, ray_grads: 
         pose = camera_optimizer.pose_adjustment
         K.camera_pose_grad_adam(batcher._set, batcher.image_ids, d["u"], d["cam"], d["c2w_adjusted"],
                                 ray_grads["origins"], ray_grads["directions"], pose.grad, camera_adam.fused_step_args(),
-                                cams=_camera_table(batcher))
+                                cams=_camera_table(batcher), pose_mode=camera_optimizer.pose_mode)
         return
     work, scale = camera_backward(camera_optimizer, batcher, ray_grads, world_size)
     if work is not None:
@@ -1438,7 +1439,9 @@ class TrainingSteps:
         dev = model.device
         side = model.__dict__.get("_side_stream")
         cams = _camera_table(self.batcher)      # recorded by value: another table is another program
-        return (None if cams is None else cams.pointers(), self._arena_version, parity, start_offset, updated, updated_next, bool(want_metrics), self.camera is not None,
+        # (the pose mode too: a camera optimiser of the other mode on the same loop is another program)
+        return (None if cams is None else cams.pointers(), self._arena_version, parity, start_offset, updated, updated_next,
+                bool(want_metrics), None if self.camera is None else getattr(self.camera[0], "pose_mode", 0),
                 getattr(fld, "mlp_precision", None), model.arena().params.data_ptr(), id(self.optimizer),
                 L.stream_ptr(dev), None if side is None else side.cuda_stream,
                 OVERLAP_PROPOSAL_BACKWARD, SERIALIZE_STREAMS, LOSSES_ON_SIDE, PAIR_PROPOSAL_LEVELS, FUSE_CAMERA_OPTIMIZER,

@@ -242,6 +242,37 @@ int fnr_camera_pose_grad_cams(const fnr_image_set* set, const fnr_camera_table* 
                               const float* pose_adjustment, const float* c2w_adjusted, const float* d_origins,
                               const float* d_directions, float* pose_grad, void* stream);
 
+/* The camera optimiser's modes (nerfstudio CameraOptimizerConfig.mode).  The entry points above are FNR_POSE_SO3XR3; the
+ * _mode entry points below take `pose_mode` and, where rays are generated, a camera table that may be NULL (= the image
+ * set's pinhole, the entry point without _cams); with FNR_POSE_SO3XR3 they give the bits of the entry points above.  Any other pose_mode is an
+ * argument error before any launch.
+ * FNR_POSE_SE3 (nerfstudio 0.3.2 lie_groups.exp_map_SE3, restated): pose row (v, w), theta = |w| (no clamp), s = theta^2,
+ *   R = c I + b_r w w^T + a_r K(w),  t = a_t v + b_t (w x v) + c_t w (w . v),  K(w) = [[0,-wz,wy],[wz,0,-wx],[-wy,wx,0]]
+ *   theta >= 1e-2: c = cos theta, a_r = a_t = sin theta / theta, b_r = b_t = (1 - cos theta) / s, c_t = (theta - sin theta) / theta^3
+ *   theta <  1e-2: c = 8 / (4 + s) - 1, a_r = c / 2 + 1 / 2, b_r = a_r / 2;  a_t = 1 - s / 6, b_t = 1 / 2 - s / 24, c_t = 1 / 6 - s / 120
+ * composed as before: R' = R1 R, t' = t1 + R1 t.  An all-zero row leaves its camera bit for bit and has a finite gradient. */
+#define FNR_POSE_SO3XR3 0
+#define FNR_POSE_SE3 1
+/* fnr_camera_adjust in `pose_mode`.  Not recordable into step programs, like fnr_camera_adjust. */
+int fnr_camera_adjust_mode(const float* c2w, const int64_t* train_ids, int n_train, const float* pose_adjustment,
+                           int pose_mode, float* c2w_adjusted, void* stream);
+/* fnr_train_prologue (cams == NULL) / fnr_train_prologue_cams in `pose_mode`: given u and jitter, every output is
+ * bit-identical to fnr_camera_adjust_mode + fnr_sample_pixels[_cams] + fnr_sample_spaced.  Recorded into step programs like
+ * fnr_train_prologue (mode and table by value). */
+int fnr_train_prologue_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode, const int64_t* train_ids,
+                            int n_train, int64_t n_rays, uint64_t seed, uint64_t offset, const float* pose_adjustment,
+                            float* c2w_adjusted, float* u, float* jitter, int n_jitter, float* origins, float* directions,
+                            int32_t* camera_indices, float* image, float* fruit_mask, float near_plane, float far_plane,
+                            int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
+                            void* stream);
+/* fnr_camera_pose_grad (cams == NULL) / fnr_camera_pose_grad_cams in `pose_mode`: the backward of fnr_camera_adjust_mode +
+ * ray generation.  In FNR_POSE_SE3 the translation columns of pose_grad depend on the rotation ones and back.  Not
+ * recordable, like fnr_camera_pose_grad. */
+int fnr_camera_pose_grad_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode, const int64_t* train_ids,
+                              int n_train, int64_t n_rays, const float* u, const int32_t* camera_indices,
+                              const float* pose_adjustment, const float* c2w_adjusted, const float* d_origins,
+                              const float* d_directions, float* pose_grad, void* stream);
+
 /* ---- samplers ------------------------------------------------------------------------------- */
 /* SpacedSampler.generate_ray_samples (components/ray_samplers.py:54-104; nerfstudio
  * UniformLinDispPiecewiseSampler for the proposal level 0, fruit_nerf.py:151-158).
@@ -477,6 +508,13 @@ int fnr_camera_pose_grad_adam_cams(const fnr_image_set* set, const fnr_camera_ta
                                    int n_train, int64_t n_rays, const float* u, const int32_t* camera_indices,
                                    const float* c2w_adjusted, const float* d_origins, const float* d_directions,
                                    float* pose_grad, const fnr_table_adam* adam, void* stream);
+/* fnr_camera_pose_grad_adam (cams == NULL) / fnr_camera_pose_grad_adam_cams in `pose_mode` (FNR_POSE_SO3XR3 | FNR_POSE_SE3):
+ * bit-identical to fnr_camera_pose_grad_mode followed by the optimiser step; recorded into step programs like
+ * fnr_camera_pose_grad_adam (mode and table by value, the Adam slot patched). */
+int fnr_camera_pose_grad_adam_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
+                                   const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
+                                   const int32_t* camera_indices, const float* c2w_adjusted, const float* d_origins,
+                                   const float* d_directions, float* pose_grad, const fnr_table_adam* adam, void* stream);
 
 /* Backward of fnr_prop_density_fwd: d_density [R,S] -> += into grads (table, w0, b0, w1, b1).
  * d_position (optional) [N,4]: gradient w.r.t. each sample's unit-cube position (xyz, w = 0) for
