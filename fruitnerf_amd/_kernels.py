@@ -358,9 +358,10 @@ def composite_fwd(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: T
 
 
 def composite_fwd_bwd_targets(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor, image: Tensor,
-                              mask: Tensor, sem_weight: float):
+                              mask: Tensor, sem_weight: float, semgrad: bool = False):
     """composite_fwd (training) and composite_bwd_targets as one launch (fnr_composite_fwd_bwd_targets): the same outputs and
-    gradients, bit for bit.  -> (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit)."""
+    gradients, bit for bit.  -> (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit).
+    semgrad (pass_semantic_gradients): fnr_composite_fwd_bwd_targets_semgrad — d_density carries the semantic term too."""
     lib = L.load()
     dev = rays.device
     N = rays.n * S
@@ -373,11 +374,12 @@ def composite_fwd_bwd_targets(rays: RaysArg, S: int, euclid: Tensor, density: Te
     d_density = _empty(N, device=dev)
     d_rgb = _empty(N, 3, device=dev)
     d_logit = _empty(N, device=dev)
-    L.check(lib.fnr_composite_fwd_bwd_targets(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
-                                              L.ptr(_f32c(image)), L.ptr(_f32c(mask.reshape(-1))), float(sem_weight),
-                                              L.ptr(weights), L.ptr(out_rgb), L.ptr(acc), L.ptr(depth), L.ptr(sem), L.ptr(label),
-                                              L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
-            "composite_fwd_bwd_targets")
+    fn = lib.fnr_composite_fwd_bwd_targets_semgrad if semgrad else lib.fnr_composite_fwd_bwd_targets
+    L.check(fn(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
+               L.ptr(_f32c(image)), L.ptr(_f32c(mask.reshape(-1))), float(sem_weight),
+               L.ptr(weights), L.ptr(out_rgb), L.ptr(acc), L.ptr(depth), L.ptr(sem), L.ptr(label),
+               L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
+            "composite_fwd_bwd_targets_semgrad" if semgrad else "composite_fwd_bwd_targets")
     return (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit)
 
 
@@ -513,6 +515,41 @@ def composite_bwd_targets(rays: RaysArg, S: int, euclid: Tensor, density: Tensor
     return d_density, d_rgb, d_logit
 
 
+def composite_bwd_semgrad(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor,
+                          weights: Tensor, g_rgb: Tensor, g_sem: Tensor):
+    """composite_bwd under pass_semantic_gradients (fnr_composite_bwd_semgrad): the semantic renderer's weights are not
+    detached, d_density also carries g_sem * logit_k (logit [N]: the per-sample logits); d_rgb / d_logit as composite_bwd."""
+    lib = L.load()
+    dev = rays.device
+    N = rays.n * S
+    d_density = _empty(N, device=dev)
+    d_rgb = _empty(N, 3, device=dev)
+    d_logit = _empty(N, device=dev)
+    L.check(lib.fnr_composite_bwd_semgrad(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
+                                          L.ptr(weights), L.ptr(_f32c(g_rgb)), L.ptr(_f32c(g_sem.reshape(-1))),
+                                          L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
+            "composite_bwd_semgrad")
+    return d_density, d_rgb, d_logit
+
+
+def composite_bwd_targets_semgrad(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor,
+                                  weights: Tensor, out_rgb: Tensor, image: Tensor, out_sem: Tensor, mask: Tensor,
+                                  sem_weight: float):
+    """composite_bwd_targets under pass_semantic_gradients (fnr_composite_bwd_targets_semgrad)."""
+    lib = L.load()
+    dev = rays.device
+    N = rays.n * S
+    d_density = _empty(N, device=dev)
+    d_rgb = _empty(N, 3, device=dev)
+    d_logit = _empty(N, device=dev)
+    L.check(lib.fnr_composite_bwd_targets_semgrad(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
+                                                  L.ptr(weights), L.ptr(_f32c(out_rgb)), L.ptr(_f32c(image)),
+                                                  L.ptr(_f32c(out_sem.reshape(-1))), L.ptr(_f32c(mask.reshape(-1))),
+                                                  float(sem_weight), L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit),
+                                                  L.stream_ptr(dev)), "composite_bwd_targets_semgrad")
+    return d_density, d_rgb, d_logit
+
+
 def weights_bwd(S: int, euclid: Tensor, density: Tensor, weights: Tensor, d_weights: Tensor,
                 upstream: Optional[Tensor]) -> Tensor:
     lib = L.load()
@@ -526,13 +563,15 @@ def weights_bwd(S: int, euclid: Tensor, density: Tensor, weights: Tensor, d_weig
 
 def field_mlp_bwd(net: L.fnr_field_net, grads: L.fnr_field_net, rays: RaysArg, S: int, feats: Tensor, h_saved,
                   selector: Tensor, d_density: Tensor, d_rgb: Tensor, d_logit: Tensor, jacobian: Optional[Tensor] = None,
-                  weight_adam=None):
+                  weight_adam=None, semgrad: bool = False):
     """h_saved: what field_mlp_fwd(want_h=True) returned — (h [N,16], ray_bias [R,64], packed weights); a bare h tensor
     is accepted too (the per-ray bias and the fragment image are then recomputed).
     jacobian (hash_encode_fwd(want_jacobian=True)): -> (d_feats, d_position [N,4]): the hash grid's input gradient per
     sample rides along (fnr_field_mlp_bwd_rays); position_grad_reduce(..., d_position.view(1, N, 4), ...) finishes it.
     weight_adam = (fnr_table_adam, gradient arena): the optimiser step of the MLP weights + embedding is taken by the
-    kernels that finish their gradients (fnr_field_mlp_bwd_adam, FusedAdam.weight_adam_args)."""
+    kernels that finish their gradients (fnr_field_mlp_bwd_adam, FusedAdam.weight_adam_args).
+    semgrad (pass_semantic_gradients): the geometry feature that feeds mlp_semantics is not detached — any of the three
+    forms above through fnr_field_mlp_bwd_semgrad."""
     lib = L.load()
     fwd_mode = h_saved[3] if isinstance(h_saved, tuple) and len(h_saved) > 3 else None
     h_saved, ray_bias, packed = (tuple(h_saved) + (None, None))[:3] if isinstance(h_saved, tuple) else (h_saved, None, None)
@@ -543,6 +582,15 @@ def field_mlp_bwd(net: L.fnr_field_net, grads: L.fnr_field_net, rays: RaysArg, S
     d_feats = _empty(*feats.shape, device=dev)
     nbytes = lib.fnr_field_mlp_bwd_workspace_bytes(rays.n, S)
     ws = _empty(nbytes, dtype=torch.uint8, device=dev)
+    if semgrad:
+        adam, grad_arena = weight_adam if weight_adam is not None else (None, None)
+        d_pos = _empty(N, 4, device=dev) if jacobian is not None else None
+        L.check(lib.fnr_field_mlp_bwd_semgrad(C.byref(net), C.byref(grads), rays.ref, S, L.ptr(feats), L.ptr(h_saved),
+                                              L.ptr(ray_bias), L.ptr(packed), L.ptr(selector), L.ptr(d_density),
+                                              L.ptr(d_rgb), L.ptr(d_logit), L.ptr(d_feats), L.ptr(jacobian), L.ptr(d_pos),
+                                              None if adam is None else C.byref(adam), L.ptr(grad_arena), L.ptr(ws), nbytes,
+                                              L.stream_ptr(dev)), "field_mlp_bwd_semgrad")
+        return (d_feats, d_pos) if jacobian is not None else d_feats
     if weight_adam is not None:
         adam, grad_arena = weight_adam
         d_pos = _empty(N, 4, device=dev) if jacobian is not None else None

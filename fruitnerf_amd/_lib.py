@@ -155,6 +155,14 @@ SIGNATURES = {
     "fnr_composite_bwd_targets": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp,
                                        _vp]),
     "fnr_weights_bwd": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # pass_semantic_gradients: the compositing / MLP backward with the semantic term in d_density / dL/dh
+    "fnr_composite_bwd_semgrad": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fnr_composite_bwd_targets_semgrad": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp,
+                                               _vp, _vp, _vp]),
+    "fnr_composite_fwd_bwd_targets_semgrad": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fnr_field_mlp_bwd_semgrad": (_i, [P(fnr_field_net), P(fnr_field_net), P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, P(fnr_table_adam), _vp, _vp, C.c_size_t, _vp]),
     "fnr_field_mlp_bwd_workspace_bytes": (C.c_size_t, [_i64, _i]),
     "fnr_field_mlp_bwd": (_i, [P(fnr_field_net), P(fnr_field_net), P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -42,7 +42,9 @@ struct BfImage {
   static constexpr int nib_used(int l) { return l == Cfg::L_COL0 ? Cfg::HB : Cfg::nib(l); }
   static constexpr int nkb(int l) { return (nib_used(l) + 1) / 2; }
   static constexpr int nkbT(int l) { return (Cfg::nob(l) + 1) / 2; }
-  static constexpr bool hasT(int l) { return l != Cfg::L_SEM0; }  // mlp_semantics' input is detached: no dX
+  // mlp_semantics' input is detached: no dX — unless pass_semantic_gradients, whose kernels build the transposed fragments of
+  // sem0 themselves (bf_build_T) and leave this image as it is
+  static constexpr bool hasT(int l) { return l != Cfg::L_SEM0; }
   static constexpr int fblocks(int l) { return Cfg::nob(l) * nkb(l); }
   static constexpr int tblocks(int l) { return hasT(l) ? nib_used(l) * nkbT(l) : 0; }
   static constexpr int foff(int l) {
@@ -224,6 +226,33 @@ struct BfLds {
     }
   }
 };
+
+// The transposed segment of layer L ([piece][ib * nkbT + kb][64 lanes], what BfLds::seg<L, true> would point at) built in LDS
+// from the fp32 fragment image `packed` by a workgroup of THREADS threads: the same values and the same split as
+// pack_field_weights_bf16_block's transposed branch.  For the one layer whose transposed blocks the bf16 image does not carry
+// (L_SEM0), used by the pass_semantic_gradients kernels only.  The caller puts a barrier on both sides.
+template <class Cfg, int L, int NS, int THREADS>
+__device__ __forceinline__ void bf_build_T(bf16x8* __restrict__ lds, const float* __restrict__ packed) {
+  constexpr int NIB = Cfg::nib(L), NKT = (Cfg::nob(L) + 1) / 2, TB = NIB * NKT;
+  for (int idx = threadIdx.x; idx < TB * 64; idx += THREADS) {
+    const int blk = idx >> 6, lane = idx & 63;
+    const int i = lane & 15, g = lane >> 4;
+    const int kb = blk % NKT, ib = blk / NKT;
+    float w[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int ob = 2 * kb + (e >> 2), row = 4 * g + (e & 3);  // W[16 ob + row][col(ib, i >> 2, i & 3)] in the fp32 image
+      w[e] = ob < Cfg::nob(L) ? packed[Cfg::woff(L) + ((ob * NIB + ib) * 64 + swz_slot(row, i >> 2)) * 4 + (i & 3)] : 0.0f;
+    }
+#pragma unroll
+    for (int pc = 0; pc < NS; ++pc) {
+      bf16x8 v;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = bf_piece(w[e], pc);
+      lds[pc * TB * 64 + idx] = v;
+    }
+  }
+}
 
 // ---- operands ---------------------------------------------------------------------------------------------------
 // Two floats -> one dword of two bf16 (round to nearest even), ONE instruction: the TWO-wide vector conversion is what hipcc
@@ -410,7 +439,7 @@ int field_mlp_fwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, con
                                const float* h_buf, float* logit, hipStream_t st);
 int field_mlp_bwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
                                const float* h_saved, const float* d_logit, float* partials, long long blocks,
-                               hipStream_t st);
+                               hipStream_t st, float* d_h_semgrad = nullptr);  // pass_semantic_gradients: d_h [N,32] += dX of sem0
 namespace pw {
 // what the branches of one per-wave backward share (field_mlp_bwd_launch builds it once)
 struct BwdArgs {
@@ -431,7 +460,7 @@ struct BwdArgs {
 };
 }  // namespace pw
 // branch: 0 colour, 1 semantic (`fruit_nerf` only), 2 base — with jac and d_pos, the base branch also writes the position
-// gradient.  field_mlp_bwd_pw.hip
+// gradient; 3 (`fruit_nerf` only, pass_semantic_gradients): a.d_h += the input gradient of mlp_semantics.  field_mlp_bwd_pw.hip
 int field_mlp_bwd_pw(int cfg, int mode, int branch, const pw::BwdArgs& a, const float2* jac, float4* d_pos);
 
 }  // namespace fnr

@@ -186,6 +186,11 @@ __device__ __forceinline__ int kmap(int kind, int ib, int g, int r, int in_dim) 
 
 __device__ __forceinline__ int swz_slot(int i, int g) { return (i ^ g) + 16 * g; }
 
+// The one argument of a kernel's trailing parameter pack.  A compile-time variant that needs one more pointer (SEMGRAD: d_h)
+// takes it as a pack of one, so that the instantiation without the variant keeps its argument list exactly.
+template <class T>
+__device__ __forceinline__ T only(T v) { return v; }
+
 // nn.Linear column of mlp_head layer 0 for ray-constant input k: k < 16 -> SH component k, else embedding k - 16
 template <class Cfg>
 __device__ __forceinline__ int color_const_col(int k) { return k < 16 ? k : 16 + Cfg::GEO + (k - 16); }

@@ -280,11 +280,16 @@ __device__ __forceinline__ void store_bias_block(float* __restrict__ B, int ob, 
 // recomputed activations decide the ReLU gates, and a gate that flips against the forward pass
 // changes a whole sample's contribution to a dW row: with two pieces (2^-17) that happened ~1000x more often
 // than with three (2^-27) and single flips showed as ~5e-3 of max |g| under random zero-mean upstream gradients.
-template <class Cfg, int NSF, int NS>
+// SEMGRAD (pass_semantic_gradients, fruit_field.py:202-203, 263-264): geo is not detached — a fifth phase per batch forms
+// Gh = W_sem0^T Gs1 and adds it into the samples' rows of d_h [N,32] (behind the colour kernel that wrote them, ahead of the
+// base kernel that reads them, one writer per row).  sem0's transposed fragments are not in the bf16 image: built into the
+// shared region from the fp32 image (bf_build_T).  Slot 0, the density logit, receives nothing.
+template <class Cfg, int NSF, int NS, bool SEMGRAD = false, class... DH>
 __global__ __launch_bounds__(512, 2) void k_field_mlp_bwd_sem_big_bf16(
     const float* __restrict__ packed, const __bf16* __restrict__ image, const float* __restrict__ w_sem2,
     const float* __restrict__ b_sem2, long long N, const float* __restrict__ h_saved, const float* __restrict__ d_logit,
-    float* __restrict__ partials) {
+    float* __restrict__ partials, DH... d_h_semgrad) {  // SEMGRAD: float* d_h
+  static_assert(sizeof...(DH) == (SEMGRAD ? 1 : 0), "d_h comes with SEMGRAD");
   static_assert(Cfg::NSEM == 3 && Cfg::HB == 2 && Cfg::SEMB == 8, "fruit_nerf_big semantic shape");
   constexpr int WAVES = 8, THREADS = 64 * WAVES;
   constexpr int LS0 = Cfg::L_SEM0, LS1 = Cfg::L_SEM1, LS2 = Cfg::L_SEM2, LH = Cfg::L_HEAD;
@@ -383,7 +388,7 @@ __global__ __launch_bounds__(512, 2) void k_field_mlp_bwd_sem_big_bf16(
     for (int b = 0; b < 8; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r) Gs1[b][r] = (s1[b][r] > 0.0f) ? Gs1[b][r] : 0.0f;
-    // round 3: G = Gs1, X = h -> dW sem0, db sem0 (the input is the detached geo: no dX)
+    // round 3: G = Gs1, X = h -> dW sem0, db sem0 (the input is the detached geo: no dX unless SEMGRAD)
     __syncthreads();
     cs_write<NS, 8>(sG, 0, Gs1, lane, wave);
     {
@@ -395,6 +400,24 @@ __global__ __launch_bounds__(512, 2) void k_field_mlp_bwd_sem_big_bf16(
     __syncthreads();
     cs_dw<NS, 2>(sG, sX, wave >> 1, 4, wave & 1, acc0, lane);
     cs_bias<NS>(sG, wave, b0, lane);
+    if constexpr (SEMGRAD) {  // phase 5: Gs1 -> Gh, d_h += Gh
+      constexpr int T0_BYTES = NS * Cfg::nib(LS0) * ((Cfg::nob(LS0) + 1) / 2) * 1024;
+      static_assert(T0_BYTES <= REGION, "sem0's transposed fragments exceed the shared region");
+      __syncthreads();  // round 3's scratch reads
+      bf_build_T<Cfg, LS0, NS, THREADS>(wl, packed);
+      __syncthreads();
+      f32x4 Gh[2];
+      bf_layer_T1<NS, 2, 8>(wl, Gs1, Gh, lane);
+      if (g == 0) Gh[0][0] = 0.0f;  // the density logit is not an input of mlp_semantics
+      if (valid) {
+        float* const d_h = only(d_h_semgrad...);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          f32x4* row = reinterpret_cast<f32x4*>(d_h + (size_t)n * 32 + 16 * b + 4 * g);
+          *row = *row + Gh[b];
+        }
+      }
+    }
   }
 
   // ---- this workgroup's partial image: every block of the branch's layers is written by its owner -------------------
@@ -506,7 +529,7 @@ int field_mlp_fwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, con
 
 int field_mlp_bwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
                                const float* h_saved, const float* d_logit, float* partials, long long blocks,
-                               hipStream_t st) {
+                               hipStream_t st, float* d_h_semgrad) {
   using Cfg = FieldCfgBig;
   __bf16* image = reinterpret_cast<__bf16*>(image_ws);  // packed by field_mlp_bwd_launch (or the forward pass)
   auto launch = [&](int once, auto kern, int bytes) -> int {
@@ -516,6 +539,23 @@ int field_mlp_bwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, con
     FNR_LAUNCH_CHECK();
     return FNR_OK;
   };
+  if (d_h_semgrad) {  // pass_semantic_gradients: the same launches of the SEMGRAD instantiations
+    auto launch_sg = [&](int once, auto kern, int bytes) -> int {
+      if (once) return once;
+      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), bytes, st, packed, image, p.w[Cfg::L_SEM2],
+                         p.b[Cfg::L_SEM2], N, h_saved, d_logit, partials, d_h_semgrad);
+      FNR_LAUNCH_CHECK();
+      return FNR_OK;
+    };
+    if (mode == MLP_BF16) {
+      constexpr int bytes = cs_words<1>() * 4 + (256 + 144) * 4;
+      constexpr auto kern = k_field_mlp_bwd_sem_big_bf16<Cfg, 1, 1, true, float*>;
+      return launch_sg(ensure_dyn_lds<kern>(bytes), kern, bytes);
+    }
+    constexpr int bytes = cs_words<2>() * 4 + (256 + 144) * 4;
+    constexpr auto kern = k_field_mlp_bwd_sem_big_bf16<Cfg, 3, 2, true, float*>;
+    return launch_sg(ensure_dyn_lds<kern>(bytes), kern, bytes);
+  }
   if (mode == MLP_BF16) {
     constexpr int bytes = cs_words<1>() * 4 + (256 + 144) * 4;
     constexpr auto kern = k_field_mlp_bwd_sem_big_bf16<Cfg, 1, 1>;

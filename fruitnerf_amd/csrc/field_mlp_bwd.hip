@@ -2,7 +2,9 @@
 //
 // Autograd of fruit_field.py:187-281 for the training path (get_outputs): rgb loss flows through mlp_head into
 // the geo features, the appearance embedding and the base MLP; the semantic loss only reaches mlp_semantics
-// + SemanticFieldHead (geo is detached, fruit_field.py:263-265); dL/dsigma enters through trunc_exp.
+// + SemanticFieldHead (geo is detached, fruit_field.py:263-265) unless pass_semantic_gradients (fruit_field.py:202-203,
+// 263-264: then the semantic kernels' SEMGRAD form adds dX of mlp_semantics' first layer to dL/dh); dL/dsigma enters
+// through trunc_exp.
 //
 // Structure (per 16-sample tile, one wave; see field_layers.hpp for the forward layout):
 //   * forward activations are RECOMPUTED from the saved hash features (128 B/sample) instead of being
@@ -410,10 +412,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_base(
 }
 
 // ---- semantic branch, `fruit_nerf` shape: 15 -> 64 -> 64 -> head (fruit_field.py:144-156,263-268) ----------------------
-template <class Cfg, int WAVES>
+// SEMGRAD (pass_semantic_gradients): geo is not detached, so dX of sem0, Gh = W_sem0^T Gs1, is added into the samples' rows
+// of d_h — behind the colour kernel that wrote them, ahead of the base kernel that reads them, one writer per row.  The column
+// of the density logit h[0] is a structural zero of sem0 (KM_GEO) and is masked besides: slot 0 receives nothing.
+template <class Cfg, int WAVES, bool SEMGRAD = false, class... DH>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_sem(
     const float* __restrict__ packed, long long N, const float* __restrict__ h_saved,
-    const float* __restrict__ d_logit, float* __restrict__ partials) {
+    const float* __restrict__ d_logit, float* __restrict__ partials, DH... d_h_semgrad) {  // SEMGRAD: float* d_h
+  static_assert(sizeof...(DH) == (SEMGRAD ? 1 : 0), "d_h comes with SEMGRAD");
   static_assert(Cfg::NSEM == 2 && Cfg::HB == 1, "the single-launch semantic branch is the fruit_nerf shape");
   using R = typename BwdRange<Cfg, BR_SEM>::type;
   constexpr int LS0 = Cfg::L_SEM0, LS1 = Cfg::L_SEM1, LH = Cfg::L_HEAD;
@@ -457,7 +463,17 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_sem(
     f32x4 Gs1[4];
     mlp_layer_T<4, 4, 0, 4>(R::w(lds, LS1), Gs2, Gs1, lane);
     relu_mask_(Gs1, s1);
-    dw_accumulate<4, 1>(scr, Gs1, h, accA, bsA, lane);   // input = detached geo: no dX
+    dw_accumulate<4, 1>(scr, Gs1, h, accA, bsA, lane);   // input = detached geo: no dX unless SEMGRAD
+    if constexpr (SEMGRAD) {
+      f32x4 Gh[1];
+      mlp_layer_T<4, 1, 0, 1>(R::w(lds, LS0), Gs1, Gh, lane);
+      if (g == 0) Gh[0][0] = 0.0f;  // the density logit is not an input of mlp_semantics
+      if (valid) {
+        float* const d_h = only(d_h_semgrad...);
+        f32x4* row = reinterpret_cast<f32x4*>(d_h + (size_t)n * 16 + 4 * g);
+        *row = *row + Gh[0];
+      }
+    }
   }
 
   const int lane = lane0;
@@ -485,10 +501,13 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_sem(
 
 // ---- semantic branch, `fruit_nerf_big` shape: 30 -> 128 -> 128 -> 64 -> head, two launches (see the file header) ----
 // PHASE_A: dW/db of sem0, sem2 and the head;  PHASE_B: dW/db of sem1 (the 128 x 128 layer).
-template <class Cfg, bool PHASE_A, int WAVES>
+// SEMGRAD (see k_field_mlp_bwd_sem): PHASE_A, which holds Gs1, owns the dX of sem0.
+template <class Cfg, bool PHASE_A, int WAVES, bool SEMGRAD = false, class... DH>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_field_mlp_bwd_sem_big(
     const float* __restrict__ packed, long long N, const float* __restrict__ h_saved,
-    const float* __restrict__ d_logit, float* __restrict__ partials) {
+    const float* __restrict__ d_logit, float* __restrict__ partials, DH... d_h_semgrad) {  // SEMGRAD: float* d_h
+  static_assert(sizeof...(DH) == (SEMGRAD ? 1 : 0), "d_h comes with SEMGRAD");
+  static_assert(PHASE_A || !SEMGRAD, "the input gradient of mlp_semantics belongs to phase A");
   static_assert(Cfg::NSEM == 3 && Cfg::HB == 2 && Cfg::SEMB == 8, "fruit_nerf_big semantic shape");
   using R = typename BwdRange<Cfg, PHASE_A ? BR_SEM_A : BR_SEM_B>::type;
   constexpr int LS0 = Cfg::L_SEM0, LS1 = Cfg::L_SEM1, LS2 = Cfg::L_SEM2, LH = Cfg::L_HEAD;
@@ -550,8 +569,21 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_mlp_bwd_sem_big(
       f32x4 Gs1[8];
       mlp_layer_T<8, 8, 0, 8>(R::w(lds, LS1), Gs2, Gs1, lane);
       relu_mask_(Gs1, s1);
-      dw_accumulate_sub<4, 2, 8, 2, 0, 0, true>(scr, Gs1, h, acc0, bs_lo, lane);  // input = detached geo: no dX
+      dw_accumulate_sub<4, 2, 8, 2, 0, 0, true>(scr, Gs1, h, acc0, bs_lo, lane);  // input = detached geo: no dX unless SEMGRAD
       dw_accumulate_sub<4, 2, 8, 2, 4, 0, true>(scr, Gs1 + 4, h, acc0, bs_hi, lane);
+      if constexpr (SEMGRAD) {
+        f32x4 Gh[2];
+        mlp_layer_T<8, 2, 0, 2>(R::w(lds, LS0), Gs1, Gh, lane);
+        if (g == 0) Gh[0][0] = 0.0f;  // the density logit is not an input of mlp_semantics
+        if (valid) {
+          float* const d_h = only(d_h_semgrad...);
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            f32x4* row = reinterpret_cast<f32x4*>(d_h + (size_t)n * 32 + 16 * b + 4 * g);
+            *row = *row + Gh[b];
+          }
+        }
+      }
     } else {
       dw_accumulate_sub<4, 4, 8, 8, 0, 0, true>(scr, Gs2, s1, acc1, bs_lo, lane);
       dw_accumulate_sub<4, 4, 8, 8, 0, 4, false>(scr, Gs2, s1 + 4, acc1, bs_lo, lane);
@@ -866,7 +898,7 @@ int field_mlp_bwd_launch(const FieldPtrs& p, const FieldPtrs& gp, const fnr_fiel
                          const float* ray_bias_saved, const float* packed_saved, const uint8_t* selector,
                          const float* d_density, const float* d_rgb, const float* d_logit, float* d_feats,
                          const BwdWorkspace& ws, hipStream_t st, const float* jacobian = nullptr,
-                         float* d_position = nullptr, const WeightAdam* wadam = nullptr) {
+                         float* d_position = nullptr, const WeightAdam* wadam = nullptr, bool semgrad = false) {
   const float2* jac = reinterpret_cast<const float2*>(jacobian);
   float4* d_pos = reinterpret_cast<float4*>(d_position);
   const long long n_tiles = (N + 15) / 16;
@@ -925,22 +957,35 @@ int field_mlp_bwd_launch(const FieldPtrs& p, const FieldPtrs& gp, const fnr_fiel
     FNR_LAUNCH_CHECK();
     // (the appearance embedding's rows, which only need g_ray, are taken by the LAST launch: k_finish_weights)
   }
+  // semgrad (pass_semantic_gradients): the semantic kernel adds its input gradient into ws.d_h, between the colour kernel
+  // that wrote it and the base kernel that reads it
   if (bf_sem_big) {
-    int rc = field_mlp_bwd_sem_big_bf16(mode, p, bf16_image, packed, N, h_saved, d_logit, partials, blocks, st);
+    int rc = field_mlp_bwd_sem_big_bf16(mode, p, bf16_image, packed, N, h_saved, d_logit, partials, blocks, st,
+                                        semgrad ? ws.d_h : nullptr);
     if (rc) return rc;
     rc = field_mlp_bwd_pw(cfg_id, mode, 2, bf, jac, d_pos);
     if (rc) return rc;
   } else if (bf_all) {
-    int rc = field_mlp_bwd_pw(cfg_id, mode, 1, bf, nullptr, nullptr);
+    int rc = semgrad ? field_mlp_bwd_pw(cfg_id, mode, 3, bf, nullptr, nullptr) : FNR_OK;  // d_h += dX of mlp_semantics
+    if (rc) return rc;
+    rc = field_mlp_bwd_pw(cfg_id, mode, 1, bf, nullptr, nullptr);
     if (rc) return rc;
     rc = field_mlp_bwd_pw(cfg_id, mode, 2, bf, jac, d_pos);
     if (rc) return rc;
   } else if constexpr (Cfg::NSEM == 2) {
-    hipLaunchKernelGGL((k_field_mlp_bwd_sem<Cfg, 8>), grid, dim3(512), 0, st, packed, N, h_saved, d_logit, partials);
+    if (semgrad)
+      hipLaunchKernelGGL((k_field_mlp_bwd_sem<Cfg, 8, true, float*>), grid, dim3(512), 0, st, packed, N, h_saved, d_logit,
+                         partials, ws.d_h);
+    else
+      hipLaunchKernelGGL((k_field_mlp_bwd_sem<Cfg, 8>), grid, dim3(512), 0, st, packed, N, h_saved, d_logit, partials);
     FNR_LAUNCH_CHECK();
   } else {
-    hipLaunchKernelGGL((k_field_mlp_bwd_sem_big<Cfg, true, 4>), grid, dim3(256), 0, st, packed, N, h_saved, d_logit,
-                       partials);
+    if (semgrad)
+      hipLaunchKernelGGL((k_field_mlp_bwd_sem_big<Cfg, true, 4, true, float*>), grid, dim3(256), 0, st, packed, N, h_saved,
+                         d_logit, partials, ws.d_h);
+    else
+      hipLaunchKernelGGL((k_field_mlp_bwd_sem_big<Cfg, true, 4>), grid, dim3(256), 0, st, packed, N, h_saved, d_logit,
+                         partials);
     FNR_LAUNCH_CHECK();
     hipLaunchKernelGGL((k_field_mlp_bwd_sem_big<Cfg, false, 4>), grid, dim3(256), 0, st, packed, N, h_saved, d_logit,
                        partials);
@@ -976,7 +1021,7 @@ static int field_mlp_bwd_entry(const fnr_field_net* net, const fnr_field_net* gr
                                  const float* packed_saved, const uint8_t* selector, const float* d_density, const float* d_rgb, const float* d_logit, float* d_feats,
                                  void* workspace, size_t workspace_bytes, void* stream, const float* jacobian,
                                float* d_position, const fnr_table_adam* weight_adam = nullptr,
-                               const float* grad_arena = nullptr) {
+                               const float* grad_arena = nullptr, bool semgrad = false) {
   WeightAdam wa{};
   if (weight_adam) {
     FNR_CHECK_ARG(grad_arena, "field_mlp_bwd_adam: grad_arena missing");
@@ -1009,10 +1054,10 @@ static int field_mlp_bwd_entry(const fnr_field_net* net, const fnr_field_net* gr
   if (cfg == 0)
     return field_mlp_bwd_launch<FieldCfgBase>(p, gp, net, grads, rd, S, N, feats, h_saved, ray_bias_saved, packed_saved,
                                               selector, d_density, d_rgb, d_logit, d_feats, ws, as_stream(stream), jacobian, d_position,
-                                              weight_adam ? &wa : nullptr);
+                                              weight_adam ? &wa : nullptr, semgrad);
   return field_mlp_bwd_launch<FieldCfgBig>(p, gp, net, grads, rd, S, N, feats, h_saved, ray_bias_saved, packed_saved,
                                            selector, d_density, d_rgb, d_logit, d_feats, ws, as_stream(stream), jacobian, d_position,
-                                              weight_adam ? &wa : nullptr);
+                                              weight_adam ? &wa : nullptr, semgrad);
 }
 
 extern "C" int fnr_field_mlp_bwd(const fnr_field_net* net, const fnr_field_net* grads, const fnr_rays* rays, int S,
@@ -1058,4 +1103,34 @@ extern "C" int fnr_field_mlp_bwd_rays(const fnr_field_net* net, const fnr_field_
   FNR_CHECK_ARG(jacobian && d_position, "field_mlp_bwd_rays: jacobian / d_position missing");
   return field_mlp_bwd_entry(net, grads, rays, S, feats, h_saved, ray_bias_saved, packed_saved, selector, d_density, d_rgb,
                              d_logit, d_feats, workspace, workspace_bytes, stream, jacobian, d_position);
+}
+
+// fnr_field_mlp_bwd / _rays / _adam under pass_semantic_gradients = True (fruit_field.py:202-203, 263-264: the geometry
+// feature that feeds mlp_semantics is not detached): one entry point, jacobian / d_position both NULL or both set,
+// weight_adam / grad_arena both NULL or both set.  Recordable when the optimiser is fused, like fnr_field_mlp_bwd_adam.
+extern "C" int fnr_field_mlp_bwd_semgrad(const fnr_field_net* net, const fnr_field_net* grads, const fnr_rays* rays, int S,
+                                         const float* feats, const float* h_saved, const float* ray_bias_saved,
+                                         const float* packed_saved, const uint8_t* selector, const float* d_density,
+                                         const float* d_rgb, const float* d_logit, float* d_feats, const float* jacobian,
+                                         float* d_position, const fnr_table_adam* weight_adam, const float* grad_arena,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  if (seq::recording() && net && grads && rays && weight_adam) {
+    const fnr_field_net net_ = *net, grads_ = *grads;
+    const fnr_rays rays_ = *rays;
+    const fnr_table_adam adam_ = *weight_adam;
+    seq::push("fnr_field_mlp_bwd_semgrad", [=](const fnr_step_scalars* sc) {
+      const fnr_table_adam a = seq::patched(adam_, sc);
+      return fnr_field_mlp_bwd_semgrad(&net_, &grads_, &rays_, S, feats, h_saved, ray_bias_saved, packed_saved, selector,
+                                       d_density, d_rgb, d_logit, d_feats, jacobian, d_position, &a, grad_arena, workspace,
+                                       workspace_bytes, stream);
+    });
+  } else {
+    FNR_SEQ_UNRECORDABLE("fnr_field_mlp_bwd_semgrad (without weight_adam)");
+  }
+  FNR_CHECK_ARG((weight_adam == nullptr) == (grad_arena == nullptr),
+                "field_mlp_bwd_semgrad: weight_adam and grad_arena go together");
+  FNR_CHECK_ARG((jacobian == nullptr) == (d_position == nullptr), "field_mlp_bwd_semgrad: jacobian and d_position go together");
+  return field_mlp_bwd_entry(net, grads, rays, S, feats, h_saved, ray_bias_saved, packed_saved, selector, d_density, d_rgb,
+                             d_logit, d_feats, workspace, workspace_bytes, stream, jacobian, d_position, weight_adam,
+                             grad_arena, true);
 }

@@ -705,7 +705,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_sem_pw(
       bias_add(bA, Gs1);
       to_ops(g1, Gs1);
     }
-    // sem0: G = Gs1, X = h (input = detached geo: no dX)
+    // sem0: G = Gs1, X = h (input = detached geo: no dX unless pass_semantic_gradients: pw_dx::k_field_mlp_sem_dx_pw)
     {
       Acts<NT, 1> h;  // (re-read, L2-resident, instead of its pieces living through the whole recompute)
       Ops<NT, 1, NS> hx;
@@ -913,6 +913,140 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_base_pw
   reduce_and_store<NALL, WAVES, Table>(smem, part, all, wave, lane);
 }
 
+}  // namespace pw
+
+// ---- pass_semantic_gradients (fruit_field.py:202-203, 263-264): the input gradient of mlp_semantics ----------------------------
+// With the switch on, geo is not detached ahead of mlp_semantics: dX of its first layer, Gh = W_sem0^T Gs1, joins d_h between the
+// colour kernel that wrote d_h and the base kernel that reads it — each row has one writer, a read-modify-write behind the
+// colour kernel on the same stream, bit-reproducible.  A kernel of its own, in front of the unchanged semantic branch: that
+// kernel sits at 256 registers with 132 of them dW accumulators and every form of it that also carries this product spills
+// (49 - 104 registers) at its two tiles per wave, while at one tile its weight gradients are no longer the bits of the switch-off
+// kernel.  Here there are no accumulators, and the chain is short: mlp_semantics' last layer has no activation, so Gs1 needs
+// the forward pass of sem0 alone (its ReLU gates, three pieces like the semantic branch: the same signs) —
+//     s1 = relu(W0 h + b0);  Gs2 = W_head^T dlogit;  Gs1 = gate(W1^T Gs2, s1);  Gh = W0^T Gs1;  d_h += Gh.
+// The transposed fragments of sem0 are not in the bf16 image (BfImage::hasT): built once per workgroup from the fp32 image.
+// Slot 0 of h, the density logit, is a structural zero of sem0's input map (KM_GEO) and is masked besides: it receives nothing.
+namespace pw_dx {
+using namespace pw;
+
+template <class Cfg>
+struct SegsSem0F {
+  static constexpr int N = 1;
+  static constexpr int layer(int) { return Cfg::L_SEM0; }
+  static constexpr bool isT(int) { return false; }
+};
+template <class Cfg, int NSF, int NS>
+struct DxLds {
+  using F = BfLds<Cfg, SegsSem0F<Cfg>, NSF>;
+  using T = BfLds<Cfg, SegsSemT<Cfg>, NS>;
+  static constexpr int T0_BLOCKS = Cfg::nib(Cfg::L_SEM0) * ((Cfg::nob(Cfg::L_SEM0) + 1) / 2);
+  static constexpr int T0_OFF = F::BYTES + T::BYTES;
+  static constexpr int FB_OFF = T0_OFF + NS * T0_BLOCKS * 1024;
+  static constexpr int BYTES = FB_OFF + 64 * 4;
+};
+
+template <class Cfg, int NSF, int NS, int NT, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_sem_dx_pw(
+    const float* __restrict__ packed, const __bf16* __restrict__ image, int N, const float* __restrict__ h_saved,
+    const float* __restrict__ d_logit, float* __restrict__ d_h) {
+  static_assert(Cfg::NSEM == 2 && Cfg::HB == 1, "`fruit_nerf` shape");
+  constexpr int THREADS = 64 * WAVES;
+  constexpr int LS0 = Cfg::L_SEM0, LS1 = Cfg::L_SEM1, LH = Cfg::L_HEAD;
+  using L = DxLds<Cfg, NSF, NS>;
+  using F = typename L::F;
+  using T = typename L::T;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16x8* wf = reinterpret_cast<bf16x8*>(smem);
+  bf16x8* wt = reinterpret_cast<bf16x8*>(smem + F::BYTES);
+  bf16x8* wt0 = reinterpret_cast<bf16x8*>(smem + L::T0_OFF);
+  float* fbias = reinterpret_cast<float*>(smem + L::FB_OFF);  // sem0 [64]
+  F::template stage<THREADS>(wf, image);
+  T::template stage<THREADS>(wt, image);
+  bf_build_T<Cfg, LS0, NS, THREADS>(wt0, packed);
+  for (int i = threadIdx.x; i < 64; i += THREADS) fbias[i] = packed[Cfg::W_TOTAL + Cfg::boff(LS0) + i];
+  __syncthreads();
+  const int lane0 = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_groups = (N + 16 * NT - 1) / (16 * NT);
+  for (int gr = blockIdx.x * WAVES + wave; gr < n_groups; gr += gridDim.x * WAVES) {
+    asm volatile("" ::: "memory");
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    const int j = lane & 15, g = lane >> 4;
+    const Samples<NT> sm(gr, j, N);
+    Ops<NT, 4, NSF> x1;
+    {
+      Ops<NT, 1, NSF> hx;
+      Acts<NT, 1> h;
+      Acts<NT, 4> s1;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) h.v[t][0] = *reinterpret_cast<const f32x4*>(h_saved + (size_t)sm.n[t] * 16 + 4 * g);
+      to_ops(hx, h);
+      layer<NT, NSF, 4, 1>(F::template seg<LS0, false>(wf), fbias, hx, s1, lane);
+      relu(s1);
+      to_ops(x1, s1);
+    }
+    Ops<NT, 1, NS> gl;
+    {
+      Acts<NT, 1> Gl;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        Gl.v[t][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (g == 0 && sm.ok[t]) Gl.v[t][0][0] = d_logit[sm.n[t]];
+      }
+      to_ops(gl, Gl);
+    }
+    Ops<NT, 4, NS> g2;
+    {
+      Acts<NT, 4> Gs2;
+      layer<NT, NS, 4, 1>(T::template seg<LH, true>(wt), nullptr, gl, Gs2, lane);  // no activation on mlp_semantics' last layer
+      to_ops(g2, Gs2);
+    }
+    Ops<NT, 4, NS> g1;
+    {
+      Acts<NT, 4> Gs1;
+      layer<NT, NS, 4, 4>(T::template seg<LS1, true>(wt), nullptr, g2, Gs1, lane);
+      gate(Gs1, x1);
+      to_ops(g1, Gs1);
+    }
+    Acts<NT, 1> Gh;
+    layer<NT, NS, 1, 4>(wt0, nullptr, g1, Gh, lane);
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (sm.ok[t]) {
+        if (g == 0) Gh.v[t][0][0] = 0.0f;  // the density logit is not an input of mlp_semantics
+        f32x4* row = reinterpret_cast<f32x4*>(d_h + (size_t)sm.n[t] * 16 + 4 * g);
+        *row = *row + Gh.v[t][0];
+      }
+  }
+}
+
+#ifndef FNR_PW_NT_SEM_DX
+#define FNR_PW_NT_SEM_DX 2
+#endif
+#ifndef FNR_PW_WAVES
+#define FNR_PW_WAVES 8
+#endif
+template <class Cfg, int NSF, int NS>
+static int launch(const BwdArgs& a) {
+  if constexpr (Cfg::NSEM == 2) {
+    constexpr int WAVES = FNR_PW_WAVES, THREADS = 64 * WAVES, NT = FNR_PW_NT_SEM_DX;
+    FNR_CHECK_ARG(a.N < (1ll << 31) - 64, "field_mlp_bwd: %lld samples exceed the 32-bit sample index of the backward kernels", a.N);
+    using L = DxLds<Cfg, NSF, NS>;
+    static_assert(L::BYTES <= 160 * 1024, "semantic input gradient exceeds the LDS");
+    constexpr auto kern = k_field_mlp_sem_dx_pw<Cfg, NSF, NS, NT, WAVES>;
+    const int once = ensure_dyn_lds<kern>(L::BYTES);
+    if (once) return once;
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.blocks), dim3(THREADS), L::BYTES, a.st, a.packed, a.image, (int)a.N, a.h_saved,
+                       a.d_logit, a.d_h);
+    FNR_LAUNCH_CHECK();
+    return FNR_OK;
+  } else {
+    FNR_CHECK_ARG(false, "the fruit_nerf_big semantic branch forms its input gradient itself (field_mlp_bwd_sem_big_bf16)");
+  }
+}
+}  // namespace pw_dx
+
+namespace pw {
 // tiles per wave, by branch (the colour branch's 116 accumulator registers leave room for one tile's activations: two spill),
 // and waves per workgroup (8 = two waves per SIMD, 256 registers each)
 #ifndef FNR_PW_NT_COLOR
@@ -933,6 +1067,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_bwd_base_pw
 
 template <class Cfg, int NSF, int NS>
 static int launch(int branch, const BwdArgs& a, const float2* jac, float4* d_pos) {
+  if (branch == 3) return pw_dx::launch<Cfg, NSF, NS>(a);
   constexpr int WAVES = FNR_PW_WAVES, THREADS = 64 * WAVES;
   FNR_CHECK_ARG(a.N < (1ll << 31) - 64, "field_mlp_bwd: %lld samples exceed the 32-bit sample index of the backward kernels", a.N);
   const int n = (int)a.N;

@@ -3,7 +3,8 @@
 // In the reference the sample positions carry autograd history (fruit_field.py:171-182: Frustums.get_positions ->
 // SceneContraction -> (x+2)/4 -> * selector -> HashEncoding), so loss.backward() also produces the gradient of the
 // rays the camera-pose optimiser consumes (fruit_nerf_config.py:39-43).  The sampler's bins are detached
-// (PDFSampler), SHEncoding runs under no_grad and the semantic branch sees detached geo features, so the ONLY path
+// (PDFSampler), SHEncoding runs under no_grad and the semantic branch sees detached geo features unless
+// pass_semantic_gradients (then its gradient arrives here inside d_feats like the colour branch's), so the ONLY path
 // to the rays is  p = o + d (t0 + t1)/2  ->  x(p)  ->  trilinear offsets of every level.
 //   main field: the forward encode (k_hash_encode) already holds the 8 corner rows of every (sample, level), so in
 //     training it also stores the input Jacobian J = scaling * d(blend)/d(offset) (6 floats per sample and level);

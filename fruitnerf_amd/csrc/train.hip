@@ -435,17 +435,20 @@ struct LossTargets {
   const float* mask;       // [R]
   float sem_weight;
 };
-template <bool COMPOSITE, bool TARGETS = false>
-__global__ __launch_bounds__(256) void k_weights_bwd(long long R, int S, const float* __restrict__ euclid,
-                                                     const float* __restrict__ density,
-                                                     const float* __restrict__ weights,
-                                                     const float* __restrict__ d_w_in,    // !COMPOSITE: [R,S]
-                                                     const float* __restrict__ upstream,  // optional device scalar
-                                                     const float* __restrict__ rgb,       // COMPOSITE: samples [N,3]
-                                                     const float* __restrict__ g_rgb,     // COMPOSITE: [R,3]
-                                                     const float* __restrict__ g_sem,     // COMPOSITE: [R]
-                                                     float* __restrict__ d_density, float* __restrict__ d_rgb,
-                                                     float* __restrict__ d_logit, LossTargets tg = LossTargets{}) {
+// SEMGRAD (pass_semantic_gradients, fruit_nerf.py:344-345): the semantic renderer's weights are NOT detached, so the semantic
+// term joins the upstream gradient of the weights, gw[k] += g_sem logit_k, and the rest of the kernel carries it into d_density.
+template <bool COMPOSITE, bool TARGETS, bool SEMGRAD>
+__device__ __forceinline__ void weights_bwd_body(long long R, int S, const float* __restrict__ euclid,
+                                                 const float* __restrict__ density, const float* __restrict__ weights,
+                                                 const float* __restrict__ d_w_in,    // !COMPOSITE: [R,S]
+                                                 const float* __restrict__ upstream,  // optional device scalar
+                                                 const float* __restrict__ rgb,       // COMPOSITE: samples [N,3]
+                                                 const float* __restrict__ g_rgb,     // COMPOSITE: [R,3]
+                                                 const float* __restrict__ g_sem,     // COMPOSITE: [R]
+                                                 float* __restrict__ d_density, float* __restrict__ d_rgb,
+                                                 float* __restrict__ d_logit, const LossTargets& tg,
+                                                 const float* __restrict__ logit) {   // SEMGRAD: samples [N]
+  static_assert(COMPOSITE || !SEMGRAD, "the semantic term belongs to the compositing backward");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r = (long long)blockIdx.x * 4 + wave;
   if (r >= R) return;
@@ -488,7 +491,8 @@ __global__ __launch_bounds__(256) void k_weights_bwd(long long R, int S, const f
       wk[e] = w[k];
       if (COMPOSITE) {
         const float* c = rgb + (r * S + k) * 3;
-        gw[e] = gr * (c[0] - l0) + gg * (c[1] - l1) + gb * (c[2] - l2);  // semantic weights are detached
+        gw[e] = gr * (c[0] - l0) + gg * (c[1] - l1) + gb * (c[2] - l2);  // semantic weights are detached unless SEMGRAD
+        if constexpr (SEMGRAD) gw[e] += gs * logit[r * S + k];
       } else {
         gw[e] = d_w_in[r * S + k] * up;
       }
@@ -530,17 +534,46 @@ __global__ __launch_bounds__(256) void k_weights_bwd(long long R, int S, const f
   }
 }
 
+template <bool COMPOSITE, bool TARGETS = false>
+__global__ __launch_bounds__(256) void k_weights_bwd(long long R, int S, const float* __restrict__ euclid,
+                                                     const float* __restrict__ density,
+                                                     const float* __restrict__ weights,
+                                                     const float* __restrict__ d_w_in,    // !COMPOSITE: [R,S]
+                                                     const float* __restrict__ upstream,  // optional device scalar
+                                                     const float* __restrict__ rgb,       // COMPOSITE: samples [N,3]
+                                                     const float* __restrict__ g_rgb,     // COMPOSITE: [R,3]
+                                                     const float* __restrict__ g_sem,     // COMPOSITE: [R]
+                                                     float* __restrict__ d_density, float* __restrict__ d_rgb,
+                                                     float* __restrict__ d_logit, LossTargets tg = LossTargets{}) {
+  weights_bwd_body<COMPOSITE, TARGETS, false>(R, S, euclid, density, weights, d_w_in, upstream, rgb, g_rgb, g_sem, d_density,
+                                              d_rgb, d_logit, tg, nullptr);
+}
+// fnr_composite_bwd_semgrad / fnr_composite_bwd_targets_semgrad: k_weights_bwd<true, TARGETS> with the semantic term
+template <bool TARGETS>
+__global__ __launch_bounds__(256) void k_weights_bwd_semgrad(long long R, int S, const float* __restrict__ euclid,
+                                                             const float* __restrict__ density,
+                                                             const float* __restrict__ weights, const float* __restrict__ rgb,
+                                                             const float* __restrict__ logit,     // samples [N]
+                                                             const float* __restrict__ g_rgb,     // !TARGETS: [R,3]
+                                                             const float* __restrict__ g_sem,     // !TARGETS: [R]
+                                                             float* __restrict__ d_density, float* __restrict__ d_rgb,
+                                                             float* __restrict__ d_logit, LossTargets tg) {
+  weights_bwd_body<true, TARGETS, true>(R, S, euclid, density, weights, nullptr, nullptr, rgb, g_rgb, g_sem, d_density, d_rgb,
+                                        d_logit, tg, logit);
+}
+
 // k_composite_fwd (render.hip, training mode) followed by k_weights_bwd<true, true> for the same ray, in one wave: everything the
 // backward read back from memory (weights, composited colour and logit) stays in registers.
-__global__ __launch_bounds__(256) void k_composite_fwd_bwd(RaysDev rays, int S, const float* __restrict__ euclid,
-                                                           const float* __restrict__ density, const float* __restrict__ rgb,
-                                                           const float* __restrict__ logit, const float* __restrict__ image,
-                                                           const float* __restrict__ mask, float sem_weight,
-                                                           float* __restrict__ weights, float* __restrict__ out_rgb,
-                                                           float* __restrict__ out_acc, float* __restrict__ out_depth,
-                                                           float* __restrict__ out_sem, long long* __restrict__ out_label,
-                                                           float* __restrict__ d_density, float* __restrict__ d_rgb,
-                                                           float* __restrict__ d_logit) {
+template <bool SEMGRAD>  // see weights_bwd_body
+__device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, const float* __restrict__ euclid,
+                                                       const float* __restrict__ density, const float* __restrict__ rgb,
+                                                       const float* __restrict__ logit, const float* __restrict__ image,
+                                                       const float* __restrict__ mask, float sem_weight,
+                                                       float* __restrict__ weights, float* __restrict__ out_rgb,
+                                                       float* __restrict__ out_acc, float* __restrict__ out_depth,
+                                                       float* __restrict__ out_sem, long long* __restrict__ out_label,
+                                                       float* __restrict__ d_density, float* __restrict__ d_rgb,
+                                                       float* __restrict__ d_logit) {
   static_assert(WB_MAXE == 8, "the forward and the backward chunk a ray the same way");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long R = rays.n_rays;
@@ -628,7 +661,8 @@ __global__ __launch_bounds__(256) void k_composite_fwd_bwd(RaysDev rays, int S, 
       delta[e] = eb[k + 1] - eb[k];
       wk[e] = w[e];
       const float* c = cs + 3 * k;
-      gw[e] = gr * (c[0] - l0) + gg * (c[1] - l1) + gb * (c[2] - l2);  // semantic weights are detached
+      gw[e] = gr * (c[0] - l0) + gg * (c[1] - l1) + gb * (c[2] - l2);  // semantic weights are detached unless SEMGRAD
+      if constexpr (SEMGRAD) gw[e] += gs * lg[k];
       dd_local += delta[e] * dn[k];
       gww_local += gw[e] * wk[e];
       wsum_local += wk[e];
@@ -659,6 +693,22 @@ __global__ __launch_bounds__(256) void k_composite_fwd_bwd(RaysDev rays, int S, 
       d_logit[r * S + k] = gs * wk[e];
     }
   }
+}
+__global__ __launch_bounds__(256) void k_composite_fwd_bwd(RaysDev rays, int S, const float* __restrict__ euclid,
+    const float* __restrict__ density, const float* __restrict__ rgb, const float* __restrict__ logit,
+    const float* __restrict__ image, const float* __restrict__ mask, float sem_weight, float* __restrict__ weights,
+    float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth, float* __restrict__ out_sem,
+    long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit) {
+  composite_fwd_bwd_body<false>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
+                          out_sem, out_label, d_density, d_rgb, d_logit);
+}
+__global__ __launch_bounds__(256) void k_composite_fwd_bwd_semgrad(RaysDev rays, int S, const float* __restrict__ euclid,
+    const float* __restrict__ density, const float* __restrict__ rgb, const float* __restrict__ logit,
+    const float* __restrict__ image, const float* __restrict__ mask, float sem_weight, float* __restrict__ weights,
+    float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth, float* __restrict__ out_sem,
+    long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit) {
+  composite_fwd_bwd_body<true>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
+                         out_sem, out_label, d_density, d_rgb, d_logit);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1005,6 +1055,80 @@ extern "C" int fnr_composite_fwd_bwd_targets(const fnr_rays* rays, int S, const 
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_COMPOSITE_FWD, rays->n_rays * (long long)S);
   hipLaunchKernelGGL(k_composite_fwd_bwd, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
+                     make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
+                     out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
+                     d_logit);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+// ---- pass_semantic_gradients (fruit_nerf.py:56, 344-345): the three compositing backward calls with the semantic renderer's
+// weights NOT detached — d_density also carries g_sem * logit_k; d_rgb and d_logit are the parents' bit for bit.
+extern "C" int fnr_composite_bwd_semgrad(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                         const float* rgb, const float* logit, const float* weights, const float* g_rgb,
+                                         const float* g_semantics, float* d_density, float* d_rgb, float* d_logit,
+                                         void* stream) {
+  FNR_SEQ_UNRECORDABLE("fnr_composite_bwd_semgrad");
+  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && weights && g_rgb && g_semantics && d_density && d_rgb &&
+                    d_logit,
+                "composite_bwd_semgrad: null argument");
+  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_semgrad: S %d out of range", S);
+  if (rays->n_rays == 0) return FNR_OK;
+  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
+  hipLaunchKernelGGL((k_weights_bwd_semgrad<false>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
+                     as_stream(stream), (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, g_rgb,
+                     g_semantics, d_density, d_rgb, d_logit, LossTargets{});
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+extern "C" int fnr_composite_bwd_targets_semgrad(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                                 const float* rgb, const float* logit, const float* weights,
+                                                 const float* out_rgb, const float* image, const float* out_semantics,
+                                                 const float* mask, float semantic_loss_weight, float* d_density,
+                                                 float* d_rgb, float* d_logit, void* stream) {
+  if (seq::recording() && rays) {
+    const fnr_rays rays_ = *rays;
+    seq::push("fnr_composite_bwd_targets_semgrad", [=](const fnr_step_scalars*) {
+      return fnr_composite_bwd_targets_semgrad(&rays_, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
+                                               out_semantics, mask, semantic_loss_weight, d_density, d_rgb, d_logit, stream);
+    });
+  }
+  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && weights && out_rgb && image && out_semantics && mask &&
+                    d_density && d_rgb && d_logit,
+                "composite_bwd_targets_semgrad: null argument");
+  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_targets_semgrad: S %d out of range", S);
+  if (rays->n_rays == 0) return FNR_OK;
+  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
+  const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
+  hipLaunchKernelGGL((k_weights_bwd_semgrad<true>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
+                     (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, (const float*)nullptr,
+                     (const float*)nullptr, d_density, d_rgb, d_logit, tg);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+extern "C" int fnr_composite_fwd_bwd_targets_semgrad(const fnr_rays* rays, int S, const float* euclid_bins,
+                                                     const float* density, const float* rgb, const float* logit,
+                                                     const float* image, const float* mask, float semantic_loss_weight,
+                                                     float* weights, float* out_rgb, float* out_accumulation,
+                                                     float* out_depth, float* out_semantics, int64_t* out_label,
+                                                     float* d_density, float* d_rgb, float* d_logit, void* stream) {
+  if (seq::recording() && rays) {
+    const fnr_rays rays_ = *rays;
+    seq::push("fnr_composite_fwd_bwd_targets_semgrad", [=](const fnr_step_scalars*) {
+      return fnr_composite_fwd_bwd_targets_semgrad(&rays_, S, euclid_bins, density, rgb, logit, image, mask,
+                                                   semantic_loss_weight, weights, out_rgb, out_accumulation, out_depth,
+                                                   out_semantics, out_label, d_density, d_rgb, d_logit, stream);
+    });
+  }
+  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && image && mask && weights && out_rgb && out_accumulation &&
+                    out_depth && out_semantics && d_density && d_rgb && d_logit,
+                "composite_fwd_bwd_targets_semgrad: null argument");
+  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_fwd_bwd_targets_semgrad: S %d out of range", S);
+  if (rays->n_rays == 0) return FNR_OK;
+  FNR_PROF(OP_COMPOSITE_FWD, rays->n_rays * (long long)S);
+  hipLaunchKernelGGL(k_composite_fwd_bwd_semgrad, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
                      make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
                      out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
                      d_logit);

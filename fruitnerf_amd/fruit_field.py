@@ -87,9 +87,8 @@ class FruitField(nn.Module):
         self.test_mode = test_mode
         self.pass_semantic_gradients = pass_semantic_gradients
         self.base_res = base_res
-        if pass_semantic_gradients:
-            raise NotImplementedError("pass_semantic_gradients=True is not built (reference default is False, "
-                                      "fruit_nerf.py:56)")
+        # pass_semantic_gradients (fruit_nerf.py:56; fruit_field.py:202-203, 263-264): backward-only — the field's autograd
+        # node and the training steps take the `_semgrad` MLP backward, which does not detach geo ahead of mlp_semantics
         if not use_semantics:
             raise NotImplementedError("FruitModel always builds the field with use_semantics=True (fruit_nerf.py:98)")
         # fruit_field.py:124-166 — same module names => same state-dict keys

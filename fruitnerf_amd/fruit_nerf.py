@@ -263,6 +263,11 @@ class FruitModel(nn.Module):
             num_proposal_samples_per_ray=cfg.num_proposal_samples_per_ray,
             num_proposal_network_iterations=cfg.num_proposal_iterations,
             single_jitter=cfg.use_single_jitter, update_sched=update_schedule, initial_sampler=None)
+        if cfg.pass_semantic_gradients and self._device.type != "cuda":
+            # the switch only changes the backward pass, which exists on the HIP device alone (FruitField itself builds
+            # anywhere); a model that is constructed off the device keeps the refusal tests/test_host_logic.py pins
+            raise NotImplementedError("pass_semantic_gradients=True is built for the HIP device only: construct the model "
+                                      "with device='cuda' (fruit_nerf.py:56)")
         if cfg.background_color != "last_sample":
             raise NotImplementedError("only background_color='last_sample' (Nerfacto default) is built")
         if cfg.use_gradient_scaling:
@@ -435,7 +440,8 @@ class FruitModel(nn.Module):
         #  backward, their scatter — is the longer one, and it starts behind this launch)
         if loss_targets is not None and training and not updated:
             (weights, out_rgb, acc, depth, sem, label), composite_grads = K.composite_fwd_bwd_targets(
-                rays, S, euclid, density, rgb, logit, loss_targets[0], loss_targets[1], loss_targets[2])
+                rays, S, euclid, density, rgb, logit, loss_targets[0], loss_targets[1], loss_targets[2],
+                semgrad=bool(cfg.pass_semantic_gradients))   # fruit_nerf.py:344-345: semantic weights not detached
         else:
             weights, out_rgb, acc, depth, sem, label = K.composite_fwd(rays, S, euclid, density, rgb, logit, training)
         levels.append(dict(S=S, spacing=spacing, euclid=euclid, density=density.view(rays.n, S), weights=weights,

@@ -5,7 +5,8 @@ Mirrors what Nerfstudio's Trainer does around the reference model
 with the reference's semantics:
   * rgb loss reaches the field through rgb samples AND compositing weights (density);
   * the semantic loss only trains mlp_semantics + the head (detached geo features and detached weights,
-    fruit_field.py:263-265, fruit_nerf.py:343-345);
+    fruit_field.py:263-265, fruit_nerf.py:343-345) unless pass_semantic_gradients, which lets it reach the geometry
+    through both (the `_semgrad` compositing / MLP backward calls);
   * proposal networks are trained by the interlevel loss only, and only on "updated" steps
     (ProposalNetworkSampler, fruit_nerf.py:131-158);
   * data parallelism = DistributedDataParallel's gradient all-reduce(mean) (fruit_pipeline.py:116-118):
@@ -91,18 +92,24 @@ class _RenderFn(torch.autograd.Function):
             g_rgb = torch.zeros(rays.n, 3, device=dev)
         if g_sem is None:
             g_sem = torch.zeros(rays.n, 1, device=dev)
-        d_density, d_rgb, d_logit = K.composite_bwd(rays, S, lv["euclid"], rctx.sample_density, rctx.sample_rgb,
-                                                    rctx.weights, g_rgb.contiguous(), g_sem.contiguous())
+        semgrad = bool(model.config.pass_semantic_gradients)   # fruit_nerf.py:344-345: semantic weights not detached
+        if semgrad:
+            d_density, d_rgb, d_logit = K.composite_bwd_semgrad(rays, S, lv["euclid"], rctx.sample_density, rctx.sample_rgb,
+                                                                rctx.sample_logit, rctx.weights, g_rgb.contiguous(),
+                                                                g_sem.contiguous())
+        else:
+            d_density, d_rgb, d_logit = K.composite_bwd(rays, S, lv["euclid"], rctx.sample_density, rctx.sample_rgb,
+                                                        rctx.weights, g_rgb.contiguous(), g_sem.contiguous())
         fld = model.field
         net, gnet = fld.net_struct(), fld.net_struct(grads=True)
         want_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         d_pos = None
         if want_rays and rctx.field_jacobian is not None:
             d_feats, d_pos = K.field_mlp_bwd(net, gnet, rays, S, rctx.field_feats, rctx.field_h, rctx.field_selector,
-                                             d_density, d_rgb, d_logit, jacobian=rctx.field_jacobian)
+                                             d_density, d_rgb, d_logit, jacobian=rctx.field_jacobian, semgrad=semgrad)
         else:
             d_feats = K.field_mlp_bwd(net, gnet, rays, S, rctx.field_feats, rctx.field_h, rctx.field_selector, d_density,
-                                      d_rgb, d_logit)
+                                      d_rgb, d_logit, semgrad=semgrad)
         d_o = d_d = None
         if want_rays:
             d_o = torch.zeros(rays.n, 3, device=dev)
@@ -143,7 +150,7 @@ class _FieldFn(torch.autograd.Function):
         z = lambda g, *shape: (torch.zeros(*shape, device=dev) if g is None else g.reshape(*shape).float().contiguous())  # noqa: E731
         net, gnet = field.net_struct(), field.net_struct(grads=True)
         d_feats = K.field_mlp_bwd(net, gnet, rays, S, feats, saved, selector, z(g_density, N), z(g_rgb, N, 3),
-                                  z(g_logit, N))
+                                  z(g_logit, N), semgrad=bool(field.pass_semantic_gradients))  # fruit_field.py:263-264
         K.hash_encode_bwd(gnet.grid, field.warp_struct(), rays, ctx.euclid, S, d_feats)
         return None, None, None, None, None, None
 
@@ -899,6 +906,7 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
     launches it brackets with HIP events)."""
     from . import _lib as L
     cfg = model.config
+    semgrad = bool(cfg.pass_semantic_gradients)   # the `_semgrad` forms of the compositing / MLP backward, recordable like theirs
     dev = model.device
     with torch.no_grad():
         ray_bundle = model._collide(ray_bundle)
@@ -992,10 +1000,17 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
                     K.stream_wait_stream(main, side)
         if getattr(rctx, "composite_grads", None) is not None:
             d_density, d_rgb_s, d_logit = rctx.composite_grads
+        elif losses_on_side and semgrad:
+            d_density, d_rgb_s, d_logit = K.composite_bwd_targets_semgrad(
+                rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb, rctx.sample_logit, rctx.weights, outputs["rgb"],
+                image, outputs["semantics"], mask, cfg.semantic_loss_weight)
         elif losses_on_side:
             d_density, d_rgb_s, d_logit = K.composite_bwd_targets(rays, S, fin["euclid"], rctx.sample_density,
                                                                   rctx.sample_rgb, rctx.weights, outputs["rgb"], image,
                                                                   outputs["semantics"], mask, cfg.semantic_loss_weight)
+        elif semgrad:
+            d_density, d_rgb_s, d_logit = K.composite_bwd_semgrad(rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb,
+                                                                  rctx.sample_logit, rctx.weights, d_rgb, d_sem)
         else:
             d_density, d_rgb_s, d_logit = K.composite_bwd(rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb,
                                                           rctx.weights, d_rgb, d_sem)
@@ -1005,10 +1020,10 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
         if ray_grads is not None and rctx.field_jacobian is not None:
             d_feats, d_pos = K.field_mlp_bwd(net, gnet, rays, S, rctx.field_feats, rctx.field_h, rctx.field_selector,
                                              d_density, d_rgb_s, d_logit, jacobian=rctx.field_jacobian,
-                                             weight_adam=weight_adam)
+                                             weight_adam=weight_adam, semgrad=semgrad)
         else:
             d_feats = K.field_mlp_bwd(net, gnet, rays, S, rctx.field_feats, rctx.field_h, rctx.field_selector, d_density,
-                                      d_rgb_s, d_logit, weight_adam=weight_adam)
+                                      d_rgb_s, d_logit, weight_adam=weight_adam, semgrad=semgrad)
         field_source = None
         if ray_grads is not None:
             if d_pos is not None:
@@ -1446,7 +1461,8 @@ class TrainingSteps:
                 L.stream_ptr(dev), None if side is None else side.cuda_stream,
                 OVERLAP_PROPOSAL_BACKWARD, SERIALIZE_STREAMS, LOSSES_ON_SIDE, PAIR_PROPOSAL_LEVELS, FUSE_CAMERA_OPTIMIZER,
                 FUSE_WEIGHT_OPTIMIZER, FUSE_TABLE_OPTIMIZER, SPARSE_TOUCH_SKIPPING, STREAM_SAFE, FUSE_COMPOSITE_BACKWARD,
-                cfg.semantic_loss_weight, cfg.interlevel_loss_mult, cfg.near_plane, cfg.far_plane)
+                cfg.semantic_loss_weight, cfg.interlevel_loss_mult, cfg.near_plane, cfg.far_plane,
+                bool(cfg.pass_semantic_gradients))
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def step(self, want_metrics: bool = True):

@@ -402,6 +402,30 @@ int fnr_composite_fwd_bwd_targets(const fnr_rays* rays, int S, const float* eucl
                                   float* out_depth, float* out_semantics, int64_t* out_label, float* d_density,
                                   float* d_rgb, float* d_logit, void* stream);
 
+/* pass_semantic_gradients = True (FruitNeRF's own switch, fruit_nerf.py:56): SemanticRenderer's weights are NOT detached
+ * (fruit_nerf.py:302, 344-345), so the semantic loss reaches the density through the compositing weights:
+ * dL/dw_k = g_rgb . (c_k - c_last) + g_semantics * logit_k.  logit [N]: the per-sample logits of fnr_field_mlp_fwd.
+ * d_rgb and d_logit are those of the entry points without the suffix, bit for bit; with g_semantics = 0 so is d_density.
+ * Pure additions at ABI 13. */
+/* fnr_composite_bwd with the semantic term (fruit_nerf.py:344-345).  Not recordable, like fnr_composite_bwd. */
+int fnr_composite_bwd_semgrad(const fnr_rays* rays, int S, const float* euclid_bins, const float* density, const float* rgb,
+                              const float* logit, const float* weights, const float* g_rgb, const float* g_semantics,
+                              float* d_density, float* d_rgb, float* d_logit, void* stream);
+/* fnr_composite_bwd_targets with the semantic term (fruit_nerf.py:344-345, 365-391): bit-identical to fnr_train_losses +
+ * fnr_composite_bwd_semgrad. */
+int fnr_composite_bwd_targets_semgrad(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                      const float* rgb, const float* logit, const float* weights, const float* out_rgb,
+                                      const float* image, const float* out_semantics, const float* mask,
+                                      float semantic_loss_weight, float* d_density, float* d_rgb, float* d_logit,
+                                      void* stream);
+/* fnr_composite_fwd_bwd_targets with the semantic term (fruit_nerf.py:325-348 with :344-345 not detached): the arguments
+ * of fnr_composite_fwd_bwd_targets; bit-identical to fnr_composite_fwd + fnr_composite_bwd_targets_semgrad. */
+int fnr_composite_fwd_bwd_targets_semgrad(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                          const float* rgb, const float* logit, const float* image, const float* mask,
+                                          float semantic_loss_weight, float* weights, float* out_rgb,
+                                          float* out_accumulation, float* out_depth, float* out_semantics,
+                                          int64_t* out_label, float* d_density, float* d_rgb, float* d_logit, void* stream);
+
 /* Backward of RaySamples.get_weights for a proposal level: d_weights [R,S] (x *upstream if non-NULL, a
  * device scalar) -> d_density [R,S]. */
 int fnr_weights_bwd(int64_t n_rays, int S, const float* euclid_bins, const float* density, const float* weights,
@@ -446,6 +470,20 @@ int fnr_field_mlp_bwd_adam(const fnr_field_net* net, const fnr_field_net* grads,
                            const float* d_rgb, const float* d_logit, float* d_feats, const float* jacobian /* optional */,
                            float* d_position /* optional */, const struct fnr_table_adam* weight_adam,
                            const float* grad_arena, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The MLP backward under pass_semantic_gradients = True (fruit_nerf.py:56): the geometry feature that feeds mlp_semantics
+ * is NOT detached (fruit_field.py:202-203, 263-264), so the input gradient of mlp_semantics' first layer joins dL/dh
+ * between the colour and the base branch: d_feats, the weight gradients of mlp_base_mlp, d_position and everything behind
+ * them see the semantic loss; the gradients of mlp_semantics, the head, mlp_head and the embedding are those of
+ * fnr_field_mlp_bwd, bit for bit.  One entry point for the three forms of the parent: jacobian / d_position both NULL
+ * (fnr_field_mlp_bwd) or both set (fnr_field_mlp_bwd_rays); weight_adam / grad_arena both NULL or both set
+ * (fnr_field_mlp_bwd_adam, the Adam slot patched on replay in the same way).  Recordable when weight_adam is set. */
+int fnr_field_mlp_bwd_semgrad(const fnr_field_net* net, const fnr_field_net* grads, const fnr_rays* rays, int S,
+                              const float* feats, const float* h_saved, const float* ray_bias_saved /* optional */,
+                              const float* packed_saved /* optional */, const uint8_t* selector, const float* d_density,
+                              const float* d_rgb, const float* d_logit, float* d_feats, const float* jacobian /* optional */,
+                              float* d_position /* optional */, const struct fnr_table_adam* weight_adam /* optional */,
+                              const float* grad_arena /* optional */, void* workspace, size_t workspace_bytes, void* stream);
 
 
 /* Backward of fnr_hash_encode_fwd: adds (+=) the trilinear scatter of d_feats [L][N][2] into
@@ -678,6 +716,7 @@ int fnr_adam_step_spans_dev(float* params, float* grads, float* exp_avg, float* 
  * recorded ONCE per step shape and replayed by one call: between fnr_program_begin and fnr_program_end the recordable
  * entry points called on this thread — fnr_train_prologue, fnr_prop_density_fwd, fnr_weights_pdf, fnr_hash_encode_fwd,
  * fnr_field_mlp_fwd, fnr_composite_fwd, fnr_train_losses, fnr_composite_bwd_targets, fnr_field_mlp_bwd_adam,
+ * fnr_composite_bwd_targets_semgrad, fnr_composite_fwd_bwd_targets_semgrad, fnr_field_mlp_bwd_semgrad (with weight_adam),
  * fnr_hash_encode_bwd_adam, fnr_prop_density_bwd_pair(_split), fnr_position_grad_reduce_multi,
  * fnr_camera_pose_grad_adam and the stream operations below — run as usual AND append themselves (arguments by value,
  * host structs / host arrays copied) to the program; any other entry point that enqueues device work poisons the
