@@ -272,7 +272,8 @@ __global__ __launch_bounds__(SC_EMIT_THREADS) void k_scatter_emit(GridDev grid, 
   if (lane == 0 && tmax > 0.0f) atomicMax(&s_max, __float_as_uint(tmax));
   __syncthreads();
   if (threadIdx.x == 0 && s_max != 0u) atomicMax(&qmax[(size_t)lrel * SC_CNT_STRIDE], s_max);
-  // exclusive scan of the per-bin counts (bins <= 1024 = 4 per thread) + one global reservation per non-empty bin
+  // exclusive scan of the per-bin counts (bins <= SC_MAX_BINS = 256, SC_BINS_PER_THREAD = 1: thread t < bins owns bin t)
+  // + one global reservation per non-empty bin
   unsigned c4[SC_BINS_PER_THREAD], tsum = 0;
 #pragma unroll
   for (int t = 0; t < SC_BINS_PER_THREAD; ++t) {
@@ -368,10 +369,14 @@ __global__ __launch_bounds__(SC_EMIT_THREADS) void k_scatter_emit(GridDev grid, 
 
 // LDS fp32 atomics (ds_add_f32) retire ~1 lane every 3 clocks per CU on gfx950 (measured: 200 G/s chip-wide,
 // 17x slower than ds_add_u32), so the per-bin sums are accumulated as 64-bit BLOCK FIXED POINT with
-// ds_add_u64 (measured 10x faster for two adds per record).  The scale is chosen per bin from the largest
-// |value| queued for it (tracked by the emit kernel) and the record count so that the sum cannot overflow:
-// resolution = max|v| * 2^-41 or better, i.e. finer than fp32 rounding of any partial sum that contains the
-// largest term; exact and order-independent (bitwise deterministic) above that resolution.
+// ds_add_u64 (measured 10x faster for two adds per record).  The scale 2^S is chosen per bin from the largest
+// |value| emitted for the bin's whole LEVEL (one maximum per level, qmax[lrel], tracked by the emit kernel: per-bin
+// maxima cost it 64 global atomics per workgroup) and the bin's own record count so that the sum cannot overflow:
+// S = 62 - nb - e with n < 2^nb records in the bin and the level's max|v| < 2^e, so a record is rounded to
+// 2^-S = 2^(nb + e - 62) <= n * max|v| * 2^-60: for the main table's queues (n < 2^20) that is the level's max|v| *
+// 2^-41 or better, i.e. finer than fp32 rounding of any partial sum that contains the level's largest term — but
+// relative to the LEVEL's maximum, not the bin's or the row's: a row that holds only values below 2^-42 of the level's
+// largest may keep no bits.  Exact and order-independent (bitwise deterministic) above that resolution.
 __device__ __forceinline__ void acc_record(unsigned long long* __restrict__ s_acc, unsigned row, const float2& v,
                                            double scale) {
   const long long ix = __double2ll_rn((double)v.x * scale), iy = __double2ll_rn((double)v.y * scale);
