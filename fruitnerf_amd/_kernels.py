@@ -383,6 +383,83 @@ def composite_fwd_bwd_targets(rays: RaysArg, S: int, euclid: Tensor, density: Te
     return (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit)
 
 
+class CompositeOptions:
+    """fnr_composite_options for the `_opt` compositing calls.  background: None = the last sample's colour; a [3] tensor =
+    one triple for every ray ("white" / "black"); an [R,3] tensor = one per ray ("random").  The tensor is kept alive here."""
+
+    def __init__(self, background: Optional[Tensor] = None, gradient_scaling: bool = False, semgrad: bool = False):
+        self.background = None if background is None else _f32c(background)
+        if self.background is not None and (self.background.dim() not in (1, 2) or self.background.shape[-1] != 3):
+            raise ValueError("CompositeOptions: background is a [3] or an [R,3] tensor")
+        self.gradient_scaling, self.semgrad = bool(gradient_scaling), bool(semgrad)
+
+    @property
+    def plain(self) -> bool:
+        """Neither option set: what the entry points without `_opt` compute."""
+        return self.background is None and not self.gradient_scaling
+
+    def ref(self, n_rays: int):
+        bg = self.background
+        if bg is not None and bg.dim() == 2 and bg.shape[0] != n_rays:
+            raise ValueError(f"CompositeOptions: background of {bg.shape[0]} rows for {n_rays} rays")
+        o = L.fnr_composite_options(L.FNR_BACKGROUND_LAST_SAMPLE if bg is None else L.FNR_BACKGROUND_EXPLICIT,
+                                    3 if (bg is not None and bg.dim() == 2) else 0, L.ptr(bg),
+                                    1 if self.gradient_scaling else 0, 1 if self.semgrad else 0)
+        return C.byref(o)
+
+
+def random_background(seed: int, offset: int, n_rays: int, device, out: Optional[Tensor] = None) -> Tensor:
+    """background_color="random": [n_rays,3] of U[0,1) from the training prologue's generator (fnr_random_background: same
+    seed and offset as the step's rays, a word group of its own)."""
+    lib = L.load()
+    if out is None:
+        out = _empty(n_rays, 3, device=device)
+    L.check(lib.fnr_random_background(int(seed) & ((1 << 64) - 1), int(offset) & ((1 << 64) - 1), n_rays, L.ptr(out),
+                                      L.stream_ptr(out.device)), "random_background")
+    return out
+
+
+def composite_fwd_opt(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor, training: bool,
+                      opts: CompositeOptions):
+    """composite_fwd with an explicit background (fnr_composite_fwd_opt)."""
+    lib = L.load()
+    dev = rays.device
+    weights = _empty(rays.n, S, device=dev)
+    out_rgb = _empty(rays.n, 3, device=dev)
+    acc = _empty(rays.n, device=dev)
+    depth = _empty(rays.n, device=dev)
+    sem = _empty(rays.n, device=dev)
+    label = _empty(rays.n, dtype=torch.int64, device=dev)
+    L.check(lib.fnr_composite_fwd_opt(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
+                                      1 if training else 0, opts.ref(rays.n), L.ptr(weights), L.ptr(out_rgb), L.ptr(acc),
+                                      L.ptr(depth), L.ptr(sem), L.ptr(label), L.stream_ptr(dev)), "composite_fwd_opt")
+    return weights, out_rgb, acc, depth, sem, label
+
+
+def composite_fwd_bwd_targets_opt(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor,
+                                  image: Tensor, mask: Tensor, sem_weight: float, opts: CompositeOptions):
+    """composite_fwd_bwd_targets under the options (fnr_composite_fwd_bwd_targets_opt): bit-identical to composite_fwd_opt +
+    composite_bwd_targets_opt.  -> (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit)."""
+    lib = L.load()
+    dev = rays.device
+    N = rays.n * S
+    weights = _empty(rays.n, S, device=dev)
+    out_rgb = _empty(rays.n, 3, device=dev)
+    acc = _empty(rays.n, device=dev)
+    depth = _empty(rays.n, device=dev)
+    sem = _empty(rays.n, device=dev)
+    label = _empty(rays.n, dtype=torch.int64, device=dev)
+    d_density = _empty(N, device=dev)
+    d_rgb = _empty(N, 3, device=dev)
+    d_logit = _empty(N, device=dev)
+    L.check(lib.fnr_composite_fwd_bwd_targets_opt(
+        rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit), L.ptr(_f32c(image)),
+        L.ptr(_f32c(mask.reshape(-1))), float(sem_weight), opts.ref(rays.n), L.ptr(weights), L.ptr(out_rgb), L.ptr(acc),
+        L.ptr(depth), L.ptr(sem), L.ptr(label), L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
+        "composite_fwd_bwd_targets_opt")
+    return (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit)
+
+
 # ---- export -------------------------------------------------------------------------------------------
 
 
@@ -547,6 +624,41 @@ def composite_bwd_targets_semgrad(rays: RaysArg, S: int, euclid: Tensor, density
                                                   L.ptr(_f32c(out_sem.reshape(-1))), L.ptr(_f32c(mask.reshape(-1))),
                                                   float(sem_weight), L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit),
                                                   L.stream_ptr(dev)), "composite_bwd_targets_semgrad")
+    return d_density, d_rgb, d_logit
+
+
+def composite_bwd_opt(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor, weights: Tensor,
+                      g_rgb: Tensor, g_sem: Tensor, opts: "CompositeOptions"):
+    """composite_bwd / composite_bwd_semgrad under the options (fnr_composite_bwd_opt): explicit background, gradients
+    scaled by the clamped squared distance of their sample."""
+    lib = L.load()
+    dev = rays.device
+    N = rays.n * S
+    d_density = _empty(N, device=dev)
+    d_rgb = _empty(N, 3, device=dev)
+    d_logit = _empty(N, device=dev)
+    L.check(lib.fnr_composite_bwd_opt(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit), L.ptr(weights),
+                                      L.ptr(_f32c(g_rgb)), L.ptr(_f32c(g_sem.reshape(-1))), opts.ref(rays.n),
+                                      L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
+            "composite_bwd_opt")
+    return d_density, d_rgb, d_logit
+
+
+def composite_bwd_targets_opt(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor,
+                              weights: Tensor, out_rgb: Tensor, image: Tensor, out_sem: Tensor, mask: Tensor,
+                              sem_weight: float, opts: "CompositeOptions"):
+    """composite_bwd_targets(_semgrad) under the options (fnr_composite_bwd_targets_opt)."""
+    lib = L.load()
+    dev = rays.device
+    N = rays.n * S
+    d_density = _empty(N, device=dev)
+    d_rgb = _empty(N, 3, device=dev)
+    d_logit = _empty(N, device=dev)
+    L.check(lib.fnr_composite_bwd_targets_opt(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
+                                              L.ptr(weights), L.ptr(_f32c(out_rgb)), L.ptr(_f32c(image)),
+                                              L.ptr(_f32c(out_sem.reshape(-1))), L.ptr(_f32c(mask.reshape(-1))),
+                                              float(sem_weight), opts.ref(rays.n), L.ptr(d_density), L.ptr(d_rgb),
+                                              L.ptr(d_logit), L.stream_ptr(dev)), "composite_bwd_targets_opt")
     return d_density, d_rgb, d_logit
 
 

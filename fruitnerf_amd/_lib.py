@@ -95,6 +95,15 @@ FNR_TRAIN_PROLOGUE_MAX_JITTER = 5    # fnr_train_prologue: n_jitter in 1..5
 FNR_TRAIN_LOSSES_ACCUM_FLOATS = 4 * FNR_LOSS_SLOTS + 33 * 32
 
 
+FNR_BACKGROUND_LAST_SAMPLE, FNR_BACKGROUND_EXPLICIT = 0, 1
+
+
+class fnr_composite_options(C.Structure):
+    # background_stride: floats between the rows of background_rgb (3: one triple per ray, 0: one triple for every ray)
+    _fields_ = [("background", C.c_int32), ("background_stride", C.c_int32), ("background_rgb", C.c_void_p),
+                ("gradient_scaling", C.c_int32), ("semantic_gradients", C.c_int32)]
+
+
 class fnr_lattice(C.Structure):
     _fields_ = [("n_x", C.c_int32), ("n_y", C.c_int32), ("n_z", C.c_int32),
                 ("xs", C.c_void_p), ("ys", C.c_void_p), ("zs", C.c_void_p)]
@@ -163,6 +172,16 @@ SIGNATURES = {
                                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "fnr_field_mlp_bwd_semgrad": (_i, [P(fnr_field_net), P(fnr_field_net), P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, P(fnr_table_adam), _vp, _vp, C.c_size_t, _vp]),
+    # background_color / use_gradient_scaling: the compositing calls with their options in fnr_composite_options
+    "fnr_composite_fwd_opt": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _i, P(fnr_composite_options), _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
+    "fnr_composite_bwd_opt": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, P(fnr_composite_options), _vp, _vp,
+                                   _vp, _vp]),
+    "fnr_composite_bwd_targets_opt": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float,
+                                           P(fnr_composite_options), _vp, _vp, _vp, _vp]),
+    "fnr_composite_fwd_bwd_targets_opt": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float,
+                                               P(fnr_composite_options), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fnr_random_background": (_i, [C.c_uint64, C.c_uint64, _i64, _vp, _vp]),
     "fnr_field_mlp_bwd_workspace_bytes": (C.c_size_t, [_i64, _i]),
     "fnr_field_mlp_bwd": (_i, [P(fnr_field_net), P(fnr_field_net), P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -46,6 +46,13 @@ void set_error(const char* fmt, ...);
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// fnr_composite_options as the compositing entry points take them: a known background, an explicit one with its buffer
+static inline bool composite_options_ok(const fnr_composite_options* o) {
+  return o && (o->background == FNR_BACKGROUND_LAST_SAMPLE ||
+               (o->background == FNR_BACKGROUND_EXPLICIT && o->background_rgb &&
+                (o->background_stride == 0 || o->background_stride == 3)));
+}
+
 // number of CUs of the current device (cached)
 int device_cu_count();
 

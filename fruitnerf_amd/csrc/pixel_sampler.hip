@@ -91,6 +91,19 @@ __device__ __forceinline__ void prologue_randoms(unsigned long long seed, unsign
   for (int i = 0; i < 4; ++i) out[i] = u01(c[i]);
 }
 
+// background_color = "random" (fnr_random_background): the ray's background triple = words 0-2 of word group 2 of the step's
+// numbers — the prologue keeps groups 0 and 1, so drawing a background changes none of its numbers.
+constexpr int RANDOM_BACKGROUND_GROUP = 2;
+__global__ __launch_bounds__(256) void k_random_background(unsigned long long seed, unsigned long long offset, long long n_rays,
+                                                           float* __restrict__ out) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rays) return;
+  float w[4];
+  prologue_randoms(seed, offset, r, RANDOM_BACKGROUND_GROUP, w);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[3 * r + c] = w[c];
+}
+
 struct PrologueArgs {
   ImageSetDev set;
   const long long* train_ids;
@@ -348,4 +361,18 @@ extern "C" int fnr_train_prologue_mode(const fnr_image_set* set, const fnr_camer
   return train_prologue("fnr_train_prologue_mode", set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, seed,
                         offset, pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices,
                         image, fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+}
+
+extern "C" int fnr_random_background(uint64_t seed, uint64_t offset, int64_t n_rays, float* out, void* stream) {
+  if (seq::recording()) {
+    seq::push("fnr_random_background", [=](const fnr_step_scalars* sc) {
+      return fnr_random_background(seed, sc ? sc->prologue_offset : offset, n_rays, out, stream);
+    });
+  }
+  FNR_CHECK_ARG(out && n_rays >= 0, "random_background: null argument or negative ray count");
+  if (n_rays == 0) return FNR_OK;
+  hipLaunchKernelGGL(k_random_background, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream),
+                     (unsigned long long)seed, (unsigned long long)offset, (long long)n_rays, out);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
 }

@@ -437,7 +437,16 @@ struct LossTargets {
 };
 // SEMGRAD (pass_semantic_gradients, fruit_nerf.py:344-345): the semantic renderer's weights are NOT detached, so the semantic
 // term joins the upstream gradient of the weights, gw[k] += g_sem logit_k, and the rest of the kernel carries it into d_density.
-template <bool COMPOSITE, bool TARGETS, bool SEMGRAD>
+// BG (background_color "white" / "black" / "random"): the background is an explicit triple, row r * bg_stride of `bg`, a
+// constant of the pass — it takes the last sample's place in dL/dw_k = g_rgb . (c_k - b) and sample S-1 gets no background share.
+// SCALE (use_gradient_scaling, nerfstudio scale_gradients_by_distance_squared): every gradient that leaves towards the field —
+// d_density, d_rgb, d_logit of sample k — is multiplied by s_k = clamp(m_k^2, 0, 1), m_k the bin's Euclidean midpoint.
+// <.., false, false> is the code it was: the two switches only add to it.
+__device__ __forceinline__ float distance_squared_scale(float e0, float e1) {
+  const float m = fdiv(fadd(e0, e1), 2.0f);
+  return fminf(fmaxf(fmul(m, m), 0.0f), 1.0f);
+}
+template <bool COMPOSITE, bool TARGETS, bool SEMGRAD, bool BG = false, bool SCALE = false>
 __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float* __restrict__ euclid,
                                                  const float* __restrict__ density, const float* __restrict__ weights,
                                                  const float* __restrict__ d_w_in,    // !COMPOSITE: [R,S]
@@ -447,8 +456,11 @@ __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float
                                                  const float* __restrict__ g_sem,     // COMPOSITE: [R]
                                                  float* __restrict__ d_density, float* __restrict__ d_rgb,
                                                  float* __restrict__ d_logit, const LossTargets& tg,
-                                                 const float* __restrict__ logit) {   // SEMGRAD: samples [N]
+                                                 const float* __restrict__ logit,     // SEMGRAD: samples [N]
+                                                 const float* __restrict__ bg = nullptr,   // BG: rows of 3, stride bg_stride
+                                                 int bg_stride = 0) {
   static_assert(COMPOSITE || !SEMGRAD, "the semantic term belongs to the compositing backward");
+  static_assert(COMPOSITE || !(BG || SCALE), "background and gradient scaling belong to the compositing backward");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r = (long long)blockIdx.x * 4 + wave;
   if (r >= R) return;
@@ -473,7 +485,7 @@ __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float
       gb = g_rgb[3 * r + 2];
       gs = g_sem[r];
     }
-    const float* cl = rgb + (r * S + (S - 1)) * 3;
+    const float* cl = BG ? bg + r * bg_stride : rgb + (r * S + (S - 1)) * 3;
     l0 = cl[0];
     l1 = cl[1];
     l2 = cl[2];
@@ -507,7 +519,7 @@ __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float
   // trunc_exp backward — the cancellation error was comparable to the real gradient (autograd's cumsum backward is a
   // reverse cumsum, i.e. exact in this sense).
   float suffix = wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane);
-  if (COMPOSITE) bgw = 1.0f - wave_sum(wsum_local);
+  if (COMPOSITE && !BG) bgw = 1.0f - wave_sum(wsum_local);
   float suf[WB_MAXE];   // suffix AFTER element e of this lane's chunk
 #pragma unroll
   for (int e = WB_MAXE - 1; e >= 0; --e) {
@@ -520,15 +532,18 @@ __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float
     if (e < E && k < S) {
       cum_dd += delta[e] * dn[k];   // inclusive of k
       const float T_next = expf(-cum_dd);
-      d_density[r * S + k] = delta[e] * (gw[e] * T_next - suf[e]);
+      float s = 1.0f;
+      if constexpr (SCALE) s = distance_squared_scale(eb[k], eb[k + 1]);
+      const auto leaving = [s](float g) { return SCALE ? s * g : g; };   // a gradient on its way to the field
+      d_density[r * S + k] = leaving(delta[e] * (gw[e] * T_next - suf[e]));
       if (COMPOSITE) {
         float f = wk[e];
-        if (k == S - 1) f += bgw;  // background = last sample's colour (RGBRenderer "last_sample")
+        if (!BG && k == S - 1) f += bgw;  // background = last sample's colour (RGBRenderer "last_sample")
         float* o = d_rgb + (r * S + k) * 3;
-        o[0] = gr * f;
-        o[1] = gg * f;
-        o[2] = gb * f;
-        d_logit[r * S + k] = gs * wk[e];
+        o[0] = leaving(gr * f);
+        o[1] = leaving(gg * f);
+        o[2] = leaving(gb * f);
+        d_logit[r * S + k] = leaving(gs * wk[e]);
       }
     }
   }
@@ -561,10 +576,25 @@ __global__ __launch_bounds__(256) void k_weights_bwd_semgrad(long long R, int S,
   weights_bwd_body<true, TARGETS, true>(R, S, euclid, density, weights, nullptr, nullptr, rgb, g_rgb, g_sem, d_density, d_rgb,
                                         d_logit, tg, logit);
 }
+// fnr_composite_bwd_opt / fnr_composite_bwd_targets_opt with an explicit background and / or gradient scaling
+template <bool TARGETS, bool SEMGRAD, bool BG, bool SCALE>
+__global__ __launch_bounds__(256) void k_composite_bwd_opt(long long R, int S, const float* __restrict__ euclid,
+                                                           const float* __restrict__ density,
+                                                           const float* __restrict__ weights, const float* __restrict__ rgb,
+                                                           const float* __restrict__ logit,     // SEMGRAD: samples [N]
+                                                           const float* __restrict__ g_rgb,     // !TARGETS: [R,3]
+                                                           const float* __restrict__ g_sem,     // !TARGETS: [R]
+                                                           float* __restrict__ d_density, float* __restrict__ d_rgb,
+                                                           float* __restrict__ d_logit, LossTargets tg,
+                                                           const float* __restrict__ bg, int bg_stride) {
+  static_assert(BG || SCALE, "<last sample, no scaling> is k_weights_bwd / k_weights_bwd_semgrad");
+  weights_bwd_body<true, TARGETS, SEMGRAD, BG, SCALE>(R, S, euclid, density, weights, nullptr, nullptr, rgb, g_rgb, g_sem,
+                                                      d_density, d_rgb, d_logit, tg, logit, bg, bg_stride);
+}
 
 // k_composite_fwd (render.hip, training mode) followed by k_weights_bwd<true, true> for the same ray, in one wave: everything the
 // backward read back from memory (weights, composited colour and logit) stays in registers.
-template <bool SEMGRAD>  // see weights_bwd_body
+template <bool SEMGRAD, bool BG = false, bool SCALE = false>  // see weights_bwd_body
 __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, const float* __restrict__ euclid,
                                                        const float* __restrict__ density, const float* __restrict__ rgb,
                                                        const float* __restrict__ logit, const float* __restrict__ image,
@@ -573,7 +603,8 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
                                                        float* __restrict__ out_acc, float* __restrict__ out_depth,
                                                        float* __restrict__ out_sem, long long* __restrict__ out_label,
                                                        float* __restrict__ d_density, float* __restrict__ d_rgb,
-                                                       float* __restrict__ d_logit) {
+                                                       float* __restrict__ d_logit, const float* __restrict__ bg = nullptr,
+                                                       int bg_stride = 0) {
   static_assert(WB_MAXE == 8, "the forward and the backward chunk a ray the same way");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long R = rays.n_rays;
@@ -633,7 +664,8 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
   cb = wave_sum(cb);
   sm = wave_sum(sm);
   // (every lane: the backward wants the composited colour; wave_sum leaves the same total in all of them)
-  const float l0 = cs[3 * (S - 1)], l1 = cs[3 * (S - 1) + 1], l2 = cs[3 * (S - 1) + 2];
+  const float* cl = BG ? bg + r * bg_stride : cs + 3 * (S - 1);
+  const float l0 = cl[0], l1 = cl[1], l2 = cl[2];
   const float o0 = cr + l0 * (1.0f - acc), o1 = cg + l1 * (1.0f - acc), o2 = cb + l2 * (1.0f - acc);
   if (lane == 0) {
     out_rgb[3 * r] = o0;
@@ -683,14 +715,17 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
     if (e < E && k < S) {
       cum_dd += delta[e] * dn[k];
       const float T_next = expf(-cum_dd);
-      d_density[r * S + k] = delta[e] * (gw[e] * T_next - suf[e]);
+      float s = 1.0f;
+      if constexpr (SCALE) s = distance_squared_scale(eb[k], eb[k + 1]);
+      const auto leaving = [s](float g) { return SCALE ? s * g : g; };
+      d_density[r * S + k] = leaving(delta[e] * (gw[e] * T_next - suf[e]));
       float f = wk[e];
-      if (k == S - 1) f += bgw;
+      if (!BG && k == S - 1) f += bgw;
       float* o = d_rgb + (r * S + k) * 3;
-      o[0] = gr * f;
-      o[1] = gg * f;
-      o[2] = gb * f;
-      d_logit[r * S + k] = gs * wk[e];
+      o[0] = leaving(gr * f);
+      o[1] = leaving(gg * f);
+      o[2] = leaving(gb * f);
+      d_logit[r * S + k] = leaving(gs * wk[e]);
     }
   }
 }
@@ -709,6 +744,18 @@ __global__ __launch_bounds__(256) void k_composite_fwd_bwd_semgrad(RaysDev rays,
     long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit) {
   composite_fwd_bwd_body<true>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
                          out_sem, out_label, d_density, d_rgb, d_logit);
+}
+// fnr_composite_fwd_bwd_targets_opt with an explicit background and / or gradient scaling
+template <bool SEMGRAD, bool BG, bool SCALE>
+__global__ __launch_bounds__(256) void k_composite_fwd_bwd_opt(RaysDev rays, int S, const float* __restrict__ euclid,
+    const float* __restrict__ density, const float* __restrict__ rgb, const float* __restrict__ logit,
+    const float* __restrict__ image, const float* __restrict__ mask, float sem_weight, float* __restrict__ weights,
+    float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth, float* __restrict__ out_sem,
+    long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit,
+    const float* __restrict__ bg, int bg_stride) {
+  static_assert(BG || SCALE, "<last sample, no scaling> is k_composite_fwd_bwd / k_composite_fwd_bwd_semgrad");
+  composite_fwd_bwd_body<SEMGRAD, BG, SCALE>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb,
+                                             out_acc, out_depth, out_sem, out_label, d_density, d_rgb, d_logit, bg, bg_stride);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1132,6 +1179,151 @@ extern "C" int fnr_composite_fwd_bwd_targets_semgrad(const fnr_rays* rays, int S
                      make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
                      out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
                      d_logit);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+// ---- background_color / use_gradient_scaling (fnr_composite_options): the compositing backward calls once more, the options
+// in one struct.  {last sample, no scaling} is the entry point above (its launch, its name in a step program), with the
+// semantic weights detached or attached; the other six combinations of {semantic weights attached, explicit background,
+// scaling} are instantiations of the same bodies.  The selectors return NULL for a combination that is not built (0 and 4:
+// the callers have returned by then) and the entry points refuse it.
+static inline int composite_options_selector(const fnr_composite_options* o) {
+  return (o->semantic_gradients ? 4 : 0) | (o->background == FNR_BACKGROUND_EXPLICIT ? 2 : 0) | (o->gradient_scaling ? 1 : 0);
+}
+template <bool TARGETS>
+static auto composite_bwd_opt_kernel(const fnr_composite_options* o) {
+  decltype(&k_composite_bwd_opt<TARGETS, true, true, true>) kernel = nullptr;
+  switch (composite_options_selector(o)) {
+    case 1: kernel = k_composite_bwd_opt<TARGETS, false, false, true>; break;
+    case 2: kernel = k_composite_bwd_opt<TARGETS, false, true, false>; break;
+    case 3: kernel = k_composite_bwd_opt<TARGETS, false, true, true>; break;
+    case 5: kernel = k_composite_bwd_opt<TARGETS, true, false, true>; break;
+    case 6: kernel = k_composite_bwd_opt<TARGETS, true, true, false>; break;
+    case 7: kernel = k_composite_bwd_opt<TARGETS, true, true, true>; break;
+    default: break;
+  }
+  return kernel;
+}
+static auto composite_fwd_bwd_opt_kernel(const fnr_composite_options* o) {
+  decltype(&k_composite_fwd_bwd_opt<true, true, true>) kernel = nullptr;
+  switch (composite_options_selector(o)) {
+    case 1: kernel = k_composite_fwd_bwd_opt<false, false, true>; break;
+    case 2: kernel = k_composite_fwd_bwd_opt<false, true, false>; break;
+    case 3: kernel = k_composite_fwd_bwd_opt<false, true, true>; break;
+    case 5: kernel = k_composite_fwd_bwd_opt<true, false, true>; break;
+    case 6: kernel = k_composite_fwd_bwd_opt<true, true, false>; break;
+    case 7: kernel = k_composite_fwd_bwd_opt<true, true, true>; break;
+    default: break;
+  }
+  return kernel;
+}
+static inline bool composite_options_plain(const fnr_composite_options* o) {
+  return o->background == FNR_BACKGROUND_LAST_SAMPLE && !o->gradient_scaling;
+}
+#define FNR_CHECK_COMPOSITE_OPTIONS(what, o)                                                                             \
+  FNR_CHECK_ARG(composite_options_ok(o), what ": options NULL or background %d (0 = last sample, 1 = explicit with a "   \
+                "buffer of row stride 0 or 3)", (o) ? (int)(o)->background : -1)
+
+extern "C" int fnr_composite_bwd_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                     const float* rgb, const float* logit, const float* weights, const float* g_rgb,
+                                     const float* g_semantics, const fnr_composite_options* opt, float* d_density,
+                                     float* d_rgb, float* d_logit, void* stream) {
+  FNR_SEQ_UNRECORDABLE("fnr_composite_bwd_opt");
+  FNR_CHECK_COMPOSITE_OPTIONS("composite_bwd_opt", opt);
+  if (composite_options_plain(opt))
+    return opt->semantic_gradients ? fnr_composite_bwd_semgrad(rays, S, euclid_bins, density, rgb, logit, weights, g_rgb,
+                                                               g_semantics, d_density, d_rgb, d_logit, stream)
+                                   : fnr_composite_bwd(rays, S, euclid_bins, density, rgb, weights, g_rgb, g_semantics,
+                                                       d_density, d_rgb, d_logit, stream);
+  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && (logit || !opt->semantic_gradients) && weights && g_rgb &&
+                    g_semantics && d_density && d_rgb && d_logit,
+                "composite_bwd_opt: null argument");
+  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_opt: S %d out of range", S);
+  if (rays->n_rays == 0) return FNR_OK;
+  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
+  const auto kernel = composite_bwd_opt_kernel<false>(opt);
+  FNR_CHECK_ARG(kernel, "composite_bwd_opt: option combination %d is not built", composite_options_selector(opt));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
+                     as_stream(stream), (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, g_rgb,
+                     g_semantics, d_density, d_rgb, d_logit, LossTargets{}, opt->background_rgb,
+                     (int)opt->background_stride);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+extern "C" int fnr_composite_bwd_targets_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                             const float* rgb, const float* logit, const float* weights,
+                                             const float* out_rgb, const float* image, const float* out_semantics,
+                                             const float* mask, float semantic_loss_weight,
+                                             const fnr_composite_options* opt, float* d_density, float* d_rgb,
+                                             float* d_logit, void* stream) {
+  if (opt && composite_options_ok(opt) && composite_options_plain(opt))
+    return opt->semantic_gradients
+               ? fnr_composite_bwd_targets_semgrad(rays, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
+                                                   out_semantics, mask, semantic_loss_weight, d_density, d_rgb, d_logit, stream)
+               : fnr_composite_bwd_targets(rays, S, euclid_bins, density, rgb, weights, out_rgb, image, out_semantics, mask,
+                                           semantic_loss_weight, d_density, d_rgb, d_logit, stream);
+  if (seq::recording() && rays && opt) {
+    const fnr_rays rays_ = *rays;
+    const fnr_composite_options opt_ = *opt;
+    seq::push("fnr_composite_bwd_targets_opt", [=](const fnr_step_scalars*) {
+      return fnr_composite_bwd_targets_opt(&rays_, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
+                                           out_semantics, mask, semantic_loss_weight, &opt_, d_density, d_rgb, d_logit,
+                                           stream);
+    });
+  }
+  FNR_CHECK_COMPOSITE_OPTIONS("composite_bwd_targets_opt", opt);
+  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && (logit || !opt->semantic_gradients) && weights && out_rgb && image &&
+                    out_semantics && mask && d_density && d_rgb && d_logit,
+                "composite_bwd_targets_opt: null argument");
+  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_targets_opt: S %d out of range", S);
+  if (rays->n_rays == 0) return FNR_OK;
+  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
+  const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
+  const auto kernel = composite_bwd_opt_kernel<true>(opt);
+  FNR_CHECK_ARG(kernel, "composite_bwd_targets_opt: option combination %d is not built", composite_options_selector(opt));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
+                     as_stream(stream), (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit,
+                     (const float*)nullptr, (const float*)nullptr, d_density, d_rgb, d_logit, tg, opt->background_rgb,
+                     (int)opt->background_stride);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+extern "C" int fnr_composite_fwd_bwd_targets_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                                 const float* rgb, const float* logit, const float* image, const float* mask,
+                                                 float semantic_loss_weight, const fnr_composite_options* opt,
+                                                 float* weights, float* out_rgb, float* out_accumulation, float* out_depth,
+                                                 float* out_semantics, int64_t* out_label, float* d_density, float* d_rgb,
+                                                 float* d_logit, void* stream) {
+  if (opt && composite_options_ok(opt) && composite_options_plain(opt))
+    return (opt->semantic_gradients ? fnr_composite_fwd_bwd_targets_semgrad : fnr_composite_fwd_bwd_targets)(
+        rays, S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb, out_accumulation,
+        out_depth, out_semantics, out_label, d_density, d_rgb, d_logit, stream);
+  if (seq::recording() && rays && opt) {
+    const fnr_rays rays_ = *rays;
+    const fnr_composite_options opt_ = *opt;
+    seq::push("fnr_composite_fwd_bwd_targets_opt", [=](const fnr_step_scalars*) {
+      return fnr_composite_fwd_bwd_targets_opt(&rays_, S, euclid_bins, density, rgb, logit, image, mask,
+                                               semantic_loss_weight, &opt_, weights, out_rgb, out_accumulation, out_depth,
+                                               out_semantics, out_label, d_density, d_rgb, d_logit, stream);
+    });
+  }
+  FNR_CHECK_COMPOSITE_OPTIONS("composite_fwd_bwd_targets_opt", opt);
+  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && image && mask && weights && out_rgb && out_accumulation &&
+                    out_depth && out_semantics && d_density && d_rgb && d_logit,
+                "composite_fwd_bwd_targets_opt: null argument");
+  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_fwd_bwd_targets_opt: S %d out of range", S);
+  if (rays->n_rays == 0) return FNR_OK;
+  FNR_PROF(OP_COMPOSITE_FWD, rays->n_rays * (long long)S);
+  const auto kernel = composite_fwd_bwd_opt_kernel(opt);
+  FNR_CHECK_ARG(kernel, "composite_fwd_bwd_targets_opt: option combination %d is not built", composite_options_selector(opt));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
+                     as_stream(stream), make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask,
+                     semantic_loss_weight, weights, out_rgb, out_accumulation, out_depth, out_semantics,
+                     reinterpret_cast<long long*>(out_label), d_density, d_rgb, d_logit, opt->background_rgb,
+                     (int)opt->background_stride);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }

@@ -210,7 +210,9 @@ class PixelBatcher:
         cameras; `last_draw` keeps what training.camera_backward_and_step needs to back-propagate into the poses.
         level0 (FruitModel.level0_spec(): S, near, far, n_jitter): the whole start of the step in ONE launch
         (fnr_train_prologue: counter-based random numbers, camera adjust, pixel sampling and the proposal sampler's
-        level-0 bins); `last_presample` then holds what to hand to the model as RayBundle.presampled."""
+        level-0 bins); `last_presample` then holds what to hand to the model as RayBundle.presampled.  With
+        level0["random_background"] (background_color="random") the rays' background colours are drawn behind the prologue
+        with its seed and offset (fnr_random_background) and travel as presampled["background"] [n_rays,3]."""
         d = self.data
         dev = d["images"].device
         if level0 is not None and dev.type == "cuda":
@@ -226,6 +228,8 @@ class PixelBatcher:
             self.last_draw = {"u": out["u"], "cam": out["cam"], "c2w_adjusted": out["c2w_adjusted"]}
             self.last_presample = {"S0": out["S0"], "near": out["near"], "far": out["far"], "spacing": out["spacing"],
                                    "euclid": out["euclid"], "jitter": [out["jitter"][i] for i in range(out["jitter"].shape[0])]}
+            if level0.get("random_background"):
+                self.last_presample["background"] = K.random_background(self.gen.initial_seed(), self._offset, n_rays, dev)
             return out["origins"], out["directions"], out["cam"][:, None], \
                 {"image": out["image"], "fruit_mask": out["mask"][:, None]}
         u = torch.rand(n_rays, 3, device=dev, generator=self.gen)

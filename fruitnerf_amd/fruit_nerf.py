@@ -23,6 +23,9 @@ from .params import HashEncoding, MLP, ParamArena
 from .rays import RayBundle
 
 
+BACKGROUND_COLORS = ("last_sample", "white", "black", "random")   # nerfstudio 0.3.2 RGBRenderer's named backgrounds
+
+
 @dataclass
 class FruitNerfModelConfig:
     """FruitNerfModelConfig(NerfactoModelConfig) — fruit_nerf.py:50-59 plus the inherited Nerfacto 0.3.2
@@ -176,6 +179,7 @@ class RenderContext:
     field_jacobian: Optional[Tensor] = None  # d feats / d(unit-cube position) [L,3,N,2] when the rays want gradients
     ray_bundle: Optional[object] = None   # the caller's RayBundle (its origins / directions may carry autograd history)
     composite_grads: Optional[tuple] = None   # (d_density, d_rgb, d_logit) when the compositing launch ran its own backward
+    composite_options: Optional["K.CompositeOptions"] = None   # background / gradient scaling of this pass (None: neither)
 
 
 class FruitModel(nn.Module):
@@ -268,10 +272,8 @@ class FruitModel(nn.Module):
             # anywhere); a model that is constructed off the device keeps the refusal tests/test_host_logic.py pins
             raise NotImplementedError("pass_semantic_gradients=True is built for the HIP device only: construct the model "
                                       "with device='cuda' (fruit_nerf.py:56)")
-        if cfg.background_color != "last_sample":
-            raise NotImplementedError("only background_color='last_sample' (Nerfacto default) is built")
-        if cfg.use_gradient_scaling:
-            raise NotImplementedError("use_gradient_scaling=True is not built (Nerfacto default False)")
+        if cfg.background_color not in BACKGROUND_COLORS:   # fruit_nerf.py:164 -> RGBRenderer(background_color=...)
+            raise ValueError(f"background_color={cfg.background_color!r}: one of {', '.join(map(repr, BACKGROUND_COLORS))}")
 
     def _apply(self, fn, *a, **kw):
         out = super()._apply(fn, *a, **kw)
@@ -354,7 +356,30 @@ class FruitModel(nn.Module):
         if sampler.num_proposal_network_iterations + 1 > L.FNR_TRAIN_PROLOGUE_MAX_JITTER:
             return None     # more jitters than fnr_train_prologue draws: the separate launches (torch.rand + sample_spaced)
         return {"S": sampler.num_proposal_samples_per_ray[0], "near": float(self.config.near_plane),
-                "far": float(self.config.far_plane), "n_jitter": sampler.num_proposal_network_iterations + 1}
+                "far": float(self.config.far_plane), "n_jitter": sampler.num_proposal_network_iterations + 1,
+                "random_background": self.config.background_color == "random"}
+
+    def _composite_options(self, ray_bundle: RayBundle, n_rays: int, dev) -> Optional["K.CompositeOptions"]:
+        """background_color / use_gradient_scaling of one pass (fruit_nerf.py:164, 280-281, 322-323) as the `_opt` compositing
+        calls take them; None when neither is set (the calls without options).  "white" / "black": one constant triple on
+        the device; "random": one triple per ray and pass — the one drawn with the rays (presampled["background"],
+        PixelBatcher) or a torch.rand draw (evaluation, a ray bundle from another datamanager)."""
+        cfg = self.config
+        color = cfg.background_color
+        if color == "last_sample" and not cfg.use_gradient_scaling:
+            return None
+        background = None
+        if color in ("white", "black"):
+            consts = self.__dict__.setdefault("_background_constants", {})
+            background = consts.get((color, str(dev)))
+            if background is None:
+                background = consts[(color, str(dev))] = torch.full((3,), 1.0 if color == "white" else 0.0, device=dev)
+        elif color == "random":
+            pre = getattr(ray_bundle, "presampled", None)
+            background = pre.get("background") if pre else None
+            if background is None or tuple(background.shape) != (n_rays, 3):
+                background = torch.rand(n_rays, 3, device=dev)
+        return K.CompositeOptions(background, cfg.use_gradient_scaling, cfg.pass_semantic_gradients)
 
     def _collide(self, ray_bundle: RayBundle) -> RayBundle:  # NearFarCollider, fruit_nerf.py:161,382-383
         if ray_bundle.nears is not None and ray_bundle.fars is not None:
@@ -436,13 +461,20 @@ class FruitModel(nn.Module):
             raise AttributeError("Camera indices are not provided.")
         density, rgb, logit, _, h_saved = K.field_mlp_fwd(net, rays, S, feats, selector, mean_emb, want_h=True)
         composite_grads = None
+        opts = self._composite_options(ray_bundle, rays.n, dev)
         # (not on the steps that train the proposal networks: there the second stream's chain — losses launch, proposal
         #  backward, their scatter — is the longer one, and it starts behind this launch)
         if loss_targets is not None and training and not updated:
-            (weights, out_rgb, acc, depth, sem, label), composite_grads = K.composite_fwd_bwd_targets(
-                rays, S, euclid, density, rgb, logit, loss_targets[0], loss_targets[1], loss_targets[2],
-                semgrad=bool(cfg.pass_semantic_gradients))   # fruit_nerf.py:344-345: semantic weights not detached
-        else:
+            if opts is not None:
+                (weights, out_rgb, acc, depth, sem, label), composite_grads = K.composite_fwd_bwd_targets_opt(
+                    rays, S, euclid, density, rgb, logit, loss_targets[0], loss_targets[1], loss_targets[2], opts)
+            else:
+                (weights, out_rgb, acc, depth, sem, label), composite_grads = K.composite_fwd_bwd_targets(
+                    rays, S, euclid, density, rgb, logit, loss_targets[0], loss_targets[1], loss_targets[2],
+                    semgrad=bool(cfg.pass_semantic_gradients))   # fruit_nerf.py:344-345: semantic weights not detached
+        elif opts is not None and opts.background is not None:
+            weights, out_rgb, acc, depth, sem, label = K.composite_fwd_opt(rays, S, euclid, density, rgb, logit, training, opts)
+        else:   # (gradient scaling alone leaves the forward values as they are)
             weights, out_rgb, acc, depth, sem, label = K.composite_fwd(rays, S, euclid, density, rgb, logit, training)
         levels.append(dict(S=S, spacing=spacing, euclid=euclid, density=density.view(rays.n, S), weights=weights,
                            depth=depth, feats=None))
@@ -453,6 +485,7 @@ class FruitModel(nn.Module):
         ctx.ray_bundle = ray_bundle
         ctx.field_jacobian = jac
         ctx.composite_grads = composite_grads
+        ctx.composite_options = opts
         outputs = {"rgb": out_rgb, "accumulation": acc[:, None], "depth": depth[:, None],
                    "semantics": sem[:, None]}
         for i in range(n_prop):

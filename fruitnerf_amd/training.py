@@ -93,7 +93,12 @@ class _RenderFn(torch.autograd.Function):
         if g_sem is None:
             g_sem = torch.zeros(rays.n, 1, device=dev)
         semgrad = bool(model.config.pass_semantic_gradients)   # fruit_nerf.py:344-345: semantic weights not detached
-        if semgrad:
+        opts = getattr(rctx, "composite_options", None)        # background_color / use_gradient_scaling of the forward pass
+        if opts is not None:
+            d_density, d_rgb, d_logit = K.composite_bwd_opt(rays, S, lv["euclid"], rctx.sample_density, rctx.sample_rgb,
+                                                            rctx.sample_logit, rctx.weights, g_rgb.contiguous(),
+                                                            g_sem.contiguous(), opts)
+        elif semgrad:
             d_density, d_rgb, d_logit = K.composite_bwd_semgrad(rays, S, lv["euclid"], rctx.sample_density, rctx.sample_rgb,
                                                                 rctx.sample_logit, rctx.weights, g_rgb.contiguous(),
                                                                 g_sem.contiguous())
@@ -998,8 +1003,16 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
                 crosses_to(main, ray_sources)
                 if serialize_streams:
                     K.stream_wait_stream(main, side)
+        opts = getattr(rctx, "composite_options", None)    # background_color / use_gradient_scaling of the forward pass
         if getattr(rctx, "composite_grads", None) is not None:
             d_density, d_rgb_s, d_logit = rctx.composite_grads
+        elif opts is not None and losses_on_side:
+            d_density, d_rgb_s, d_logit = K.composite_bwd_targets_opt(
+                rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb, rctx.sample_logit, rctx.weights, outputs["rgb"],
+                image, outputs["semantics"], mask, cfg.semantic_loss_weight, opts)
+        elif opts is not None:
+            d_density, d_rgb_s, d_logit = K.composite_bwd_opt(rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb,
+                                                              rctx.sample_logit, rctx.weights, d_rgb, d_sem, opts)
         elif losses_on_side and semgrad:
             d_density, d_rgb_s, d_logit = K.composite_bwd_targets_semgrad(
                 rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb, rctx.sample_logit, rctx.weights, outputs["rgb"],
@@ -1462,7 +1475,7 @@ class TrainingSteps:
                 OVERLAP_PROPOSAL_BACKWARD, SERIALIZE_STREAMS, LOSSES_ON_SIDE, PAIR_PROPOSAL_LEVELS, FUSE_CAMERA_OPTIMIZER,
                 FUSE_WEIGHT_OPTIMIZER, FUSE_TABLE_OPTIMIZER, SPARSE_TOUCH_SKIPPING, STREAM_SAFE, FUSE_COMPOSITE_BACKWARD,
                 cfg.semantic_loss_weight, cfg.interlevel_loss_mult, cfg.near_plane, cfg.far_plane,
-                bool(cfg.pass_semantic_gradients))
+                bool(cfg.pass_semantic_gradients), cfg.background_color, bool(cfg.use_gradient_scaling))
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def step(self, want_metrics: bool = True):

@@ -426,6 +426,57 @@ int fnr_composite_fwd_bwd_targets_semgrad(const fnr_rays* rays, int S, const flo
                                           float* out_accumulation, float* out_depth, float* out_semantics,
                                           int64_t* out_label, float* d_density, float* d_rgb, float* d_logit, void* stream);
 
+/* ---- compositing with Nerfacto's two remaining switches (pure additions at ABI 13) -----------------------------
+ * background_color (reference fruit_nerf.py:164; nerfstudio 0.3.2 RGBRenderer.combine_rgb, recalled — DESIGN §2):
+ *   out_rgb = sum_k w_k c_k + b (1 - sum_k w_k), b = the last sample's colour ("last_sample", what the entry points above
+ *   build) or an explicit triple: "white" (1,1,1), "black" (0,0,0), "random" (U[0,1)^3 per ray and forward pass).  An explicit
+ *   b is a constant of the pass: dL/dw_k = g_rgb . (c_k - b), d_rgb_k = g_rgb w_k for EVERY k (no background share on
+ *   sample S-1), no nan_to_num of b outside training; the clamp of out_rgb outside training stays.
+ * use_gradient_scaling (reference fruit_nerf.py:280-281, 322-323; nerfstudio scale_gradients_by_distance_squared):
+ *   forward values unchanged; d_density, d_rgb and d_logit of sample k are multiplied by s_k = clamp(m_k^2, 0, 1),
+ *   m_k = (euclid_bins[k] + euclid_bins[k+1]) / 2, in float32, as the LAST operation: each output is float32(s_k) x the
+ *   unscaled output, bit for bit.  The proposal levels are not scaled.
+ * The options travel in one struct; with {last sample, no scaling} every entry point below makes the launch of its
+ * counterpart above (same kernel, same bits). */
+#define FNR_BACKGROUND_LAST_SAMPLE 0
+#define FNR_BACKGROUND_EXPLICIT 1
+typedef struct fnr_composite_options {
+  int32_t background;          /* FNR_BACKGROUND_* */
+  int32_t background_stride;   /* explicit: floats between the rows of background_rgb — 3: one triple per ray [R,3];
+                                * 0: one triple for every ray */
+  const float* background_rgb; /* explicit: device; ignored (may be NULL) for the last sample */
+  int32_t gradient_scaling;    /* != 0: use_gradient_scaling */
+  int32_t semantic_gradients;  /* != 0: pass_semantic_gradients (the `_semgrad` entry points) */
+} fnr_composite_options;
+/* fnr_composite_fwd; recordable. */
+int fnr_composite_fwd_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density, const float* rgb,
+                          const float* logit, int training, const fnr_composite_options* options, float* weights,
+                          float* out_rgb, float* out_accumulation, float* out_depth, float* out_semantics,
+                          int64_t* out_label, void* stream);
+/* fnr_composite_bwd / fnr_composite_bwd_semgrad (logit [N]: read with semantic_gradients only); not recordable. */
+int fnr_composite_bwd_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density, const float* rgb,
+                          const float* logit, const float* weights, const float* g_rgb, const float* g_semantics,
+                          const fnr_composite_options* options, float* d_density, float* d_rgb, float* d_logit,
+                          void* stream);
+/* fnr_composite_bwd_targets(_semgrad): bit-identical to fnr_train_losses + fnr_composite_bwd_opt; recordable. */
+int fnr_composite_bwd_targets_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                  const float* rgb, const float* logit, const float* weights, const float* out_rgb,
+                                  const float* image, const float* out_semantics, const float* mask,
+                                  float semantic_loss_weight, const fnr_composite_options* options, float* d_density,
+                                  float* d_rgb, float* d_logit, void* stream);
+/* fnr_composite_fwd_bwd_targets(_semgrad): bit-identical to fnr_composite_fwd_opt (training) +
+ * fnr_composite_bwd_targets_opt; recordable. */
+int fnr_composite_fwd_bwd_targets_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
+                                      const float* rgb, const float* logit, const float* image, const float* mask,
+                                      float semantic_loss_weight, const fnr_composite_options* options, float* weights,
+                                      float* out_rgb, float* out_accumulation, float* out_depth, float* out_semantics,
+                                      int64_t* out_label, float* d_density, float* d_rgb, float* d_logit, void* stream);
+/* background_color = "random": out [n_rays,3] = U[0,1)^3 per ray from the generator of fnr_train_prologue — Philox4x32-10,
+ * counter (ray, word group 2, offset), key seed, words 0-2 through (x >> 8) * 2^-24; the prologue's own numbers are word
+ * groups 0 and 1 of the same (seed, offset).  Recordable: a replayed call takes `offset` from
+ * fnr_step_scalars.prologue_offset, like the prologue. */
+int fnr_random_background(uint64_t seed, uint64_t offset, int64_t n_rays, float* out, void* stream);
+
 /* Backward of RaySamples.get_weights for a proposal level: d_weights [R,S] (x *upstream if non-NULL, a
  * device scalar) -> d_density [R,S]. */
 int fnr_weights_bwd(int64_t n_rays, int S, const float* euclid_bins, const float* density, const float* weights,
@@ -717,6 +768,7 @@ int fnr_adam_step_spans_dev(float* params, float* grads, float* exp_avg, float* 
  * entry points called on this thread — fnr_train_prologue, fnr_prop_density_fwd, fnr_weights_pdf, fnr_hash_encode_fwd,
  * fnr_field_mlp_fwd, fnr_composite_fwd, fnr_train_losses, fnr_composite_bwd_targets, fnr_field_mlp_bwd_adam,
  * fnr_composite_bwd_targets_semgrad, fnr_composite_fwd_bwd_targets_semgrad, fnr_field_mlp_bwd_semgrad (with weight_adam),
+ * fnr_composite_fwd_opt, fnr_composite_bwd_targets_opt, fnr_composite_fwd_bwd_targets_opt, fnr_random_background,
  * fnr_hash_encode_bwd_adam, fnr_prop_density_bwd_pair(_split), fnr_position_grad_reduce_multi,
  * fnr_camera_pose_grad_adam and the stream operations below — run as usual AND append themselves (arguments by value,
  * host structs / host arrays copied) to the program; any other entry point that enqueues device work poisons the
@@ -725,7 +777,7 @@ int fnr_adam_step_spans_dev(float* params, float* grads, float* exp_avg, float* 
  * alive and unchanged in place for as long as it replays the program. */
 #define FNR_PROGRAM_ADAM_SLOTS 4
 typedef struct fnr_step_scalars {
-  uint64_t prologue_offset; /* fnr_train_prologue: `offset` (the step's random-number counter) */
+  uint64_t prologue_offset; /* fnr_train_prologue, fnr_random_background: `offset` (the step's random-number counter) */
   float anneal;             /* fnr_weights_pdf: `anneal` */
   int32_t reserved;
   struct {
