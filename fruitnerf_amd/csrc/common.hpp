@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "../../include/fruitnerf_hip.h"
 
@@ -181,6 +182,19 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ float wave_bcast(float v, int src) { return __shfl(v, src, 64); }
 // per-lane source (lane permutation), e.g. 63 - lane reverses the wave
 __device__ __forceinline__ float wave_bcast_lane(float v, int src_lane) { return __shfl(v, src_lane, 64); }
+
+// The one-wave-per-ray kernels (sampler.hip, train.hip) keep a lane's samples in register arrays and are compiled for ME = 1, 2,
+// 4 or 8 samples per lane (S <= 64 ME): eight-wide arrays cost them waves per SIMD, and with that a second or third generation
+// of workgroups at a training batch.  f(std::integral_constant<int, ME>) with the narrowest ME that holds S samples.
+constexpr int RAY_MAX_LANE_ELEMS = 8;
+template <class F>
+static inline void with_lane_elems(int S, F&& f) {
+  const int E = (S + 63) >> 6;
+  if (E <= 1) f(std::integral_constant<int, 1>{});
+  else if (E <= 2) f(std::integral_constant<int, 2>{});
+  else if (E <= 4) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, RAY_MAX_LANE_ELEMS>{});
+}
 
 // ---- position warp (fruit_field.py:168-179) -------------------------------------------------------
 struct Warp {

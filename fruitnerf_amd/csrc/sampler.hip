@@ -27,37 +27,71 @@ __global__ __launch_bounds__(256) void k_sample_spaced(RaysDev rays, int kind, i
 
 constexpr int PDF_MAXE = 8;        // elements per lane -> S_prev <= 512
 constexpr int PDF_MAX_PREV = 512;  // LDS cdf capacity per wave
+static_assert(PDF_MAXE == RAY_MAX_LANE_ELEMS && PDF_MAX_PREV == 64 * PDF_MAXE, "with_lane_elems picks the kernel");
 
-__global__ __launch_bounds__(256) void k_weights_pdf(RaysDev rays, int kind, int S_prev, int S_new,
-                                                     const float* __restrict__ density,
-                                                     const float* __restrict__ spacing_prev,
-                                                     const float* __restrict__ euclid_prev, float anneal,
-                                                     const float* __restrict__ u_base, const float* __restrict__ rand,
-                                                     float* __restrict__ weights, float* __restrict__ median_depth,
-                                                     float* __restrict__ spacing_new, float* __restrict__ euclid_new) {
-  __shared__ float s_cdf[4][PDF_MAX_PREV + 1];
+// ME: elements per lane the register arrays hold (S_prev <= 64 ME; with_lane_elems picks the narrowest).  The elements a
+// narrower form drops are zeros added to sums that start from +0.0 behind the live elements, or feed nothing: same bits.
+// Everything the wave reads from memory is issued at the top — the resampling's inputs included, the previous level's bin
+// edges staged into LDS next to the CDF — so that a wave waits for memory once, not once per phase.  Six waves per SIMD (80
+// registers at most) keep a 4096-ray launch one resident generation of workgroups whatever ME.
+template <int ME>
+__global__ __launch_bounds__(256, 6) void k_weights_pdf(RaysDev rays, int kind, int S_prev, int S_new,
+                                                        const float* __restrict__ density,
+                                                        const float* __restrict__ spacing_prev,
+                                                        const float* __restrict__ euclid_prev, float anneal,
+                                                        const float* __restrict__ u_base, const float* __restrict__ rand,
+                                                        float* __restrict__ weights, float* __restrict__ median_depth,
+                                                        float* __restrict__ spacing_new, float* __restrict__ euclid_new) {
+  constexpr int CAP = 64 * ME;
+  __shared__ float s_cdf[4][CAP + 1];
+  __shared__ float s_ex[4][CAP + 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r = (long long)blockIdx.x * 4 + wave;
   if (r >= rays.n_rays) return;  // whole wave exits together
   float* cdf = s_cdf[wave];
+  float* ex = s_ex[wave];
   const int E = (S_prev + 63) >> 6;
   const float* eb = euclid_prev + r * (S_prev + 1);
   const float* dn = density + r * S_prev;
+  const int nb = S_new + 1;
+
+  // ---- the resampling's inputs: asked for first, used last ------------------------------------------
+  float near_r = 0.0f, far_r = 0.0f, rand_r = 0.0f, u0 = 0.0f, u1 = 0.0f;
+  float spv[ME + 1];
+#pragma unroll
+  for (int q = 0; q <= ME; ++q) {
+    const int k = lane + 64 * q;
+    spv[q] = (S_new > 0 && k <= S_prev) ? spacing_prev[r * (S_prev + 1) + k] : 0.0f;
+  }
+  if (S_new > 0) {
+    near_r = rays.nears[r];
+    far_r = rays.fars[r];
+    if (rand) rand_r = rand[r];
+    if (lane < nb) u0 = u_base[lane];
+    if (lane + 64 < nb) u1 = u_base[lane + 64];
+  }
 
   // ---- RaySamples.get_weights ----------------------------------------------------------------
-  float dd[PDF_MAXE], w[PDF_MAXE];
+  float dd[ME], w[ME];
   float local = 0.0f;
 #pragma unroll
-  for (int e = 0; e < PDF_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     dd[e] = 0.0f;
     if (e < E && k < S_prev) dd[e] = fmul(fsub(eb[k + 1], eb[k]), dn[k]);
     local += dd[e];
   }
+  if (S_new > 0) {
+#pragma unroll
+    for (int q = 0; q <= ME; ++q) {
+      const int k = lane + 64 * q;
+      if (k <= S_prev) ex[k] = spv[q];   // (read behind the CDF's lgkmcnt(0) + wave barrier)
+    }
+  }
   float excl = wave_excl_scan(local, lane);  // sum of delta*sigma before this lane's chunk
   float wsum_local = 0.0f;
 #pragma unroll
-  for (int e = 0; e < PDF_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     const float T = expf(-excl);
     const float alpha = 1.0f - expf(-dd[e]);
@@ -76,7 +110,7 @@ __global__ __launch_bounds__(256) void k_weights_pdf(RaysDev rays, int kind, int
     float cw = wave_excl_scan(wsum_local, lane);
     int first = 0x7fffffff;
 #pragma unroll
-    for (int e = 0; e < PDF_MAXE; ++e) {
+    for (int e = 0; e < ME; ++e) {
       const int k = lane * E + e;
       cw += w[e];
       if (e < E && k < S_prev && cw >= 0.5f && first == 0x7fffffff) first = k;
@@ -89,10 +123,10 @@ __global__ __launch_bounds__(256) void k_weights_pdf(RaysDev rays, int kind, int
   if (S_new <= 0) return;
 
   // ---- PDFSampler: annealed, padded histogram -> CDF in LDS --------------------------------------
-  float wa[PDF_MAXE];
+  float wa[ME];
   float sum_local = 0.0f;
 #pragma unroll
-  for (int e = 0; e < PDF_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     wa[e] = 0.0f;
     if (e < E && k < S_prev) {
@@ -107,7 +141,7 @@ __global__ __launch_bounds__(256) void k_weights_pdf(RaysDev rays, int kind, int
   wsum = fadd(wsum, padding);
   float pdf_local = 0.0f;
 #pragma unroll
-  for (int e = 0; e < PDF_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     if (e < E && k < S_prev) {
       wa[e] = fdiv(fadd(wa[e], pad_each), wsum);
@@ -117,7 +151,7 @@ __global__ __launch_bounds__(256) void k_weights_pdf(RaysDev rays, int kind, int
   float run = wave_excl_scan(pdf_local, lane);
   if (lane == 0) cdf[0] = 0.0f;
 #pragma unroll
-  for (int e = 0; e < PDF_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     if (e < E && k < S_prev) {
       run += wa[e];
@@ -128,12 +162,10 @@ __global__ __launch_bounds__(256) void k_weights_pdf(RaysDev rays, int kind, int
   __builtin_amdgcn_wave_barrier();
 
   // ---- inverse-CDF resampling ----------------------------------------------------------------------
-  const int nb = S_new + 1;
-  const float u_shift = rand ? fdiv(rand[r], (float)nb) : (float)(1.0 / (2.0 * (double)nb));
-  const float s_near = spacing_fn(kind, rays.nears[r]), s_far = spacing_fn(kind, rays.fars[r]);
-  const float* ex = spacing_prev + r * (S_prev + 1);
+  const float u_shift = rand ? fdiv(rand_r, (float)nb) : (float)(1.0 / (2.0 * (double)nb));
+  const float s_near = spacing_fn(kind, near_r), s_far = spacing_fn(kind, far_r);
   for (int jj = lane; jj < nb; jj += 64) {
-    const float u = fadd(u_base[jj], u_shift);
+    const float u = fadd(jj == lane ? u0 : jj == lane + 64 ? u1 : u_base[jj], u_shift);
     // searchsorted(cdf, u, side="right"): number of entries <= u
     int lo = 0, hi = S_prev + 1;
     while (lo < hi) {
@@ -192,9 +224,11 @@ extern "C" int fnr_weights_pdf(const fnr_rays* rays, int spacing_kind, int S_pre
   FNR_CHECK_ARG(spacing_kind == 0 || spacing_kind == 1, "weights_pdf: spacing_kind %d", spacing_kind);
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_WEIGHTS_PDF, rays->n_rays * (long long)S_prev);
-  hipLaunchKernelGGL(k_weights_pdf, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                     make_rays(rays), spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev, anneal, u_base,
-                     rand, weights, median_depth, spacing_new, euclid_new);
+  with_lane_elems(S_prev, [&](auto me) {
+    hipLaunchKernelGGL(k_weights_pdf<decltype(me)::value>, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
+                       as_stream(stream), make_rays(rays), spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev,
+                       anneal, u_base, rand, weights, median_depth, spacing_new, euclid_new);
+  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }

@@ -78,44 +78,48 @@ __global__ __launch_bounds__(1024) void k_losses(long long R, const float* __res
 // ---------------------------------------------------------------------------------------------------
 constexpr int IL_MAX_P = 512;
 constexpr int WB_MAXE = 8;   // samples per lane in the per-ray weight kernels (S <= 512)
+static_assert(WB_MAXE == RAY_MAX_LANE_ELEMS, "with_lane_elems picks the kernel");
 
-// k_weights_bwd<false> for one ray with the upstream gradient d(loss)/d(w_k) already in registers (gw[e] belongs to
-// sample lane * E + e, zero beyond S): same operations in the same order -> bit-identical d_density.
-__device__ __forceinline__ void weights_bwd_ray_from_regs(long long r, int S, int lane, const float* __restrict__ euclid,
-                                                          const float* __restrict__ density,
-                                                          const float* __restrict__ weights,
-                                                          const float (&gw)[WB_MAXE], float* __restrict__ d_density) {
+// The per-ray weight kernels are compiled per ME, the samples a lane's register arrays hold (common.hpp: with_lane_elems).  A
+// narrower form does what the eight-wide one does: the elements it drops are zeros, added to sums that start from +0.0 or
+// behind the live elements (no effect), with one exception — `suffix += 0 * 0` AHEAD of the live elements turns a suffix of
+// -0.0 into +0.0.  padded_suffix() keeps that one addition (x + 0.0 + 0.0 == x + 0.0; at ME = 8 a full lane never had it).
+template <int ME>
+__device__ __forceinline__ float padded_suffix(float suffix) {
+  if constexpr (ME < WB_MAXE) suffix += 0.0f;
+  return suffix;
+}
+// k_weights_bwd<false> for one ray with everything it reads already in registers: the upstream gradient d(loss)/d(w_k) (gw[e]
+// belongs to sample lane * E + e, zero beyond S), the weights, delta = the bin widths and the densities.  Same operations in the
+// same order -> bit-identical d_density.
+template <int ME>
+__device__ __forceinline__ void weights_bwd_ray_from_regs(long long r, int S, int lane, const float (&delta)[ME],
+                                                          const float (&dnv)[ME], const float (&wk)[ME],
+                                                          const float (&gw)[ME], float* __restrict__ d_density) {
   const int E = (S + 63) >> 6;
-  const float* eb = euclid + r * (S + 1);
-  const float* dn = density + r * S;
-  const float* w = weights + r * S;
-  float delta[WB_MAXE], wk[WB_MAXE];
   float dd_local = 0.0f, gww_local = 0.0f;
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
-    delta[e] = 0.0f;
-    wk[e] = 0.0f;
     if (e < E && k < S) {
-      delta[e] = eb[k + 1] - eb[k];
-      wk[e] = w[k];
-      dd_local += delta[e] * dn[k];
+      dd_local += delta[e] * dnv[e];
       gww_local += gw[e] * wk[e];
     }
   }
   float cum_dd = wave_excl_scan(dd_local, lane);
-  float suffix = wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane);
-  float suf[WB_MAXE];
+  float suffix =
+      padded_suffix<ME>(wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane));
+  float suf[ME];
 #pragma unroll
-  for (int e = WB_MAXE - 1; e >= 0; --e) {
+  for (int e = ME - 1; e >= 0; --e) {
     suf[e] = suffix;
-    suffix += gw[e] * wk[e];
+    suffix += gw[e] * wk[e];   // gw / wk are 0 for e >= E or k >= S
   }
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     if (e < E && k < S) {
-      cum_dd += delta[e] * dn[k];
+      cum_dd += delta[e] * dnv[e];
       const float T_next = expf(-cum_dd);
       d_density[r * S + k] = delta[e] * (gw[e] * T_next - suf[e]);
     }
@@ -158,7 +162,36 @@ __device__ __forceinline__ void slot_add(float* __restrict__ row, int block, int
   }
 }
 
-template <bool FIXED = false>
+// distortion_loss (metric, fruit_nerf.py:400) of one ray, by its wave: sum_ij w_i w_j |m_i - m_j| + sum_i w_i^2 ds_i / 3, the
+// wave's total in every lane.  s_m / s_w: S floats of LDS each, this wave's own.  t0, t1, w0: t[lane], t[lane + 1], w[lane],
+// loaded by the caller (lanes >= S: anything) — a caller that holds the ray already pays no second round trip to memory.
+__device__ __forceinline__ float distortion_wave(int S, const float* __restrict__ t, const float* __restrict__ w,
+                                                 float* s_m, float* s_w, int lane, float t0, float t1, float w0) {
+  if (lane < S) {
+    s_m[lane] = (t1 + t0) / 2.0f;
+    s_w[lane] = w0;
+  }
+  for (int k = lane + 64; k < S; k += 64) {
+    s_m[k] = (t[k + 1] + t[k]) / 2.0f;
+    s_w[k] = w[k];
+  }
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_wave_barrier();
+  float acc = 0.0f;
+  for (int i = lane; i < S; i += 64) {
+    const float mi = s_m[i], wi = s_w[i];
+    float inner = 0.0f;
+    for (int j = 0; j < S; ++j) inner += s_w[j] * fabsf(mi - s_m[j]);
+    const float ds = i == lane ? t1 - t0 : t[i + 1] - t[i];
+    acc += wi * inner + wi * wi * ds / 3.0f;
+  }
+  return wave_sum(acc);
+}
+
+// ME: samples per lane the register arrays hold (S_p <= 64 ME).  dist_out (k_train_losses): this wave also sums the
+// distortion metric of its ray — it needs only the final level's spacing and weights, which the wave reads anyway — in the
+// first 2 S_f floats of its own LDS region, once it has read `dd` for the last time.
+template <bool FIXED = false, int ME = WB_MAXE>
 __device__ __forceinline__ void interlevel_block(long long R, int S_f, const float* __restrict__ spacing_f,
                                                  const float* __restrict__ w_f, int S_p,
                                                  const float* __restrict__ spacing_p, const float* __restrict__ w_p,
@@ -166,7 +199,8 @@ __device__ __forceinline__ void interlevel_block(long long R, int S_f, const flo
                                                  int block, float* lds, int p_cap,  // lds: 4 * (3 * p_cap + 4) floats
                                                  const float* __restrict__ euclid_p = nullptr,
                                                  const float* __restrict__ density_p = nullptr,
-                                                 float* __restrict__ d_density_p = nullptr, unsigned* flag = nullptr) {
+                                                 float* __restrict__ d_density_p = nullptr, unsigned* flag = nullptr,
+                                                 float* __restrict__ dist_out = nullptr) {  // needs 2 S_f <= 3 p_cap + 4
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r = (long long)block * 4 + wave;
   if (r >= R) return;
@@ -175,38 +209,75 @@ __device__ __forceinline__ void interlevel_block(long long R, int S_f, const flo
   float* dd = cy + p_cap + 1;
   const float* sp = spacing_p + r * (S_p + 1);
   const float* wp = w_p + r * S_p;
-  // cy1 = [0, cumsum(wp)] : lane-chunked scan
+  const float* c = spacing_f + r * (S_f + 1);
+  const float* w = w_f + r * S_f;
   const int E = (S_p + 63) >> 6;
-  float local = 0.0f;
-  for (int e = 0; e < E; ++e) {
+  // ---- everything the wave reads from memory, issued before anything waits: one round trip, not one per phase ----------
+  float wv[ME], spv[ME + 1], delta[ME], dnv[ME];
+#pragma unroll
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
-    if (k < S_p) local += wp[k];
+    wv[e] = (e < E && k < S_p) ? wp[k] : 0.0f;
+  }
+#pragma unroll
+  for (int q = 0; q <= ME; ++q) {
+    const int k = lane + 64 * q;
+    spv[q] = k <= S_p ? sp[k] : 0.0f;
+  }
+  float c0 = 0.0f, c1 = 0.0f, w0 = 0.0f;   // the final level's first 64 samples (all of them at the usual 48)
+  if (lane < S_f) {
+    c0 = c[lane];
+    c1 = c[lane + 1];
+    w0 = w[lane];
+  }
+#pragma unroll
+  for (int e = 0; e < ME; ++e) {
+    const int k = lane * E + e;
+    delta[e] = 0.0f;
+    dnv[e] = 0.0f;
+    if (d_density_p && e < E && k < S_p) {
+      const float* eb = euclid_p + r * (S_p + 1);
+      delta[e] = eb[k + 1] - eb[k];
+      dnv[e] = density_p[r * S_p + k];
+    }
+  }
+  // cy1 = [0, cumsum(wp)] : lane-chunked scan
+  float local = 0.0f;
+#pragma unroll
+  for (int e = 0; e < ME; ++e) {
+    const int k = lane * E + e;
+    if (e < E && k < S_p) local += wv[e];
   }
   float run = wave_excl_scan(local, lane);
   if (lane == 0) cy[0] = 0.0f;
-  for (int e = 0; e < E; ++e) {
+#pragma unroll
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
-    if (k < S_p) {
-      run += wp[k];
+    if (e < E && k < S_p) {
+      run += wv[e];
       cy[k + 1] = run;
     }
   }
-  for (int k = lane; k <= S_p; k += 64) cp[k] = sp[k];
+#pragma unroll
+  for (int q = 0; q <= ME; ++q) {
+    const int k = lane + 64 * q;
+    if (k <= S_p) cp[k] = spv[q];
+  }
   for (int k = lane; k <= S_p + 1; k += 64) dd[k] = 0.0f;
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_wave_barrier();
 
-  const float* c = spacing_f + r * (S_f + 1);
-  const float* w = w_f + r * S_f;
   const float scale = mult / (float)(R * (long long)S_f);
   float lsum = 0.0f;
   for (int i = lane; i < S_f; i += 64) {
-    int lo = searchsorted_right(cp, S_p, c[i]) - 1;          // t1_starts = cp[:-1]
+    const bool head = i == lane;
+    const float ci = head ? c0 : c[i], ci1 = head ? c1 : c[i + 1];
+    int lo = searchsorted_right(cp, S_p, ci) - 1;            // t1_starts = cp[:-1]
     lo = min(max(lo, 0), S_p - 1);
-    int hi = searchsorted_right(cp + 1, S_p, c[i + 1]);      // t1_ends = cp[1:]
+    int hi = searchsorted_right(cp + 1, S_p, ci1);           // t1_ends = cp[1:]
     hi = min(max(hi, 0), S_p - 1);
     const float w_outer = cy[hi + 1] - cy[lo];
-    const float wi = w[i];
+    const float wi = head ? w0 : w[i];
     const float diff = fmaxf(wi - w_outer, 0.0f);
     const float den = wi + 1.0e-7f;
     lsum += diff * diff / den;
@@ -222,35 +293,37 @@ __device__ __forceinline__ void interlevel_block(long long R, int S_f, const flo
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_wave_barrier();
   // d_wp = inclusive scan of the difference array
+  float ddv[ME];
   float l2 = 0.0f;
-  for (int e = 0; e < E; ++e) {
+#pragma unroll
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
-    if (k < S_p) l2 += dd[k];
+    ddv[e] = 0.0f;
+    if (e < E && k < S_p) {
+      ddv[e] = dd[k];
+      l2 += ddv[e];
+    }
   }
   float run2 = wave_excl_scan(l2, lane);
-  if (!d_density_p) {
-    for (int e = 0; e < E; ++e) {
-      const int k = lane * E + e;
-      if (k < S_p) {
-        run2 += dd[k];
-        d_wp[r * S_p + k] = run2;
-      }
-    }
-    return;
-  }
-  // the proposal level's weights backward right here (the ray is in this wave's hands; d_wp stays in registers)
-  float gw[WB_MAXE];
+  // (with d_density_p: the proposal level's weights backward right here — the ray is in this wave's hands, d_wp and the
+  // level's weights stay in registers)
+  float gw[ME];
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     gw[e] = 0.0f;
     if (e < E && k < S_p) {
-      run2 += dd[k];
+      run2 += ddv[e];
       gw[e] = run2;
       if (d_wp) d_wp[r * S_p + k] = run2;
     }
   }
-  weights_bwd_ray_from_regs(r, S_p, lane, euclid_p, density_p, w_p, gw, d_density_p);
+  if (dist_out) {   // ahead of the backward: its slot atomic is acknowledged while the backward runs
+    __builtin_amdgcn_wave_barrier();   // `dd` has been read: the region is free
+    const float acc = distortion_wave(S_f, c, w, cp, cp + S_f, lane, c0, c1, w0);
+    if (lane == 0) slot_add<FIXED>(dist_out, block, wave, acc / (float)R, flag);
+  }
+  if (d_density_p) weights_bwd_ray_from_regs<ME>(r, S_p, lane, delta, dnv, wv, gw, d_density_p);
 }
 __global__ __launch_bounds__(256) void k_interlevel(long long R, int S_f, const float* __restrict__ spacing_f,
                                                     const float* __restrict__ w_f, int S_p,
@@ -271,24 +344,15 @@ __device__ __forceinline__ void distortion_block(long long R, int S, const float
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r = (long long)block * 4 + wave;
   if (r >= R) return;
-  float* s_m = s_m_all + wave * s_cap;
-  float* s_w = s_w_all + wave * s_cap;
   const float* t = spacing + r * (S + 1);
   const float* w = weights + r * S;
-  for (int k = lane; k < S; k += 64) {
-    s_m[k] = (t[k + 1] + t[k]) / 2.0f;
-    s_w[k] = w[k];
+  float t0 = 0.0f, t1 = 0.0f, w0 = 0.0f;
+  if (lane < S) {
+    t0 = t[lane];
+    t1 = t[lane + 1];
+    w0 = w[lane];
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-  float acc = 0.0f;
-  for (int i = lane; i < S; i += 64) {
-    const float mi = s_m[i], wi = s_w[i];
-    float inner = 0.0f;
-    for (int j = 0; j < S; ++j) inner += s_w[j] * fabsf(mi - s_m[j]);
-    acc += wi * inner + wi * wi * (t[i + 1] - t[i]) / 3.0f;
-  }
-  acc = wave_sum(acc);
+  const float acc = distortion_wave(S, t, w, s_m_all + wave * s_cap, s_w_all + wave * s_cap, lane, t0, t1, w0);
   if (lane == 0) slot_add<FIXED>(out, block, wave, acc / (float)R, flag);
 }
 __global__ __launch_bounds__(256) void k_distortion(long long R, int S, const float* __restrict__ spacing,
@@ -299,11 +363,16 @@ __global__ __launch_bounds__(256) void k_distortion(long long R, int S, const fl
 
 // Every loss of a training step in ONE launch (fnr_train_losses; five dependent 4-10 us launches before): workgroups
 // [0, nbl) = rgb + semantic losses and their gradients (256 rays each), then (R + 3) / 4 workgroups per proposal level
-// = interlevel loss, then as many for the distortion metric.  Sums go to accumulator slots in 32 different 128-byte
+// = interlevel loss, one wave per ray.  The distortion metric of a ray is summed by the wave that holds the ray for the
+// proposal level with the fewest samples (dist_host); only where no level can host it — none given, or 2 S_f floats do not
+// fit a wave's LDS region — it gets (R + 3) / 4 workgroups of its own at the end.  The kernel is compiled per ME (see
+// with_lane_elems) and kept at 64 registers for ME <= 4, eight workgroups per CU: a 4096-ray batch with two proposal
+// levels is 2064 workgroups, one resident generation on 256 CUs.  Sums go to accumulator slots in 32 different 128-byte
 // lines (same-line atomics serialise at ~12 ns each); the last workgroup to finish — found with a two-level
 // completion count for the same reason — adds the slots up and writes the five scalars.
 struct LevelLossArgs {
   int n_levels;
+  int dist_host;   // the level whose waves sum the distortion metric too; -1: none
   int S_p[FNR_MAX_PROPOSAL_LEVELS];
   const float* spacing_p[FNR_MAX_PROPOSAL_LEVELS];
   const float* w_p[FNR_MAX_PROPOSAL_LEVELS];
@@ -315,7 +384,8 @@ struct LevelLossArgs {
 constexpr int TL_ROWS = 4;                                       // slot rows: interlevel, distortion, rgb, semantic
 constexpr int TL_ACCUM_FLOATS = TL_ROWS * FNR_LOSS_SLOTS + 33 * 32;  // + 32 group counters and the top one, a line each
 static_assert(TL_ACCUM_FLOATS == FNR_TRAIN_LOSSES_ACCUM_FLOATS, "fruitnerf_hip.h: FNR_TRAIN_LOSSES_ACCUM_FLOATS");
-__global__ __launch_bounds__(256) void k_train_losses(long long R, const float* __restrict__ rgb,
+template <int ME>
+__global__ __launch_bounds__(256, ME <= 4 ? 8 : 1) void k_train_losses(long long R, const float* __restrict__ rgb,
                                                       const float* __restrict__ image, const float* __restrict__ sem,
                                                       const float* __restrict__ mask, float sem_weight,
                                                       float* __restrict__ d_rgb, float* __restrict__ d_sem, int S_f,
@@ -323,9 +393,10 @@ __global__ __launch_bounds__(256) void k_train_losses(long long R, const float* 
                                                       const float* __restrict__ w_f, LevelLossArgs lv, float mult,
                                                       int want_distortion, float* __restrict__ accum,
                                                       float* __restrict__ losses, int p_cap) {
-  extern __shared__ float lds[];   // max(4 * (3 * p_cap + 4), 8 * S_f) floats: sized by the launch, not for 512 samples
+  extern __shared__ float lds[];   // 4 * (3 * p_cap + 4) floats, 8 * S_f for a distortion role: sized by the launch
   __shared__ bool s_last;
-  __shared__ long long s_red[TL_ROWS][4];
+  __shared__ unsigned long long s_tot[TL_ROWS];
+  static_assert(TL_ROWS == 4 && FNR_LOSS_SLOTS == 1024, "the last workgroup's two rows per thread");
   float* il_slots = accum;
   float* di_slots = accum + FNR_LOSS_SLOTS;
   float* rgb_slots = accum + 2 * FNR_LOSS_SLOTS;
@@ -363,9 +434,9 @@ __global__ __launch_bounds__(256) void k_train_losses(long long R, const float* 
     const int b = (int)blockIdx.x - nbl;
     const int role = b / per, local = b - role * per;
     if (role < lv.n_levels)
-      interlevel_block<true>(R, S_f, spacing_f, w_f, lv.S_p[role], lv.spacing_p[role], lv.w_p[role], mult, il_slots,
-                             lv.d_wp[role], local, lds, p_cap, lv.euclid_p[role], lv.density_p[role],
-                             lv.d_density_p[role], flag);
+      interlevel_block<true, ME>(R, S_f, spacing_f, w_f, lv.S_p[role], lv.spacing_p[role], lv.w_p[role], mult, il_slots,
+                                 lv.d_wp[role], local, lds, p_cap, lv.euclid_p[role], lv.density_p[role],
+                                 lv.d_density_p[role], flag, role == lv.dist_host ? di_slots : nullptr);
     else
       distortion_block<true>(R, S_f, spacing_f, w_f, di_slots, local, lds, S_f, flag);
   }
@@ -382,30 +453,29 @@ __global__ __launch_bounds__(256) void k_train_losses(long long R, const float* 
     if (atomicAdd(&cnt[g * 32], 1u) == gsize - 1u) last = atomicAdd(&cnt[32 * 32], 1u) == ngroups - 1u;
     s_last = last;
   }
+  if (threadIdx.x < TL_ROWS) s_tot[threadIdx.x] = 0ull;
   __syncthreads();
   if (!s_last) return;
-  // the rows hold 64-bit fixed point (slot_add<true>): integer sums, any order
-  long long acc[TL_ROWS] = {0, 0, 0, 0};
-  for (int i = threadIdx.x; i < FNR_LOSS_SLOTS / 2; i += 256)
+  // The rows hold 64-bit fixed point (slot_add<true>): integer sums, any order.  A row is 512 words of which slot_add uses
+  // (block & 31) * 16 + wave, wave < 4: 128.  Two rows per thread, summed with LDS atomics (a handful of cycles against a
+  // shuffle tree per row); thread 0 asks for the flag in the same trip to memory.
+  const int word = ((threadIdx.x & 127) >> 2) * 16 + (threadIdx.x & 3), q0 = (threadIdx.x >> 7) * 2;
+  unsigned bad_bits = 0u;
+  if (threadIdx.x == 0) bad_bits = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-    for (int q = 0; q < TL_ROWS; ++q)
-      acc[q] += (long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(accum + q * FNR_LOSS_SLOTS) + i,
-                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-  for (int q = 0; q < TL_ROWS; ++q) {
-#pragma unroll
-    for (int dsh = 32; dsh >= 1; dsh >>= 1) acc[q] += __shfl_xor(acc[q], dsh, 64);
-    if (lane == 0) s_red[q][wave] = acc[q];
-  }
+  for (int q = 0; q < 2; ++q)
+    atomicAdd(&s_tot[q0 + q],
+              __hip_atomic_load(reinterpret_cast<unsigned long long*>(accum + (q0 + q) * FNR_LOSS_SLOTS) + word,
+                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   __syncthreads();
+  // self-cleaning: this (last) workgroup has read every slot and every other workgroup is done, so the accumulator goes
+  // back to zero here — a caller that keeps the buffer needs no fill launch before the next step
+  for (int i = threadIdx.x; i < TL_ACCUM_FLOATS; i += 256) accum[i] = 0.0f;
   if (threadIdx.x == 0) {
-    const bool bad = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+    const bool bad = bad_bits != 0u;
     float t[TL_ROWS];
 #pragma unroll
-    for (int q = 0; q < TL_ROWS; ++q) {
-      const long long tot = (s_red[q][0] + s_red[q][1]) + (s_red[q][2] + s_red[q][3]);
-      t[q] = bad ? __builtin_nanf("") : (float)((double)tot / TL_FIX_SCALE);
-    }
+    for (int q = 0; q < TL_ROWS; ++q) t[q] = bad ? __builtin_nanf("") : (float)((double)(long long)s_tot[q] / TL_FIX_SCALE);
     const float mse = t[2] * inv3r;
     losses[0] = mse;
     losses[1] = sem_weight * t[3] * invr;
@@ -413,10 +483,6 @@ __global__ __launch_bounds__(256) void k_train_losses(long long R, const float* 
     losses[3] = t[0];
     losses[4] = want_distortion ? t[1] : 0.0f;
   }
-  // self-cleaning: this (last) workgroup has read every slot and every other workgroup is done, so the accumulator goes
-  // back to zero here — a caller that keeps the buffer needs no fill launch before the next step
-  __syncthreads();
-  for (int i = threadIdx.x; i < TL_ACCUM_FLOATS; i += 256) accum[i] = 0.0f;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -446,7 +512,7 @@ __device__ __forceinline__ float distance_squared_scale(float e0, float e1) {
   const float m = fdiv(fadd(e0, e1), 2.0f);
   return fminf(fmaxf(fmul(m, m), 0.0f), 1.0f);
 }
-template <bool COMPOSITE, bool TARGETS, bool SEMGRAD, bool BG = false, bool SCALE = false>
+template <bool COMPOSITE, bool TARGETS, bool SEMGRAD, bool BG = false, bool SCALE = false, int ME = WB_MAXE>
 __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float* __restrict__ euclid,
                                                  const float* __restrict__ density, const float* __restrict__ weights,
                                                  const float* __restrict__ d_w_in,    // !COMPOSITE: [R,S]
@@ -490,10 +556,10 @@ __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float
     l1 = cl[1];
     l2 = cl[2];
   }
-  float delta[WB_MAXE], gw[WB_MAXE], wk[WB_MAXE];
+  float delta[ME], gw[ME], wk[ME];
   float dd_local = 0.0f, gww_local = 0.0f, wsum_local = 0.0f;
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     delta[e] = 0.0f;
     gw[e] = 0.0f;
@@ -518,16 +584,17 @@ __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float
   // tiny terms while total and prefix agree to 7 digits, and dL/dsigma there is multiplied by sigma (up to e^15) in the
   // trunc_exp backward — the cancellation error was comparable to the real gradient (autograd's cumsum backward is a
   // reverse cumsum, i.e. exact in this sense).
-  float suffix = wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane);
+  float suffix =
+      padded_suffix<ME>(wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane));
   if (COMPOSITE && !BG) bgw = 1.0f - wave_sum(wsum_local);
-  float suf[WB_MAXE];   // suffix AFTER element e of this lane's chunk
+  float suf[ME];   // suffix AFTER element e of this lane's chunk
 #pragma unroll
-  for (int e = WB_MAXE - 1; e >= 0; --e) {
+  for (int e = ME - 1; e >= 0; --e) {
     suf[e] = suffix;
     suffix += gw[e] * wk[e];   // gw / wk are 0 for e >= E or k >= S
   }
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     if (e < E && k < S) {
       cum_dd += delta[e] * dn[k];   // inclusive of k
@@ -549,7 +616,7 @@ __device__ __forceinline__ void weights_bwd_body(long long R, int S, const float
   }
 }
 
-template <bool COMPOSITE, bool TARGETS = false>
+template <bool COMPOSITE, bool TARGETS = false, int ME = WB_MAXE>
 __global__ __launch_bounds__(256) void k_weights_bwd(long long R, int S, const float* __restrict__ euclid,
                                                      const float* __restrict__ density,
                                                      const float* __restrict__ weights,
@@ -560,11 +627,11 @@ __global__ __launch_bounds__(256) void k_weights_bwd(long long R, int S, const f
                                                      const float* __restrict__ g_sem,     // COMPOSITE: [R]
                                                      float* __restrict__ d_density, float* __restrict__ d_rgb,
                                                      float* __restrict__ d_logit, LossTargets tg = LossTargets{}) {
-  weights_bwd_body<COMPOSITE, TARGETS, false>(R, S, euclid, density, weights, d_w_in, upstream, rgb, g_rgb, g_sem, d_density,
+  weights_bwd_body<COMPOSITE, TARGETS, false, false, false, ME>(R, S, euclid, density, weights, d_w_in, upstream, rgb, g_rgb, g_sem, d_density,
                                               d_rgb, d_logit, tg, nullptr);
 }
 // fnr_composite_bwd_semgrad / fnr_composite_bwd_targets_semgrad: k_weights_bwd<true, TARGETS> with the semantic term
-template <bool TARGETS>
+template <bool TARGETS, int ME = WB_MAXE>
 __global__ __launch_bounds__(256) void k_weights_bwd_semgrad(long long R, int S, const float* __restrict__ euclid,
                                                              const float* __restrict__ density,
                                                              const float* __restrict__ weights, const float* __restrict__ rgb,
@@ -573,7 +640,7 @@ __global__ __launch_bounds__(256) void k_weights_bwd_semgrad(long long R, int S,
                                                              const float* __restrict__ g_sem,     // !TARGETS: [R]
                                                              float* __restrict__ d_density, float* __restrict__ d_rgb,
                                                              float* __restrict__ d_logit, LossTargets tg) {
-  weights_bwd_body<true, TARGETS, true>(R, S, euclid, density, weights, nullptr, nullptr, rgb, g_rgb, g_sem, d_density, d_rgb,
+  weights_bwd_body<true, TARGETS, true, false, false, ME>(R, S, euclid, density, weights, nullptr, nullptr, rgb, g_rgb, g_sem, d_density, d_rgb,
                                         d_logit, tg, logit);
 }
 // fnr_composite_bwd_opt / fnr_composite_bwd_targets_opt with an explicit background and / or gradient scaling
@@ -594,7 +661,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd_opt(long long R, int S, c
 
 // k_composite_fwd (render.hip, training mode) followed by k_weights_bwd<true, true> for the same ray, in one wave: everything the
 // backward read back from memory (weights, composited colour and logit) stays in registers.
-template <bool SEMGRAD, bool BG = false, bool SCALE = false>  // see weights_bwd_body
+template <bool SEMGRAD, bool BG = false, bool SCALE = false, int ME = WB_MAXE>  // see weights_bwd_body
 __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, const float* __restrict__ euclid,
                                                        const float* __restrict__ density, const float* __restrict__ rgb,
                                                        const float* __restrict__ logit, const float* __restrict__ image,
@@ -605,7 +672,7 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
                                                        float* __restrict__ d_density, float* __restrict__ d_rgb,
                                                        float* __restrict__ d_logit, const float* __restrict__ bg = nullptr,
                                                        int bg_stride = 0) {
-  static_assert(WB_MAXE == 8, "the forward and the backward chunk a ray the same way");
+  static_assert(ME <= WB_MAXE, "the forward and the backward chunk a ray the same way");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long R = rays.n_rays;
   const long long r = (long long)blockIdx.x * 4 + wave;
@@ -616,20 +683,20 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
   const float* cs = rgb + r * S * 3;
   const float* lg = logit + r * S;
   // ---- forward: k_composite_fwd with training = 1 -----------------------------------------------------------------------
-  float dd[WB_MAXE];
+  float dd[ME];
   float local = 0.0f;
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     dd[e] = 0.0f;
     if (e < E && k < S) dd[e] = fmul(fsub(eb[k + 1], eb[k]), dn[k]);
     local += dd[e];
   }
   float excl = wave_excl_scan(local, lane);
-  float w[WB_MAXE];
+  float w[ME];
   float acc_l = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f, sm = 0.0f;
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     const float T = expf(-excl);
     const float alpha = 1.0f - expf(-dd[e]);
@@ -650,7 +717,7 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
   float cw = wave_excl_scan(acc_l, lane);
   int first = 0x7fffffff;
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     cw += w[e];
     if (e < E && k < S && cw >= 0.5f && first == 0x7fffffff) first = k;
@@ -681,10 +748,10 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
   const float gr = mse_grad(o0 - image[3 * r], inv3r), gg = mse_grad(o1 - image[3 * r + 1], inv3r),
               gb = mse_grad(o2 - image[3 * r + 2], inv3r);
   const float gs = bce_logit_grad(sm, mask[r], sem_weight, invr);
-  float delta[WB_MAXE], gw[WB_MAXE], wk[WB_MAXE];
+  float delta[ME], gw[ME], wk[ME];
   float dd_local = 0.0f, gww_local = 0.0f, wsum_local = 0.0f;
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     delta[e] = 0.0f;
     gw[e] = 0.0f;
@@ -701,16 +768,17 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
     }
   }
   float cum_dd = wave_excl_scan(dd_local, lane);
-  float suffix = wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane);
+  float suffix =
+      padded_suffix<ME>(wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane));
   const float bgw = 1.0f - wave_sum(wsum_local);
-  float suf[WB_MAXE];
+  float suf[ME];
 #pragma unroll
-  for (int e = WB_MAXE - 1; e >= 0; --e) {
+  for (int e = ME - 1; e >= 0; --e) {
     suf[e] = suffix;
     suffix += gw[e] * wk[e];
   }
 #pragma unroll
-  for (int e = 0; e < WB_MAXE; ++e) {
+  for (int e = 0; e < ME; ++e) {
     const int k = lane * E + e;
     if (e < E && k < S) {
       cum_dd += delta[e] * dn[k];
@@ -729,20 +797,22 @@ __device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, cons
     }
   }
 }
+template <int ME = WB_MAXE>
 __global__ __launch_bounds__(256) void k_composite_fwd_bwd(RaysDev rays, int S, const float* __restrict__ euclid,
     const float* __restrict__ density, const float* __restrict__ rgb, const float* __restrict__ logit,
     const float* __restrict__ image, const float* __restrict__ mask, float sem_weight, float* __restrict__ weights,
     float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth, float* __restrict__ out_sem,
     long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit) {
-  composite_fwd_bwd_body<false>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
+  composite_fwd_bwd_body<false, false, false, ME>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
                           out_sem, out_label, d_density, d_rgb, d_logit);
 }
+template <int ME = WB_MAXE>
 __global__ __launch_bounds__(256) void k_composite_fwd_bwd_semgrad(RaysDev rays, int S, const float* __restrict__ euclid,
     const float* __restrict__ density, const float* __restrict__ rgb, const float* __restrict__ logit,
     const float* __restrict__ image, const float* __restrict__ mask, float sem_weight, float* __restrict__ weights,
     float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth, float* __restrict__ out_sem,
     long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit) {
-  composite_fwd_bwd_body<true>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
+  composite_fwd_bwd_body<true, false, false, ME>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
                          out_sem, out_label, d_density, d_rgb, d_logit);
 }
 // fnr_composite_fwd_bwd_targets_opt with an explicit background and / or gradient scaling
@@ -1045,9 +1115,11 @@ extern "C" int fnr_composite_bwd(const fnr_rays* rays, int S, const float* eucli
   FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd: S %d out of range", S);
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
-  hipLaunchKernelGGL((k_weights_bwd<true>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                     (long long)rays->n_rays, S, euclid_bins, density, weights, (const float*)nullptr,
-                     (const float*)nullptr, rgb, g_rgb, g_semantics, d_density, d_rgb, d_logit);
+  with_lane_elems(S, [&](auto me) {
+    hipLaunchKernelGGL((k_weights_bwd<true, false, decltype(me)::value>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       (long long)rays->n_rays, S, euclid_bins, density, weights, (const float*)nullptr,
+                       (const float*)nullptr, rgb, g_rgb, g_semantics, d_density, d_rgb, d_logit);
+  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -1070,9 +1142,11 @@ extern "C" int fnr_composite_bwd_targets(const fnr_rays* rays, int S, const floa
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
   const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
-  hipLaunchKernelGGL((k_weights_bwd<true, true>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                     (long long)rays->n_rays, S, euclid_bins, density, weights, (const float*)nullptr,
-                     (const float*)nullptr, rgb, (const float*)nullptr, (const float*)nullptr, d_density, d_rgb, d_logit, tg);
+  with_lane_elems(S, [&](auto me) {
+    hipLaunchKernelGGL((k_weights_bwd<true, true, decltype(me)::value>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       (long long)rays->n_rays, S, euclid_bins, density, weights, (const float*)nullptr,
+                       (const float*)nullptr, rgb, (const float*)nullptr, (const float*)nullptr, d_density, d_rgb, d_logit, tg);
+  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -1101,10 +1175,12 @@ extern "C" int fnr_composite_fwd_bwd_targets(const fnr_rays* rays, int S, const 
   FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_fwd_bwd_targets: S %d out of range", S);
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_COMPOSITE_FWD, rays->n_rays * (long long)S);
-  hipLaunchKernelGGL(k_composite_fwd_bwd, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                     make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
-                     out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
-                     d_logit);
+  with_lane_elems(S, [&](auto me) {
+    hipLaunchKernelGGL(k_composite_fwd_bwd<decltype(me)::value>, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
+                       out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
+                       d_logit);
+  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -1122,9 +1198,11 @@ extern "C" int fnr_composite_bwd_semgrad(const fnr_rays* rays, int S, const floa
   FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_semgrad: S %d out of range", S);
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
-  hipLaunchKernelGGL((k_weights_bwd_semgrad<false>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
-                     as_stream(stream), (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, g_rgb,
-                     g_semantics, d_density, d_rgb, d_logit, LossTargets{});
+  with_lane_elems(S, [&](auto me) {
+    hipLaunchKernelGGL((k_weights_bwd_semgrad<false, decltype(me)::value>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
+                       as_stream(stream), (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, g_rgb,
+                       g_semantics, d_density, d_rgb, d_logit, LossTargets{});
+  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -1148,9 +1226,11 @@ extern "C" int fnr_composite_bwd_targets_semgrad(const fnr_rays* rays, int S, co
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
   const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
-  hipLaunchKernelGGL((k_weights_bwd_semgrad<true>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                     (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, (const float*)nullptr,
-                     (const float*)nullptr, d_density, d_rgb, d_logit, tg);
+  with_lane_elems(S, [&](auto me) {
+    hipLaunchKernelGGL((k_weights_bwd_semgrad<true, decltype(me)::value>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, (const float*)nullptr,
+                       (const float*)nullptr, d_density, d_rgb, d_logit, tg);
+  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -1175,10 +1255,12 @@ extern "C" int fnr_composite_fwd_bwd_targets_semgrad(const fnr_rays* rays, int S
   FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_fwd_bwd_targets_semgrad: S %d out of range", S);
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_COMPOSITE_FWD, rays->n_rays * (long long)S);
-  hipLaunchKernelGGL(k_composite_fwd_bwd_semgrad, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                     make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
-                     out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
-                     d_logit);
+  with_lane_elems(S, [&](auto me) {
+    hipLaunchKernelGGL(k_composite_fwd_bwd_semgrad<decltype(me)::value>, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
+                       out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
+                       d_logit);
+  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -1336,9 +1418,11 @@ extern "C" int fnr_weights_bwd(int64_t n_rays, int S, const float* euclid_bins, 
   FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "weights_bwd: S %d out of range", S);
   if (n_rays == 0) return FNR_OK;
   FNR_PROF(OP_WEIGHTS_BWD, n_rays * (long long)S);
-  hipLaunchKernelGGL((k_weights_bwd<false>), dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                     (long long)n_rays, S, euclid_bins, density, weights, d_weights, upstream, (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, d_density, (float*)nullptr, (float*)nullptr);
+  with_lane_elems(S, [&](auto me) {
+    hipLaunchKernelGGL((k_weights_bwd<false, false, decltype(me)::value>), dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       (long long)n_rays, S, euclid_bins, density, weights, d_weights, upstream, (const float*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr, d_density, (float*)nullptr, (float*)nullptr);
+  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -1545,15 +1629,24 @@ extern "C" int fnr_train_losses(int64_t n_rays, const float* rgb, const float* i
       FNR_CHECK_ARG(lv.d_wp[l], "train_losses: level %d: neither d_weights_p nor d_density_p", l);
     }
   }
-  const long long per = (n_rays + 3) / 4;
-  const long long blocks = (n_rays + 255) / 256 + per * (n_levels + (want_distortion ? 1 : 0));
-  FNR_CHECK_ARG(blocks < (1ll << 31), "train_losses: too many rays");
-  FNR_PROF(OP_LOSSES, n_rays);
   int p_cap = 1;
   for (int l = 0; l < n_levels; ++l) p_cap = S_p[l] > p_cap ? S_p[l] : p_cap;
+  lv.dist_host = -1;
+  if (want_distortion && n_levels > 0 && 2ll * S_f <= 3ll * p_cap + 4) {
+    lv.dist_host = 0;
+    for (int l = 1; l < n_levels; ++l)
+      if (S_p[l] < S_p[lv.dist_host]) lv.dist_host = l;
+  }
+  const bool distortion_role = want_distortion && lv.dist_host < 0;
+  const long long per = (n_rays + 3) / 4;
+  const long long blocks = (n_rays + 255) / 256 + per * (n_levels + (distortion_role ? 1 : 0));
+  FNR_CHECK_ARG(blocks < (1ll << 31), "train_losses: too many rays");
+  FNR_PROF(OP_LOSSES, n_rays);
   size_t lds_floats = 4 * (size_t)(3 * p_cap + 4);
-  if (want_distortion && (size_t)8 * S_f > lds_floats) lds_floats = (size_t)8 * S_f;
-  hipLaunchKernelGGL(k_train_losses, dim3((unsigned)blocks), dim3(256), lds_floats * sizeof(float), as_stream(stream),
+  if (distortion_role && (size_t)8 * S_f > lds_floats) lds_floats = (size_t)8 * S_f;
+  // (no one-wide form: two samples per lane fit the 64 registers of eight workgroups per CU already)
+  auto kernel = p_cap <= 128 ? k_train_losses<2> : p_cap <= 256 ? k_train_losses<4> : k_train_losses<WB_MAXE>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_floats * sizeof(float), as_stream(stream),
                      (long long)n_rays, rgb, image, semantics, fruit_mask, semantic_loss_weight, d_rgb, d_semantics, S_f,
                      spacing_f, weights_f, lv, interlevel_mult, want_distortion, accum, losses, p_cap);
   FNR_LAUNCH_CHECK();
