@@ -357,30 +357,27 @@ def composite_fwd(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: T
     return weights, out_rgb, acc, depth, sem, label
 
 
+def _composite_fwd_bwd_call(name: str, rays: RaysArg, S: int, *args):
+    """fnr_<name>(rays, S, *args, <six forward outputs>, <three gradients>, stream) with the outputs allocated here (tensors
+    among `args` by address, as in _composite_bwd_call).  -> (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb,
+    d_logit)."""
+    dev = rays.device
+    N = rays.n * S
+    outs = (_empty(rays.n, S, device=dev), _empty(rays.n, 3, device=dev), _empty(rays.n, device=dev),
+            _empty(rays.n, device=dev), _empty(rays.n, device=dev), _empty(rays.n, dtype=torch.int64, device=dev))
+    grads = (_empty(N, device=dev), _empty(N, 3, device=dev), _empty(N, device=dev))
+    argv = [L.ptr(a) if isinstance(a, Tensor) else a for a in args]
+    L.check(getattr(L.load(), "fnr_" + name)(rays.ref, S, *argv, *map(L.ptr, outs + grads), L.stream_ptr(dev)), name)
+    return outs, grads
+
+
 def composite_fwd_bwd_targets(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor, image: Tensor,
                               mask: Tensor, sem_weight: float, semgrad: bool = False):
     """composite_fwd (training) and composite_bwd_targets as one launch (fnr_composite_fwd_bwd_targets): the same outputs and
     gradients, bit for bit.  -> (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit).
     semgrad (pass_semantic_gradients): fnr_composite_fwd_bwd_targets_semgrad — d_density carries the semantic term too."""
-    lib = L.load()
-    dev = rays.device
-    N = rays.n * S
-    weights = _empty(rays.n, S, device=dev)
-    out_rgb = _empty(rays.n, 3, device=dev)
-    acc = _empty(rays.n, device=dev)
-    depth = _empty(rays.n, device=dev)
-    sem = _empty(rays.n, device=dev)
-    label = _empty(rays.n, dtype=torch.int64, device=dev)
-    d_density = _empty(N, device=dev)
-    d_rgb = _empty(N, 3, device=dev)
-    d_logit = _empty(N, device=dev)
-    fn = lib.fnr_composite_fwd_bwd_targets_semgrad if semgrad else lib.fnr_composite_fwd_bwd_targets
-    L.check(fn(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
-               L.ptr(_f32c(image)), L.ptr(_f32c(mask.reshape(-1))), float(sem_weight),
-               L.ptr(weights), L.ptr(out_rgb), L.ptr(acc), L.ptr(depth), L.ptr(sem), L.ptr(label),
-               L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
-            "composite_fwd_bwd_targets_semgrad" if semgrad else "composite_fwd_bwd_targets")
-    return (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit)
+    return _composite_fwd_bwd_call("composite_fwd_bwd_targets_semgrad" if semgrad else "composite_fwd_bwd_targets", rays, S,
+                                   euclid, density, rgb, logit, _f32c(image), _f32c(mask.reshape(-1)), float(sem_weight))
 
 
 class CompositeOptions:
@@ -440,24 +437,8 @@ def composite_fwd_bwd_targets_opt(rays: RaysArg, S: int, euclid: Tensor, density
                                   image: Tensor, mask: Tensor, sem_weight: float, opts: CompositeOptions):
     """composite_fwd_bwd_targets under the options (fnr_composite_fwd_bwd_targets_opt): bit-identical to composite_fwd_opt +
     composite_bwd_targets_opt.  -> (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit)."""
-    lib = L.load()
-    dev = rays.device
-    N = rays.n * S
-    weights = _empty(rays.n, S, device=dev)
-    out_rgb = _empty(rays.n, 3, device=dev)
-    acc = _empty(rays.n, device=dev)
-    depth = _empty(rays.n, device=dev)
-    sem = _empty(rays.n, device=dev)
-    label = _empty(rays.n, dtype=torch.int64, device=dev)
-    d_density = _empty(N, device=dev)
-    d_rgb = _empty(N, 3, device=dev)
-    d_logit = _empty(N, device=dev)
-    L.check(lib.fnr_composite_fwd_bwd_targets_opt(
-        rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit), L.ptr(_f32c(image)),
-        L.ptr(_f32c(mask.reshape(-1))), float(sem_weight), opts.ref(rays.n), L.ptr(weights), L.ptr(out_rgb), L.ptr(acc),
-        L.ptr(depth), L.ptr(sem), L.ptr(label), L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
-        "composite_fwd_bwd_targets_opt")
-    return (weights, out_rgb, acc, depth, sem, label), (d_density, d_rgb, d_logit)
+    return _composite_fwd_bwd_call("composite_fwd_bwd_targets_opt", rays, S, euclid, density, rgb, logit, _f32c(image),
+                                   _f32c(mask.reshape(-1)), float(sem_weight), opts.ref(rays.n))
 
 
 # ---- export -------------------------------------------------------------------------------------------
@@ -561,105 +542,63 @@ def train_losses(rgb: Tensor, image: Tensor, semantics: Tensor, fruit_mask: Tens
     return losses, d_rgb, d_sem, outs
 
 
-def composite_bwd(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, weights: Tensor, g_rgb: Tensor,
-                  g_sem: Tensor):
-    lib = L.load()
+def _composite_bwd_call(name: str, rays: RaysArg, S: int, *args):
+    """fnr_<name>(rays, S, *args, d_density, d_rgb, d_logit, stream) -> the three gradients, allocated here.  Tensors among
+    `args` go by address; they are held until the call is enqueued and converted after the outputs are allocated, so a
+    contiguous copy made for the call cannot give its memory to an output."""
     dev = rays.device
     N = rays.n * S
-    d_density = _empty(N, device=dev)
-    d_rgb = _empty(N, 3, device=dev)
-    d_logit = _empty(N, device=dev)
-    L.check(lib.fnr_composite_bwd(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(weights),
-                                  L.ptr(_f32c(g_rgb)), L.ptr(_f32c(g_sem.reshape(-1))), L.ptr(d_density),
-                                  L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)), "composite_bwd")
-    return d_density, d_rgb, d_logit
+    grads = (_empty(N, device=dev), _empty(N, 3, device=dev), _empty(N, device=dev))
+    argv = [L.ptr(a) if isinstance(a, Tensor) else a for a in args]
+    L.check(getattr(L.load(), "fnr_" + name)(rays.ref, S, *argv, *map(L.ptr, grads), L.stream_ptr(dev)), name)
+    return grads
+
+
+def composite_bwd(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, weights: Tensor, g_rgb: Tensor,
+                  g_sem: Tensor):
+    return _composite_bwd_call("composite_bwd", rays, S, euclid, density, rgb, weights, _f32c(g_rgb),
+                               _f32c(g_sem.reshape(-1)))
 
 
 def composite_bwd_targets(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, weights: Tensor,
                           out_rgb: Tensor, image: Tensor, out_sem: Tensor, mask: Tensor, sem_weight: float):
     """composite_bwd with the per-ray loss gradients formed inside the kernel from the composited outputs and the batch
     (fnr_composite_bwd_targets): no dependence on the losses launch, same bits."""
-    lib = L.load()
-    dev = rays.device
-    N = rays.n * S
-    d_density = _empty(N, device=dev)
-    d_rgb = _empty(N, 3, device=dev)
-    d_logit = _empty(N, device=dev)
-    L.check(lib.fnr_composite_bwd_targets(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(weights),
-                                          L.ptr(_f32c(out_rgb)), L.ptr(_f32c(image)), L.ptr(_f32c(out_sem.reshape(-1))),
-                                          L.ptr(_f32c(mask.reshape(-1))), float(sem_weight), L.ptr(d_density),
-                                          L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)), "composite_bwd_targets")
-    return d_density, d_rgb, d_logit
+    return _composite_bwd_call("composite_bwd_targets", rays, S, euclid, density, rgb, weights, _f32c(out_rgb), _f32c(image),
+                               _f32c(out_sem.reshape(-1)), _f32c(mask.reshape(-1)), float(sem_weight))
 
 
 def composite_bwd_semgrad(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor,
                           weights: Tensor, g_rgb: Tensor, g_sem: Tensor):
     """composite_bwd under pass_semantic_gradients (fnr_composite_bwd_semgrad): the semantic renderer's weights are not
     detached, d_density also carries g_sem * logit_k (logit [N]: the per-sample logits); d_rgb / d_logit as composite_bwd."""
-    lib = L.load()
-    dev = rays.device
-    N = rays.n * S
-    d_density = _empty(N, device=dev)
-    d_rgb = _empty(N, 3, device=dev)
-    d_logit = _empty(N, device=dev)
-    L.check(lib.fnr_composite_bwd_semgrad(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
-                                          L.ptr(weights), L.ptr(_f32c(g_rgb)), L.ptr(_f32c(g_sem.reshape(-1))),
-                                          L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
-            "composite_bwd_semgrad")
-    return d_density, d_rgb, d_logit
+    return _composite_bwd_call("composite_bwd_semgrad", rays, S, euclid, density, rgb, logit, weights, _f32c(g_rgb),
+                               _f32c(g_sem.reshape(-1)))
 
 
 def composite_bwd_targets_semgrad(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor,
                                   weights: Tensor, out_rgb: Tensor, image: Tensor, out_sem: Tensor, mask: Tensor,
                                   sem_weight: float):
     """composite_bwd_targets under pass_semantic_gradients (fnr_composite_bwd_targets_semgrad)."""
-    lib = L.load()
-    dev = rays.device
-    N = rays.n * S
-    d_density = _empty(N, device=dev)
-    d_rgb = _empty(N, 3, device=dev)
-    d_logit = _empty(N, device=dev)
-    L.check(lib.fnr_composite_bwd_targets_semgrad(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
-                                                  L.ptr(weights), L.ptr(_f32c(out_rgb)), L.ptr(_f32c(image)),
-                                                  L.ptr(_f32c(out_sem.reshape(-1))), L.ptr(_f32c(mask.reshape(-1))),
-                                                  float(sem_weight), L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit),
-                                                  L.stream_ptr(dev)), "composite_bwd_targets_semgrad")
-    return d_density, d_rgb, d_logit
+    return _composite_bwd_call("composite_bwd_targets_semgrad", rays, S, euclid, density, rgb, logit, weights, _f32c(out_rgb),
+                               _f32c(image), _f32c(out_sem.reshape(-1)), _f32c(mask.reshape(-1)), float(sem_weight))
 
 
 def composite_bwd_opt(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor, weights: Tensor,
                       g_rgb: Tensor, g_sem: Tensor, opts: "CompositeOptions"):
     """composite_bwd / composite_bwd_semgrad under the options (fnr_composite_bwd_opt): explicit background, gradients
     scaled by the clamped squared distance of their sample."""
-    lib = L.load()
-    dev = rays.device
-    N = rays.n * S
-    d_density = _empty(N, device=dev)
-    d_rgb = _empty(N, 3, device=dev)
-    d_logit = _empty(N, device=dev)
-    L.check(lib.fnr_composite_bwd_opt(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit), L.ptr(weights),
-                                      L.ptr(_f32c(g_rgb)), L.ptr(_f32c(g_sem.reshape(-1))), opts.ref(rays.n),
-                                      L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.stream_ptr(dev)),
-            "composite_bwd_opt")
-    return d_density, d_rgb, d_logit
+    return _composite_bwd_call("composite_bwd_opt", rays, S, euclid, density, rgb, logit, weights, _f32c(g_rgb),
+                               _f32c(g_sem.reshape(-1)), opts.ref(rays.n))
 
 
 def composite_bwd_targets_opt(rays: RaysArg, S: int, euclid: Tensor, density: Tensor, rgb: Tensor, logit: Tensor,
                               weights: Tensor, out_rgb: Tensor, image: Tensor, out_sem: Tensor, mask: Tensor,
                               sem_weight: float, opts: "CompositeOptions"):
     """composite_bwd_targets(_semgrad) under the options (fnr_composite_bwd_targets_opt)."""
-    lib = L.load()
-    dev = rays.device
-    N = rays.n * S
-    d_density = _empty(N, device=dev)
-    d_rgb = _empty(N, 3, device=dev)
-    d_logit = _empty(N, device=dev)
-    L.check(lib.fnr_composite_bwd_targets_opt(rays.ref, S, L.ptr(euclid), L.ptr(density), L.ptr(rgb), L.ptr(logit),
-                                              L.ptr(weights), L.ptr(_f32c(out_rgb)), L.ptr(_f32c(image)),
-                                              L.ptr(_f32c(out_sem.reshape(-1))), L.ptr(_f32c(mask.reshape(-1))),
-                                              float(sem_weight), opts.ref(rays.n), L.ptr(d_density), L.ptr(d_rgb),
-                                              L.ptr(d_logit), L.stream_ptr(dev)), "composite_bwd_targets_opt")
-    return d_density, d_rgb, d_logit
+    return _composite_bwd_call("composite_bwd_targets_opt", rays, S, euclid, density, rgb, logit, weights, _f32c(out_rgb),
+                               _f32c(image), _f32c(out_sem.reshape(-1)), _f32c(mask.reshape(-1)), float(sem_weight),
+                               opts.ref(rays.n))
 
 
 def weights_bwd(S: int, euclid: Tensor, density: Tensor, weights: Tensor, d_weights: Tensor,

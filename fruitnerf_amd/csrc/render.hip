@@ -1,6 +1,7 @@
 // render.hip — alpha compositing for gfx950: RaySamples.get_weights + RGBRenderer("last_sample") +
 // AccumulationRenderer + DepthRenderer("median") + SemanticRenderer (fruit_nerf.py:325-348), one wave per ray.
 #include "common.hpp"
+#include "composite_math.hpp"
 #include "sequencer.hpp"
 
 namespace fnr {
@@ -22,66 +23,15 @@ __device__ __forceinline__ void composite_fwd_body(RaysDev rays, int S, const fl
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r = (long long)blockIdx.x * 4 + wave;
   if (r >= rays.n_rays) return;
-  const int E = (S + 63) >> 6;
   const float* eb = euclid + r * (S + 1);
   const float* dn = density + r * S;
   const float* cs = rgb + r * S * 3;
   const float* lg = logit + r * S;
 
-  float dd[CMP_MAXE];
-  float local = 0.0f;
-#pragma unroll
-  for (int e = 0; e < CMP_MAXE; ++e) {
-    const int k = lane * E + e;
-    dd[e] = 0.0f;
-    if (e < E && k < S) dd[e] = fmul(fsub(eb[k + 1], eb[k]), dn[k]);
-    local += dd[e];
-  }
-  float excl = wave_excl_scan(local, lane);
   float w[CMP_MAXE];
-  float acc_l = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f, sm = 0.0f;
-#pragma unroll
-  for (int e = 0; e < CMP_MAXE; ++e) {
-    const int k = lane * E + e;
-    const float T = expf(-excl);
-    const float alpha = 1.0f - expf(-dd[e]);
-    w[e] = nan_to_num(alpha * T);
-    excl += dd[e];
-    if (e < E && k < S) {
-      weights[r * S + k] = w[e];
-      float c0 = cs[3 * k], c1 = cs[3 * k + 1], c2 = cs[3 * k + 2];
-      if (!training) {
-        c0 = nan_to_num(c0);
-        c1 = nan_to_num(c1);
-        c2 = nan_to_num(c2);
-      }
-      acc_l += w[e];
-      cr = fmaf(w[e], c0, cr);
-      cg = fmaf(w[e], c1, cg);
-      cb = fmaf(w[e], c2, cb);
-      sm = fmaf(w[e], lg[k], sm);
-    } else {
-      w[e] = 0.0f;
-    }
-  }
-  // median depth before the reductions destroy the per-lane partials
-  float cw = wave_excl_scan(acc_l, lane);
-  int first = 0x7fffffff;
-#pragma unroll
-  for (int e = 0; e < CMP_MAXE; ++e) {
-    const int k = lane * E + e;
-    cw += w[e];
-    if (e < E && k < S && cw >= 0.5f && first == 0x7fffffff) first = k;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) first = min(first, __shfl_xor(first, d, 64));
-  if (first > S - 1) first = S - 1;
-
-  const float acc = wave_sum(acc_l);
-  cr = wave_sum(cr);
-  cg = wave_sum(cg);
-  cb = wave_sum(cb);
-  sm = wave_sum(sm);
+  float acc, cr, cg, cb, sm;
+  int first;
+  composite_fwd_ray<CMP_MAXE>(r, S, lane, eb, dn, cs, lg, training, weights, w, acc, cr, cg, cb, sm, first);
   if (lane == 0) {
     // background_color = "last_sample": rgb[..., -1, :] * (1 - accumulated_weight)
     float l0, l1, l2;
@@ -181,9 +131,7 @@ extern "C" int fnr_composite_fwd_opt(const fnr_rays* rays, int S, const float* e
                                    out_accumulation, out_depth, out_semantics, out_label, stream);
     });
   }
-  FNR_CHECK_ARG(composite_options_ok(opt),
-                "composite_fwd_opt: options NULL or background %d (0 = last sample, 1 = explicit with a buffer of row "
-                "stride 0 or 3)", opt ? (int)opt->background : -1);
+  FNR_CHECK_COMPOSITE_OPTIONS("composite_fwd_opt", opt);
   FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && weights && out_rgb && out_accumulation && out_depth &&
                     out_semantics,
                 "composite_fwd_opt: null argument");

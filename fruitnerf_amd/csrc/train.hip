@@ -1,26 +1,17 @@
-// train.hip — losses, their gradients, compositing backward and the fused Adam step for gfx950.
+// train.hip — losses, their gradients and the fused Adam step for gfx950.
 //   get_loss_dict (fruit_nerf.py:359-372): MSELoss, BCEWithLogitsLoss, interlevel_loss
 //   get_metrics_dict (fruit_nerf.py:396-401): distortion_loss (metric only)
-//   backward of RaySamples.get_weights + renderers (fruit_nerf.py:325-348)
 //   optimiser: torch.optim.Adam semantics (fruit_nerf_config.py:47-56)
+// (the backward of RaySamples.get_weights + renderers: composite_bwd.hip)
 // One wave per ray for the per-ray scans; everything here is bandwidth-trivial next to the field kernels.
 #include "common.hpp"
+#include "composite_math.hpp"
 #include "sequencer.hpp"
 
 namespace fnr {
 
 // ---------------------------------------------------------------------------------------------------
-// rgb MSE + semantic BCE-with-logits: values and unit gradients
-// The per-ray gradients of the two image losses, unit upstream: d MSELoss(mean over 3 R values) / d rgb_c and
-// d (w * BCEWithLogitsLoss(mean over R)) / d logit.  ONE definition for every kernel that forms them — losses_block,
-// k_train_losses and the composite backward that takes the targets itself (k_weights_bwd<.., TARGETS>): the bit-identity of
-// those paths (tests/test_gpu_training_parity.py::test_composite_bwd_targets_is_losses_then_composite_bwd) rests on it.
-__device__ __forceinline__ float mse_grad(float diff, float inv3r) { return 2.0f * diff * inv3r; }
-__device__ __forceinline__ float bce_logit_grad(float x, float y, float sem_weight, float invr) {
-  const float sg = 1.0f / (1.0f + expf(-x));
-  return sem_weight * (sg - y) * invr;
-}
-
+// rgb MSE + semantic BCE-with-logits: values and unit gradients (mse_grad, bce_logit_grad: composite_math.hpp)
 // ---------------------------------------------------------------------------------------------------
 // One workgroup: a training batch is a few thousand rays, and finishing inside the kernel (block reduction, PSNR)
 // saves the memset, the atomics and three follow-up elementwise launches per step.
@@ -77,19 +68,8 @@ __global__ __launch_bounds__(1024) void k_losses(long long R, const float* __res
 // value (accumulated) + unit gradient w.r.t. the proposal weights.
 // ---------------------------------------------------------------------------------------------------
 constexpr int IL_MAX_P = 512;
-constexpr int WB_MAXE = 8;   // samples per lane in the per-ray weight kernels (S <= 512)
-static_assert(WB_MAXE == RAY_MAX_LANE_ELEMS, "with_lane_elems picks the kernel");
 
-// The per-ray weight kernels are compiled per ME, the samples a lane's register arrays hold (common.hpp: with_lane_elems).  A
-// narrower form does what the eight-wide one does: the elements it drops are zeros, added to sums that start from +0.0 or
-// behind the live elements (no effect), with one exception — `suffix += 0 * 0` AHEAD of the live elements turns a suffix of
-// -0.0 into +0.0.  padded_suffix() keeps that one addition (x + 0.0 + 0.0 == x + 0.0; at ME = 8 a full lane never had it).
-template <int ME>
-__device__ __forceinline__ float padded_suffix(float suffix) {
-  if constexpr (ME < WB_MAXE) suffix += 0.0f;
-  return suffix;
-}
-// k_weights_bwd<false> for one ray with everything it reads already in registers: the upstream gradient d(loss)/d(w_k) (gw[e]
+// k_weights_bwd (composite_bwd.hip) for one ray with everything it reads already in registers: the upstream gradient d(loss)/d(w_k) (gw[e]
 // belongs to sample lane * E + e, zero beyond S), the weights, delta = the bin widths and the densities.  Same operations in the
 // same order -> bit-identical d_density.
 template <int ME>
@@ -486,349 +466,6 @@ __global__ __launch_bounds__(256, ME <= 4 ? 8 : 1) void k_train_losses(long long
 }
 
 // ---------------------------------------------------------------------------------------------------
-// backward of w_i = (1 - exp(-d_i s_i)) exp(-sum_{j<i} d_j s_j):
-//   dL/ds_k = d_k [ g_k T_{k+1} - sum_{i>k} g_i w_i ],  T_{k+1} = exp(-sum_{j<=k} d_j s_j)
-// ---------------------------------------------------------------------------------------------------
-// TARGETS (fnr_composite_bwd_targets): the per-ray loss gradients are not read from memory but formed here from the
-// composited outputs and the batch — g_rgb = 2 (rgb - image) / (3 R), g_sem = w_sem (sigmoid(sem) - mask) / R: the very
-// expressions of k_train_losses, so the same bits — which makes this launch independent of the losses launch: a training
-// step runs the MLP backward straight behind the forward while the loss VALUES (and the interlevel loss with the proposal
-// levels' weights backward) are summed on the second stream.
-struct LossTargets {
-  const float* out_rgb;    // [R,3] composited colour
-  const float* image;      // [R,3]
-  const float* out_sem;    // [R]   composited logit
-  const float* mask;       // [R]
-  float sem_weight;
-};
-// SEMGRAD (pass_semantic_gradients, fruit_nerf.py:344-345): the semantic renderer's weights are NOT detached, so the semantic
-// term joins the upstream gradient of the weights, gw[k] += g_sem logit_k, and the rest of the kernel carries it into d_density.
-// BG (background_color "white" / "black" / "random"): the background is an explicit triple, row r * bg_stride of `bg`, a
-// constant of the pass — it takes the last sample's place in dL/dw_k = g_rgb . (c_k - b) and sample S-1 gets no background share.
-// SCALE (use_gradient_scaling, nerfstudio scale_gradients_by_distance_squared): every gradient that leaves towards the field —
-// d_density, d_rgb, d_logit of sample k — is multiplied by s_k = clamp(m_k^2, 0, 1), m_k the bin's Euclidean midpoint.
-// <.., false, false> is the code it was: the two switches only add to it.
-__device__ __forceinline__ float distance_squared_scale(float e0, float e1) {
-  const float m = fdiv(fadd(e0, e1), 2.0f);
-  return fminf(fmaxf(fmul(m, m), 0.0f), 1.0f);
-}
-template <bool COMPOSITE, bool TARGETS, bool SEMGRAD, bool BG = false, bool SCALE = false, int ME = WB_MAXE>
-__device__ __forceinline__ void weights_bwd_body(long long R, int S, const float* __restrict__ euclid,
-                                                 const float* __restrict__ density, const float* __restrict__ weights,
-                                                 const float* __restrict__ d_w_in,    // !COMPOSITE: [R,S]
-                                                 const float* __restrict__ upstream,  // optional device scalar
-                                                 const float* __restrict__ rgb,       // COMPOSITE: samples [N,3]
-                                                 const float* __restrict__ g_rgb,     // COMPOSITE: [R,3]
-                                                 const float* __restrict__ g_sem,     // COMPOSITE: [R]
-                                                 float* __restrict__ d_density, float* __restrict__ d_rgb,
-                                                 float* __restrict__ d_logit, const LossTargets& tg,
-                                                 const float* __restrict__ logit,     // SEMGRAD: samples [N]
-                                                 const float* __restrict__ bg = nullptr,   // BG: rows of 3, stride bg_stride
-                                                 int bg_stride = 0) {
-  static_assert(COMPOSITE || !SEMGRAD, "the semantic term belongs to the compositing backward");
-  static_assert(COMPOSITE || !(BG || SCALE), "background and gradient scaling belong to the compositing backward");
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long r = (long long)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const int E = (S + 63) >> 6;
-  const float* eb = euclid + r * (S + 1);
-  const float* dn = density + r * S;
-  const float* w = weights + r * S;
-  const float up = upstream ? upstream[0] : 1.0f;
-  float gr = 0.0f, gg = 0.0f, gb = 0.0f, gs = 0.0f, l0 = 0.0f, l1 = 0.0f, l2 = 0.0f, bgw = 0.0f;
-  if (COMPOSITE) {
-    if constexpr (TARGETS) {
-      const float inv3r = 1.0f / (float)(3 * R), invr = 1.0f / (float)R;   // (k_train_losses, rgb / semantic role)
-      const float d0 = tg.out_rgb[3 * r] - tg.image[3 * r], d1 = tg.out_rgb[3 * r + 1] - tg.image[3 * r + 1],
-                  d2 = tg.out_rgb[3 * r + 2] - tg.image[3 * r + 2];
-      gr = mse_grad(d0, inv3r);
-      gg = mse_grad(d1, inv3r);
-      gb = mse_grad(d2, inv3r);
-      gs = bce_logit_grad(tg.out_sem[r], tg.mask[r], tg.sem_weight, invr);
-    } else {
-      gr = g_rgb[3 * r];
-      gg = g_rgb[3 * r + 1];
-      gb = g_rgb[3 * r + 2];
-      gs = g_sem[r];
-    }
-    const float* cl = BG ? bg + r * bg_stride : rgb + (r * S + (S - 1)) * 3;
-    l0 = cl[0];
-    l1 = cl[1];
-    l2 = cl[2];
-  }
-  float delta[ME], gw[ME], wk[ME];
-  float dd_local = 0.0f, gww_local = 0.0f, wsum_local = 0.0f;
-#pragma unroll
-  for (int e = 0; e < ME; ++e) {
-    const int k = lane * E + e;
-    delta[e] = 0.0f;
-    gw[e] = 0.0f;
-    wk[e] = 0.0f;
-    if (e < E && k < S) {
-      delta[e] = eb[k + 1] - eb[k];
-      wk[e] = w[k];
-      if (COMPOSITE) {
-        const float* c = rgb + (r * S + k) * 3;
-        gw[e] = gr * (c[0] - l0) + gg * (c[1] - l1) + gb * (c[2] - l2);  // semantic weights are detached unless SEMGRAD
-        if constexpr (SEMGRAD) gw[e] += gs * logit[r * S + k];
-      } else {
-        gw[e] = d_w_in[r * S + k] * up;
-      }
-      dd_local += delta[e] * dn[k];
-      gww_local += gw[e] * wk[e];
-      wsum_local += wk[e];
-    }
-  }
-  float cum_dd = wave_excl_scan(dd_local, lane);     // sum_{j<first k of lane}
-  // sum_{i>k} g_i w_i as a true SUFFIX sum (reverse scan), not `total - prefix`: behind a surface the suffix is a sum of
-  // tiny terms while total and prefix agree to 7 digits, and dL/dsigma there is multiplied by sigma (up to e^15) in the
-  // trunc_exp backward — the cancellation error was comparable to the real gradient (autograd's cumsum backward is a
-  // reverse cumsum, i.e. exact in this sense).
-  float suffix =
-      padded_suffix<ME>(wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane));
-  if (COMPOSITE && !BG) bgw = 1.0f - wave_sum(wsum_local);
-  float suf[ME];   // suffix AFTER element e of this lane's chunk
-#pragma unroll
-  for (int e = ME - 1; e >= 0; --e) {
-    suf[e] = suffix;
-    suffix += gw[e] * wk[e];   // gw / wk are 0 for e >= E or k >= S
-  }
-#pragma unroll
-  for (int e = 0; e < ME; ++e) {
-    const int k = lane * E + e;
-    if (e < E && k < S) {
-      cum_dd += delta[e] * dn[k];   // inclusive of k
-      const float T_next = expf(-cum_dd);
-      float s = 1.0f;
-      if constexpr (SCALE) s = distance_squared_scale(eb[k], eb[k + 1]);
-      const auto leaving = [s](float g) { return SCALE ? s * g : g; };   // a gradient on its way to the field
-      d_density[r * S + k] = leaving(delta[e] * (gw[e] * T_next - suf[e]));
-      if (COMPOSITE) {
-        float f = wk[e];
-        if (!BG && k == S - 1) f += bgw;  // background = last sample's colour (RGBRenderer "last_sample")
-        float* o = d_rgb + (r * S + k) * 3;
-        o[0] = leaving(gr * f);
-        o[1] = leaving(gg * f);
-        o[2] = leaving(gb * f);
-        d_logit[r * S + k] = leaving(gs * wk[e]);
-      }
-    }
-  }
-}
-
-template <bool COMPOSITE, bool TARGETS = false, int ME = WB_MAXE>
-__global__ __launch_bounds__(256) void k_weights_bwd(long long R, int S, const float* __restrict__ euclid,
-                                                     const float* __restrict__ density,
-                                                     const float* __restrict__ weights,
-                                                     const float* __restrict__ d_w_in,    // !COMPOSITE: [R,S]
-                                                     const float* __restrict__ upstream,  // optional device scalar
-                                                     const float* __restrict__ rgb,       // COMPOSITE: samples [N,3]
-                                                     const float* __restrict__ g_rgb,     // COMPOSITE: [R,3]
-                                                     const float* __restrict__ g_sem,     // COMPOSITE: [R]
-                                                     float* __restrict__ d_density, float* __restrict__ d_rgb,
-                                                     float* __restrict__ d_logit, LossTargets tg = LossTargets{}) {
-  weights_bwd_body<COMPOSITE, TARGETS, false, false, false, ME>(R, S, euclid, density, weights, d_w_in, upstream, rgb, g_rgb, g_sem, d_density,
-                                              d_rgb, d_logit, tg, nullptr);
-}
-// fnr_composite_bwd_semgrad / fnr_composite_bwd_targets_semgrad: k_weights_bwd<true, TARGETS> with the semantic term
-template <bool TARGETS, int ME = WB_MAXE>
-__global__ __launch_bounds__(256) void k_weights_bwd_semgrad(long long R, int S, const float* __restrict__ euclid,
-                                                             const float* __restrict__ density,
-                                                             const float* __restrict__ weights, const float* __restrict__ rgb,
-                                                             const float* __restrict__ logit,     // samples [N]
-                                                             const float* __restrict__ g_rgb,     // !TARGETS: [R,3]
-                                                             const float* __restrict__ g_sem,     // !TARGETS: [R]
-                                                             float* __restrict__ d_density, float* __restrict__ d_rgb,
-                                                             float* __restrict__ d_logit, LossTargets tg) {
-  weights_bwd_body<true, TARGETS, true, false, false, ME>(R, S, euclid, density, weights, nullptr, nullptr, rgb, g_rgb, g_sem, d_density, d_rgb,
-                                        d_logit, tg, logit);
-}
-// fnr_composite_bwd_opt / fnr_composite_bwd_targets_opt with an explicit background and / or gradient scaling
-template <bool TARGETS, bool SEMGRAD, bool BG, bool SCALE>
-__global__ __launch_bounds__(256) void k_composite_bwd_opt(long long R, int S, const float* __restrict__ euclid,
-                                                           const float* __restrict__ density,
-                                                           const float* __restrict__ weights, const float* __restrict__ rgb,
-                                                           const float* __restrict__ logit,     // SEMGRAD: samples [N]
-                                                           const float* __restrict__ g_rgb,     // !TARGETS: [R,3]
-                                                           const float* __restrict__ g_sem,     // !TARGETS: [R]
-                                                           float* __restrict__ d_density, float* __restrict__ d_rgb,
-                                                           float* __restrict__ d_logit, LossTargets tg,
-                                                           const float* __restrict__ bg, int bg_stride) {
-  static_assert(BG || SCALE, "<last sample, no scaling> is k_weights_bwd / k_weights_bwd_semgrad");
-  weights_bwd_body<true, TARGETS, SEMGRAD, BG, SCALE>(R, S, euclid, density, weights, nullptr, nullptr, rgb, g_rgb, g_sem,
-                                                      d_density, d_rgb, d_logit, tg, logit, bg, bg_stride);
-}
-
-// k_composite_fwd (render.hip, training mode) followed by k_weights_bwd<true, true> for the same ray, in one wave: everything the
-// backward read back from memory (weights, composited colour and logit) stays in registers.
-template <bool SEMGRAD, bool BG = false, bool SCALE = false, int ME = WB_MAXE>  // see weights_bwd_body
-__device__ __forceinline__ void composite_fwd_bwd_body(RaysDev rays, int S, const float* __restrict__ euclid,
-                                                       const float* __restrict__ density, const float* __restrict__ rgb,
-                                                       const float* __restrict__ logit, const float* __restrict__ image,
-                                                       const float* __restrict__ mask, float sem_weight,
-                                                       float* __restrict__ weights, float* __restrict__ out_rgb,
-                                                       float* __restrict__ out_acc, float* __restrict__ out_depth,
-                                                       float* __restrict__ out_sem, long long* __restrict__ out_label,
-                                                       float* __restrict__ d_density, float* __restrict__ d_rgb,
-                                                       float* __restrict__ d_logit, const float* __restrict__ bg = nullptr,
-                                                       int bg_stride = 0) {
-  static_assert(ME <= WB_MAXE, "the forward and the backward chunk a ray the same way");
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long R = rays.n_rays;
-  const long long r = (long long)blockIdx.x * 4 + wave;
-  if (r >= R) return;
-  const int E = (S + 63) >> 6;
-  const float* eb = euclid + r * (S + 1);
-  const float* dn = density + r * S;
-  const float* cs = rgb + r * S * 3;
-  const float* lg = logit + r * S;
-  // ---- forward: k_composite_fwd with training = 1 -----------------------------------------------------------------------
-  float dd[ME];
-  float local = 0.0f;
-#pragma unroll
-  for (int e = 0; e < ME; ++e) {
-    const int k = lane * E + e;
-    dd[e] = 0.0f;
-    if (e < E && k < S) dd[e] = fmul(fsub(eb[k + 1], eb[k]), dn[k]);
-    local += dd[e];
-  }
-  float excl = wave_excl_scan(local, lane);
-  float w[ME];
-  float acc_l = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f, sm = 0.0f;
-#pragma unroll
-  for (int e = 0; e < ME; ++e) {
-    const int k = lane * E + e;
-    const float T = expf(-excl);
-    const float alpha = 1.0f - expf(-dd[e]);
-    w[e] = nan_to_num(alpha * T);
-    excl += dd[e];
-    if (e < E && k < S) {
-      weights[r * S + k] = w[e];
-      const float c0 = cs[3 * k], c1 = cs[3 * k + 1], c2 = cs[3 * k + 2];
-      acc_l += w[e];
-      cr = fmaf(w[e], c0, cr);
-      cg = fmaf(w[e], c1, cg);
-      cb = fmaf(w[e], c2, cb);
-      sm = fmaf(w[e], lg[k], sm);
-    } else {
-      w[e] = 0.0f;
-    }
-  }
-  float cw = wave_excl_scan(acc_l, lane);
-  int first = 0x7fffffff;
-#pragma unroll
-  for (int e = 0; e < ME; ++e) {
-    const int k = lane * E + e;
-    cw += w[e];
-    if (e < E && k < S && cw >= 0.5f && first == 0x7fffffff) first = k;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) first = min(first, __shfl_xor(first, d, 64));
-  if (first > S - 1) first = S - 1;
-  const float acc = wave_sum(acc_l);
-  cr = wave_sum(cr);
-  cg = wave_sum(cg);
-  cb = wave_sum(cb);
-  sm = wave_sum(sm);
-  // (every lane: the backward wants the composited colour; wave_sum leaves the same total in all of them)
-  const float* cl = BG ? bg + r * bg_stride : cs + 3 * (S - 1);
-  const float l0 = cl[0], l1 = cl[1], l2 = cl[2];
-  const float o0 = cr + l0 * (1.0f - acc), o1 = cg + l1 * (1.0f - acc), o2 = cb + l2 * (1.0f - acc);
-  if (lane == 0) {
-    out_rgb[3 * r] = o0;
-    out_rgb[3 * r + 1] = o1;
-    out_rgb[3 * r + 2] = o2;
-    out_acc[r] = acc;
-    out_sem[r] = sm;
-    if (out_label) out_label[r] = (fsub(1.0f / (1.0f + expf(-sm)), 0.9f) > 0.0f) ? 1 : 0;
-    out_depth[r] = fdiv(fadd(eb[first], eb[first + 1]), 2.0f);
-  }
-  // ---- backward: k_weights_bwd<true, true> --------------------------------------------------------------------------------
-  const float inv3r = 1.0f / (float)(3 * R), invr = 1.0f / (float)R;
-  const float gr = mse_grad(o0 - image[3 * r], inv3r), gg = mse_grad(o1 - image[3 * r + 1], inv3r),
-              gb = mse_grad(o2 - image[3 * r + 2], inv3r);
-  const float gs = bce_logit_grad(sm, mask[r], sem_weight, invr);
-  float delta[ME], gw[ME], wk[ME];
-  float dd_local = 0.0f, gww_local = 0.0f, wsum_local = 0.0f;
-#pragma unroll
-  for (int e = 0; e < ME; ++e) {
-    const int k = lane * E + e;
-    delta[e] = 0.0f;
-    gw[e] = 0.0f;
-    wk[e] = 0.0f;
-    if (e < E && k < S) {
-      delta[e] = eb[k + 1] - eb[k];
-      wk[e] = w[e];
-      const float* c = cs + 3 * k;
-      gw[e] = gr * (c[0] - l0) + gg * (c[1] - l1) + gb * (c[2] - l2);  // semantic weights are detached unless SEMGRAD
-      if constexpr (SEMGRAD) gw[e] += gs * lg[k];
-      dd_local += delta[e] * dn[k];
-      gww_local += gw[e] * wk[e];
-      wsum_local += wk[e];
-    }
-  }
-  float cum_dd = wave_excl_scan(dd_local, lane);
-  float suffix =
-      padded_suffix<ME>(wave_bcast_lane(wave_excl_scan(wave_bcast_lane(gww_local, 63 - lane), lane), 63 - lane));
-  const float bgw = 1.0f - wave_sum(wsum_local);
-  float suf[ME];
-#pragma unroll
-  for (int e = ME - 1; e >= 0; --e) {
-    suf[e] = suffix;
-    suffix += gw[e] * wk[e];
-  }
-#pragma unroll
-  for (int e = 0; e < ME; ++e) {
-    const int k = lane * E + e;
-    if (e < E && k < S) {
-      cum_dd += delta[e] * dn[k];
-      const float T_next = expf(-cum_dd);
-      float s = 1.0f;
-      if constexpr (SCALE) s = distance_squared_scale(eb[k], eb[k + 1]);
-      const auto leaving = [s](float g) { return SCALE ? s * g : g; };
-      d_density[r * S + k] = leaving(delta[e] * (gw[e] * T_next - suf[e]));
-      float f = wk[e];
-      if (!BG && k == S - 1) f += bgw;
-      float* o = d_rgb + (r * S + k) * 3;
-      o[0] = leaving(gr * f);
-      o[1] = leaving(gg * f);
-      o[2] = leaving(gb * f);
-      d_logit[r * S + k] = leaving(gs * wk[e]);
-    }
-  }
-}
-template <int ME = WB_MAXE>
-__global__ __launch_bounds__(256) void k_composite_fwd_bwd(RaysDev rays, int S, const float* __restrict__ euclid,
-    const float* __restrict__ density, const float* __restrict__ rgb, const float* __restrict__ logit,
-    const float* __restrict__ image, const float* __restrict__ mask, float sem_weight, float* __restrict__ weights,
-    float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth, float* __restrict__ out_sem,
-    long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit) {
-  composite_fwd_bwd_body<false, false, false, ME>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
-                          out_sem, out_label, d_density, d_rgb, d_logit);
-}
-template <int ME = WB_MAXE>
-__global__ __launch_bounds__(256) void k_composite_fwd_bwd_semgrad(RaysDev rays, int S, const float* __restrict__ euclid,
-    const float* __restrict__ density, const float* __restrict__ rgb, const float* __restrict__ logit,
-    const float* __restrict__ image, const float* __restrict__ mask, float sem_weight, float* __restrict__ weights,
-    float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth, float* __restrict__ out_sem,
-    long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit) {
-  composite_fwd_bwd_body<true, false, false, ME>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb, out_acc, out_depth,
-                         out_sem, out_label, d_density, d_rgb, d_logit);
-}
-// fnr_composite_fwd_bwd_targets_opt with an explicit background and / or gradient scaling
-template <bool SEMGRAD, bool BG, bool SCALE>
-__global__ __launch_bounds__(256) void k_composite_fwd_bwd_opt(RaysDev rays, int S, const float* __restrict__ euclid,
-    const float* __restrict__ density, const float* __restrict__ rgb, const float* __restrict__ logit,
-    const float* __restrict__ image, const float* __restrict__ mask, float sem_weight, float* __restrict__ weights,
-    float* __restrict__ out_rgb, float* __restrict__ out_acc, float* __restrict__ out_depth, float* __restrict__ out_sem,
-    long long* __restrict__ out_label, float* __restrict__ d_density, float* __restrict__ d_rgb, float* __restrict__ d_logit,
-    const float* __restrict__ bg, int bg_stride) {
-  static_assert(BG || SCALE, "<last sample, no scaling> is k_composite_fwd_bwd / k_composite_fwd_bwd_semgrad");
-  composite_fwd_bwd_body<SEMGRAD, BG, SCALE>(rays, S, euclid, density, rgb, logit, image, mask, sem_weight, weights, out_rgb,
-                                             out_acc, out_depth, out_sem, out_label, d_density, d_rgb, d_logit, bg, bg_stride);
-}
-
-// ---------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam incl. its L2 weight_decay, no amsgrad), whole arena in one launch; optionally zeroes grads
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_adam(float4* __restrict__ p, float4* __restrict__ g, float4* __restrict__ m,
@@ -1101,328 +738,6 @@ extern "C" int fnr_distortion(int64_t n_rays, int S, const float* spacing, const
   FNR_PROF(OP_DISTORTION, n_rays * (long long)S);
   hipLaunchKernelGGL(k_distortion, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
                      (long long)n_rays, S, spacing, weights, out);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_composite_bwd(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
-                                 const float* rgb, const float* weights, const float* g_rgb, const float* g_semantics,
-                                 float* d_density, float* d_rgb, float* d_logit, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_composite_bwd");
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && weights && g_rgb && g_semantics && d_density && d_rgb &&
-                    d_logit,
-                "composite_bwd: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
-  with_lane_elems(S, [&](auto me) {
-    hipLaunchKernelGGL((k_weights_bwd<true, false, decltype(me)::value>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                       (long long)rays->n_rays, S, euclid_bins, density, weights, (const float*)nullptr,
-                       (const float*)nullptr, rgb, g_rgb, g_semantics, d_density, d_rgb, d_logit);
-  });
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_composite_bwd_targets(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
-                                         const float* rgb, const float* weights, const float* out_rgb, const float* image,
-                                         const float* out_semantics, const float* mask, float semantic_loss_weight,
-                                         float* d_density, float* d_rgb, float* d_logit, void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_bwd_targets", [=](const fnr_step_scalars*) {
-      return fnr_composite_bwd_targets(&rays_, S, euclid_bins, density, rgb, weights, out_rgb, image, out_semantics, mask,
-                                       semantic_loss_weight, d_density, d_rgb, d_logit, stream);
-    });
-  }
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && weights && out_rgb && image && out_semantics && mask && d_density &&
-                    d_rgb && d_logit,
-                "composite_bwd_targets: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_targets: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
-  const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
-  with_lane_elems(S, [&](auto me) {
-    hipLaunchKernelGGL((k_weights_bwd<true, true, decltype(me)::value>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                       (long long)rays->n_rays, S, euclid_bins, density, weights, (const float*)nullptr,
-                       (const float*)nullptr, rgb, (const float*)nullptr, (const float*)nullptr, d_density, d_rgb, d_logit, tg);
-  });
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-// fnr_composite_fwd (training) and fnr_composite_bwd_targets as ONE launch (ABI 13): a wave composites its ray and, with the
-// outputs still in registers, forms the per-ray loss gradients and runs the backward — the same operations on the same values in
-// the same order as the two kernels (tests/test_gpu_training_parity.py: bit-identical), one launch ramp less on the chain
-// forward -> MLP backward of every training step.
-extern "C" int fnr_composite_fwd_bwd_targets(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
-                                             const float* rgb, const float* logit, const float* image, const float* mask,
-                                             float semantic_loss_weight, float* weights, float* out_rgb,
-                                             float* out_accumulation, float* out_depth, float* out_semantics,
-                                             int64_t* out_label, float* d_density, float* d_rgb, float* d_logit,
-                                             void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_fwd_bwd_targets", [=](const fnr_step_scalars*) {
-      return fnr_composite_fwd_bwd_targets(&rays_, S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights,
-                                           out_rgb, out_accumulation, out_depth, out_semantics, out_label, d_density, d_rgb,
-                                           d_logit, stream);
-    });
-  }
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && image && mask && weights && out_rgb && out_accumulation &&
-                    out_depth && out_semantics && d_density && d_rgb && d_logit,
-                "composite_fwd_bwd_targets: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_fwd_bwd_targets: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_FWD, rays->n_rays * (long long)S);
-  with_lane_elems(S, [&](auto me) {
-    hipLaunchKernelGGL(k_composite_fwd_bwd<decltype(me)::value>, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                       make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
-                       out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
-                       d_logit);
-  });
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-// ---- pass_semantic_gradients (fruit_nerf.py:56, 344-345): the three compositing backward calls with the semantic renderer's
-// weights NOT detached — d_density also carries g_sem * logit_k; d_rgb and d_logit are the parents' bit for bit.
-extern "C" int fnr_composite_bwd_semgrad(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
-                                         const float* rgb, const float* logit, const float* weights, const float* g_rgb,
-                                         const float* g_semantics, float* d_density, float* d_rgb, float* d_logit,
-                                         void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_composite_bwd_semgrad");
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && weights && g_rgb && g_semantics && d_density && d_rgb &&
-                    d_logit,
-                "composite_bwd_semgrad: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_semgrad: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
-  with_lane_elems(S, [&](auto me) {
-    hipLaunchKernelGGL((k_weights_bwd_semgrad<false, decltype(me)::value>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
-                       as_stream(stream), (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, g_rgb,
-                       g_semantics, d_density, d_rgb, d_logit, LossTargets{});
-  });
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_composite_bwd_targets_semgrad(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
-                                                 const float* rgb, const float* logit, const float* weights,
-                                                 const float* out_rgb, const float* image, const float* out_semantics,
-                                                 const float* mask, float semantic_loss_weight, float* d_density,
-                                                 float* d_rgb, float* d_logit, void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_bwd_targets_semgrad", [=](const fnr_step_scalars*) {
-      return fnr_composite_bwd_targets_semgrad(&rays_, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
-                                               out_semantics, mask, semantic_loss_weight, d_density, d_rgb, d_logit, stream);
-    });
-  }
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && weights && out_rgb && image && out_semantics && mask &&
-                    d_density && d_rgb && d_logit,
-                "composite_bwd_targets_semgrad: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_targets_semgrad: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
-  const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
-  with_lane_elems(S, [&](auto me) {
-    hipLaunchKernelGGL((k_weights_bwd_semgrad<true, decltype(me)::value>), dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                       (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, (const float*)nullptr,
-                       (const float*)nullptr, d_density, d_rgb, d_logit, tg);
-  });
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_composite_fwd_bwd_targets_semgrad(const fnr_rays* rays, int S, const float* euclid_bins,
-                                                     const float* density, const float* rgb, const float* logit,
-                                                     const float* image, const float* mask, float semantic_loss_weight,
-                                                     float* weights, float* out_rgb, float* out_accumulation,
-                                                     float* out_depth, float* out_semantics, int64_t* out_label,
-                                                     float* d_density, float* d_rgb, float* d_logit, void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_fwd_bwd_targets_semgrad", [=](const fnr_step_scalars*) {
-      return fnr_composite_fwd_bwd_targets_semgrad(&rays_, S, euclid_bins, density, rgb, logit, image, mask,
-                                                   semantic_loss_weight, weights, out_rgb, out_accumulation, out_depth,
-                                                   out_semantics, out_label, d_density, d_rgb, d_logit, stream);
-    });
-  }
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && image && mask && weights && out_rgb && out_accumulation &&
-                    out_depth && out_semantics && d_density && d_rgb && d_logit,
-                "composite_fwd_bwd_targets_semgrad: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_fwd_bwd_targets_semgrad: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_FWD, rays->n_rays * (long long)S);
-  with_lane_elems(S, [&](auto me) {
-    hipLaunchKernelGGL(k_composite_fwd_bwd_semgrad<decltype(me)::value>, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                       make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb,
-                       out_accumulation, out_depth, out_semantics, reinterpret_cast<long long*>(out_label), d_density, d_rgb,
-                       d_logit);
-  });
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-// ---- background_color / use_gradient_scaling (fnr_composite_options): the compositing backward calls once more, the options
-// in one struct.  {last sample, no scaling} is the entry point above (its launch, its name in a step program), with the
-// semantic weights detached or attached; the other six combinations of {semantic weights attached, explicit background,
-// scaling} are instantiations of the same bodies.  The selectors return NULL for a combination that is not built (0 and 4:
-// the callers have returned by then) and the entry points refuse it.
-static inline int composite_options_selector(const fnr_composite_options* o) {
-  return (o->semantic_gradients ? 4 : 0) | (o->background == FNR_BACKGROUND_EXPLICIT ? 2 : 0) | (o->gradient_scaling ? 1 : 0);
-}
-template <bool TARGETS>
-static auto composite_bwd_opt_kernel(const fnr_composite_options* o) {
-  decltype(&k_composite_bwd_opt<TARGETS, true, true, true>) kernel = nullptr;
-  switch (composite_options_selector(o)) {
-    case 1: kernel = k_composite_bwd_opt<TARGETS, false, false, true>; break;
-    case 2: kernel = k_composite_bwd_opt<TARGETS, false, true, false>; break;
-    case 3: kernel = k_composite_bwd_opt<TARGETS, false, true, true>; break;
-    case 5: kernel = k_composite_bwd_opt<TARGETS, true, false, true>; break;
-    case 6: kernel = k_composite_bwd_opt<TARGETS, true, true, false>; break;
-    case 7: kernel = k_composite_bwd_opt<TARGETS, true, true, true>; break;
-    default: break;
-  }
-  return kernel;
-}
-static auto composite_fwd_bwd_opt_kernel(const fnr_composite_options* o) {
-  decltype(&k_composite_fwd_bwd_opt<true, true, true>) kernel = nullptr;
-  switch (composite_options_selector(o)) {
-    case 1: kernel = k_composite_fwd_bwd_opt<false, false, true>; break;
-    case 2: kernel = k_composite_fwd_bwd_opt<false, true, false>; break;
-    case 3: kernel = k_composite_fwd_bwd_opt<false, true, true>; break;
-    case 5: kernel = k_composite_fwd_bwd_opt<true, false, true>; break;
-    case 6: kernel = k_composite_fwd_bwd_opt<true, true, false>; break;
-    case 7: kernel = k_composite_fwd_bwd_opt<true, true, true>; break;
-    default: break;
-  }
-  return kernel;
-}
-static inline bool composite_options_plain(const fnr_composite_options* o) {
-  return o->background == FNR_BACKGROUND_LAST_SAMPLE && !o->gradient_scaling;
-}
-#define FNR_CHECK_COMPOSITE_OPTIONS(what, o)                                                                             \
-  FNR_CHECK_ARG(composite_options_ok(o), what ": options NULL or background %d (0 = last sample, 1 = explicit with a "   \
-                "buffer of row stride 0 or 3)", (o) ? (int)(o)->background : -1)
-
-extern "C" int fnr_composite_bwd_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
-                                     const float* rgb, const float* logit, const float* weights, const float* g_rgb,
-                                     const float* g_semantics, const fnr_composite_options* opt, float* d_density,
-                                     float* d_rgb, float* d_logit, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_composite_bwd_opt");
-  FNR_CHECK_COMPOSITE_OPTIONS("composite_bwd_opt", opt);
-  if (composite_options_plain(opt))
-    return opt->semantic_gradients ? fnr_composite_bwd_semgrad(rays, S, euclid_bins, density, rgb, logit, weights, g_rgb,
-                                                               g_semantics, d_density, d_rgb, d_logit, stream)
-                                   : fnr_composite_bwd(rays, S, euclid_bins, density, rgb, weights, g_rgb, g_semantics,
-                                                       d_density, d_rgb, d_logit, stream);
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && (logit || !opt->semantic_gradients) && weights && g_rgb &&
-                    g_semantics && d_density && d_rgb && d_logit,
-                "composite_bwd_opt: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_opt: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
-  const auto kernel = composite_bwd_opt_kernel<false>(opt);
-  FNR_CHECK_ARG(kernel, "composite_bwd_opt: option combination %d is not built", composite_options_selector(opt));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
-                     as_stream(stream), (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit, g_rgb,
-                     g_semantics, d_density, d_rgb, d_logit, LossTargets{}, opt->background_rgb,
-                     (int)opt->background_stride);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_composite_bwd_targets_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
-                                             const float* rgb, const float* logit, const float* weights,
-                                             const float* out_rgb, const float* image, const float* out_semantics,
-                                             const float* mask, float semantic_loss_weight,
-                                             const fnr_composite_options* opt, float* d_density, float* d_rgb,
-                                             float* d_logit, void* stream) {
-  if (opt && composite_options_ok(opt) && composite_options_plain(opt))
-    return opt->semantic_gradients
-               ? fnr_composite_bwd_targets_semgrad(rays, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
-                                                   out_semantics, mask, semantic_loss_weight, d_density, d_rgb, d_logit, stream)
-               : fnr_composite_bwd_targets(rays, S, euclid_bins, density, rgb, weights, out_rgb, image, out_semantics, mask,
-                                           semantic_loss_weight, d_density, d_rgb, d_logit, stream);
-  if (seq::recording() && rays && opt) {
-    const fnr_rays rays_ = *rays;
-    const fnr_composite_options opt_ = *opt;
-    seq::push("fnr_composite_bwd_targets_opt", [=](const fnr_step_scalars*) {
-      return fnr_composite_bwd_targets_opt(&rays_, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
-                                           out_semantics, mask, semantic_loss_weight, &opt_, d_density, d_rgb, d_logit,
-                                           stream);
-    });
-  }
-  FNR_CHECK_COMPOSITE_OPTIONS("composite_bwd_targets_opt", opt);
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && (logit || !opt->semantic_gradients) && weights && out_rgb && image &&
-                    out_semantics && mask && d_density && d_rgb && d_logit,
-                "composite_bwd_targets_opt: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_bwd_targets_opt: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_BWD, rays->n_rays * (long long)S);
-  const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
-  const auto kernel = composite_bwd_opt_kernel<true>(opt);
-  FNR_CHECK_ARG(kernel, "composite_bwd_targets_opt: option combination %d is not built", composite_options_selector(opt));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
-                     as_stream(stream), (long long)rays->n_rays, S, euclid_bins, density, weights, rgb, logit,
-                     (const float*)nullptr, (const float*)nullptr, d_density, d_rgb, d_logit, tg, opt->background_rgb,
-                     (int)opt->background_stride);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_composite_fwd_bwd_targets_opt(const fnr_rays* rays, int S, const float* euclid_bins, const float* density,
-                                                 const float* rgb, const float* logit, const float* image, const float* mask,
-                                                 float semantic_loss_weight, const fnr_composite_options* opt,
-                                                 float* weights, float* out_rgb, float* out_accumulation, float* out_depth,
-                                                 float* out_semantics, int64_t* out_label, float* d_density, float* d_rgb,
-                                                 float* d_logit, void* stream) {
-  if (opt && composite_options_ok(opt) && composite_options_plain(opt))
-    return (opt->semantic_gradients ? fnr_composite_fwd_bwd_targets_semgrad : fnr_composite_fwd_bwd_targets)(
-        rays, S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb, out_accumulation,
-        out_depth, out_semantics, out_label, d_density, d_rgb, d_logit, stream);
-  if (seq::recording() && rays && opt) {
-    const fnr_rays rays_ = *rays;
-    const fnr_composite_options opt_ = *opt;
-    seq::push("fnr_composite_fwd_bwd_targets_opt", [=](const fnr_step_scalars*) {
-      return fnr_composite_fwd_bwd_targets_opt(&rays_, S, euclid_bins, density, rgb, logit, image, mask,
-                                               semantic_loss_weight, &opt_, weights, out_rgb, out_accumulation, out_depth,
-                                               out_semantics, out_label, d_density, d_rgb, d_logit, stream);
-    });
-  }
-  FNR_CHECK_COMPOSITE_OPTIONS("composite_fwd_bwd_targets_opt", opt);
-  FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && image && mask && weights && out_rgb && out_accumulation &&
-                    out_depth && out_semantics && d_density && d_rgb && d_logit,
-                "composite_fwd_bwd_targets_opt: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "composite_fwd_bwd_targets_opt: S %d out of range", S);
-  if (rays->n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_COMPOSITE_FWD, rays->n_rays * (long long)S);
-  const auto kernel = composite_fwd_bwd_opt_kernel(opt);
-  FNR_CHECK_ARG(kernel, "composite_fwd_bwd_targets_opt: option combination %d is not built", composite_options_selector(opt));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
-                     as_stream(stream), make_rays(rays), S, euclid_bins, density, rgb, logit, image, mask,
-                     semantic_loss_weight, weights, out_rgb, out_accumulation, out_depth, out_semantics,
-                     reinterpret_cast<long long*>(out_label), d_density, d_rgb, d_logit, opt->background_rgb,
-                     (int)opt->background_stride);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_weights_bwd(int64_t n_rays, int S, const float* euclid_bins, const float* density,
-                               const float* weights, const float* d_weights, const float* upstream,
-                               float* d_density, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_weights_bwd");
-  FNR_CHECK_ARG(euclid_bins && density && weights && d_weights && d_density, "weights_bwd: null argument");
-  FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "weights_bwd: S %d out of range", S);
-  if (n_rays == 0) return FNR_OK;
-  FNR_PROF(OP_WEIGHTS_BWD, n_rays * (long long)S);
-  with_lane_elems(S, [&](auto me) {
-    hipLaunchKernelGGL((k_weights_bwd<false, false, decltype(me)::value>), dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
-                       (long long)n_rays, S, euclid_bins, density, weights, d_weights, upstream, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, d_density, (float*)nullptr, (float*)nullptr);
-  });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }

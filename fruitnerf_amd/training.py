@@ -59,6 +59,24 @@ def _field_ray_grads(model, rctx, d_feats: Tensor, d_origins: Tensor, d_directio
     K.position_grad_reduce(fld.warp_struct(), rctx.rays, lv["euclid"], lv["S"], partial, d_origins, d_directions)
 
 
+def _composite_backward(rctx, semgrad: bool, *, given=None, targets=None):
+    """The compositing backward call of a render context's final level -> (d_density, d_rgb, d_logit).  Under the context's
+    composite_options (background_color / use_gradient_scaling of the forward pass) if it has them, else with the semantic
+    weights attached if `semgrad` (fruit_nerf.py:344-345); from `given` = (g_rgb, g_sem), the per-ray gradients, or from
+    `targets` = (out_rgb, image, out_sem, mask, sem_weight), the loss targets the kernel forms them from."""
+    opts = getattr(rctx, "composite_options", None)
+    lv = rctx.levels[-1]
+    suffix = "_opt" if opts is not None else "_semgrad" if semgrad else ""
+    fn = getattr(K, ("composite_bwd" if targets is None else "composite_bwd_targets") + suffix)
+    args = [rctx.rays, lv["S"], lv["euclid"], rctx.sample_density, rctx.sample_rgb]
+    if suffix:
+        args.append(rctx.sample_logit)          # (the two plain calls take no per-sample logits)
+    args += [rctx.weights, *(given if targets is None else targets)]
+    if opts is not None:
+        args.append(opts)
+    return fn(*args)
+
+
 class _RenderFn(torch.autograd.Function):
     """rays -> (rgb, semantics, accumulation, depth, prop depths); backward runs compositing-bwd,
     field-MLP-bwd (MFMA) and the hash-grid scatter."""
@@ -93,18 +111,7 @@ class _RenderFn(torch.autograd.Function):
         if g_sem is None:
             g_sem = torch.zeros(rays.n, 1, device=dev)
         semgrad = bool(model.config.pass_semantic_gradients)   # fruit_nerf.py:344-345: semantic weights not detached
-        opts = getattr(rctx, "composite_options", None)        # background_color / use_gradient_scaling of the forward pass
-        if opts is not None:
-            d_density, d_rgb, d_logit = K.composite_bwd_opt(rays, S, lv["euclid"], rctx.sample_density, rctx.sample_rgb,
-                                                            rctx.sample_logit, rctx.weights, g_rgb.contiguous(),
-                                                            g_sem.contiguous(), opts)
-        elif semgrad:
-            d_density, d_rgb, d_logit = K.composite_bwd_semgrad(rays, S, lv["euclid"], rctx.sample_density, rctx.sample_rgb,
-                                                                rctx.sample_logit, rctx.weights, g_rgb.contiguous(),
-                                                                g_sem.contiguous())
-        else:
-            d_density, d_rgb, d_logit = K.composite_bwd(rays, S, lv["euclid"], rctx.sample_density, rctx.sample_rgb,
-                                                        rctx.weights, g_rgb.contiguous(), g_sem.contiguous())
+        d_density, d_rgb, d_logit = _composite_backward(rctx, semgrad, given=(g_rgb.contiguous(), g_sem.contiguous()))
         fld = model.field
         net, gnet = fld.net_struct(), fld.net_struct(grads=True)
         want_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
@@ -1003,30 +1010,13 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
                 crosses_to(main, ray_sources)
                 if serialize_streams:
                     K.stream_wait_stream(main, side)
-        opts = getattr(rctx, "composite_options", None)    # background_color / use_gradient_scaling of the forward pass
         if getattr(rctx, "composite_grads", None) is not None:
             d_density, d_rgb_s, d_logit = rctx.composite_grads
-        elif opts is not None and losses_on_side:
-            d_density, d_rgb_s, d_logit = K.composite_bwd_targets_opt(
-                rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb, rctx.sample_logit, rctx.weights, outputs["rgb"],
-                image, outputs["semantics"], mask, cfg.semantic_loss_weight, opts)
-        elif opts is not None:
-            d_density, d_rgb_s, d_logit = K.composite_bwd_opt(rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb,
-                                                              rctx.sample_logit, rctx.weights, d_rgb, d_sem, opts)
-        elif losses_on_side and semgrad:
-            d_density, d_rgb_s, d_logit = K.composite_bwd_targets_semgrad(
-                rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb, rctx.sample_logit, rctx.weights, outputs["rgb"],
-                image, outputs["semantics"], mask, cfg.semantic_loss_weight)
         elif losses_on_side:
-            d_density, d_rgb_s, d_logit = K.composite_bwd_targets(rays, S, fin["euclid"], rctx.sample_density,
-                                                                  rctx.sample_rgb, rctx.weights, outputs["rgb"], image,
-                                                                  outputs["semantics"], mask, cfg.semantic_loss_weight)
-        elif semgrad:
-            d_density, d_rgb_s, d_logit = K.composite_bwd_semgrad(rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb,
-                                                                  rctx.sample_logit, rctx.weights, d_rgb, d_sem)
+            d_density, d_rgb_s, d_logit = _composite_backward(
+                rctx, semgrad, targets=(outputs["rgb"], image, outputs["semantics"], mask, cfg.semantic_loss_weight))
         else:
-            d_density, d_rgb_s, d_logit = K.composite_bwd(rays, S, fin["euclid"], rctx.sample_density, rctx.sample_rgb,
-                                                          rctx.weights, d_rgb, d_sem)
+            d_density, d_rgb_s, d_logit = _composite_backward(rctx, semgrad, given=(d_rgb, d_sem))
         fld = model.field
         net, gnet = fld.net_struct(), fld.net_struct(grads=True)
         d_pos = None

@@ -26,13 +26,13 @@ LDS_PER_CU = 160 * 1024
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    """{kernel symbol: {vgpr, agpr, spill, scratch, lds}} of every kernel of train.hip and sampler.hip, compiled with the
-    Makefile's flags (tests/test_isa_invariants.py reads its kernels' metadata the same way)."""
+    """{kernel symbol: {vgpr, agpr, spill, scratch, lds}} of every kernel of train.hip, composite_bwd.hip and sampler.hip, compiled
+    with the Makefile's flags (tests/test_isa_invariants.py reads its kernels' metadata the same way)."""
     if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
         pytest.skip("hipcc not available")
     tmp = tmp_path_factory.mktemp("per_ray")
     out = {}
-    for src in ("train.hip", "sampler.hip"):
+    for src in ("train.hip", "composite_bwd.hip", "sampler.hip"):
         asm = tmp / (src[:-4] + ".s")
         cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-ffp-contract=off",
                "-S", "--cuda-device-only", "-o", str(asm), os.path.join(CSRC, src)]
@@ -72,15 +72,18 @@ def test_train_losses_eight_wide_form_does_not_spill(kernels):
     assert _clean(_one(kernels, "_ZN3fnr14k_train_lossesILi8EEE"))
 
 
-@pytest.mark.parametrize("mangled", [
-    "_ZN3fnr19k_composite_fwd_bwdILi1EEE",              # a default step's fused forward + backward
-    "_ZN3fnr13k_weights_bwdILb1ELb0ELi1EEE",            # fnr_composite_bwd
-    "_ZN3fnr13k_weights_bwdILb1ELb1ELi1EEE",            # fnr_composite_bwd_targets
-    "_ZN3fnr13k_weights_bwdILb0ELb0ELi1EEE",            # fnr_weights_bwd
-    "_ZN3fnr27k_composite_fwd_bwd_semgradILi1EEE",
-    "_ZN3fnr21k_weights_bwd_semgradILb0ELi1EEE",
-    "_ZN3fnr21k_weights_bwd_semgradILb1ELi1EEE",
-])
+def _compositing_backward_forms(me):
+    """Mangled prefixes of the compositing / weights backward family at `me` samples per lane: k_weights_bwd (fnr_weights_bwd),
+    k_composite_bwd<TARGETS, SEMGRAD, BG, SCALE> (the six standalone entry points) and k_composite_fwd_bwd<SEMGRAD, BG, SCALE>
+    (the three fused ones; <0, 0, 0> is a default step's) — every combination of the switches."""
+    b = "01"
+    forms = [f"_ZN3fnr13k_weights_bwdILi{me}EEE"]
+    forms += [f"_ZN3fnr15k_composite_bwdILb{t}ELb{sg}ELb{bg}ELb{sc}ELi{me}EEE" for t in b for sg in b for bg in b for sc in b]
+    forms += [f"_ZN3fnr19k_composite_fwd_bwdILb{sg}ELb{bg}ELb{sc}ELi{me}EEE" for sg in b for bg in b for sc in b]
+    return forms
+
+
+@pytest.mark.parametrize("mangled", _compositing_backward_forms(1))
 def test_compositing_backward_at_one_sample_per_lane_is_one_generation(kernels, mangled):
     m = _one(kernels, mangled)
     assert _clean(m) and m["vgpr"] <= 128 and m["lds"] == 0, m
@@ -88,8 +91,7 @@ def test_compositing_backward_at_one_sample_per_lane_is_one_generation(kernels, 
 
 @pytest.mark.parametrize("me", [2, 4, 8])
 def test_wider_compositing_backward_forms_do_not_spill(kernels, me):
-    for mangled in (f"_ZN3fnr19k_composite_fwd_bwdILi{me}EEE", f"_ZN3fnr13k_weights_bwdILb1ELb0ELi{me}EEE",
-                    f"_ZN3fnr13k_weights_bwdILb1ELb1ELi{me}EEE", f"_ZN3fnr13k_weights_bwdILb0ELb0ELi{me}EEE"):
+    for mangled in _compositing_backward_forms(me):
         assert _clean(_one(kernels, mangled)), mangled
 
 
