@@ -452,6 +452,8 @@ def export_compact(lat: Optional[LatticeArg], ray_begin: int, n_rays: int, posit
     lib = L.load()
     dev = density.device
     N = density.numel()
+    if N == 0:
+        return      # an empty batch appends nothing (its tensors have no storage: the C entry point would see NULLs)
     ws = _empty(lib.fnr_export_workspace_bytes(N), dtype=torch.uint8, device=dev)
     cap = points[0].shape[0]
     assert all(p.shape[0] == cap for p in points) and all(c.shape[0] == cap for c in colors)

@@ -16,6 +16,7 @@ import torch
 from .. import _kernels as K
 
 SET_NAMES = ("semantic_colormap", "semantic", "density")
+INITIAL_CAPACITY = 1 << 20   # rows per stream buffer a sample_volume call starts with (read at call time; doubled on overflow)
 
 
 def _ensure_buffers(state, dev):
@@ -70,7 +71,7 @@ def sample_volume(pipeline, num_points: int, output_dir: Optional[Path] = None, 
     dm = pipeline.datamanager
     pts = {k: [] for k in SET_NAMES}
     cols = {k: [] for k in SET_NAMES}
-    state = {"cap": 1 << 20}
+    state = {"cap": INITIAL_CAPACITY}
     lattice = getattr(dm, "export_lattice", None)
     lat = None
     smp = getattr(model, "proposal_sampler", None)

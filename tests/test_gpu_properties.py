@@ -364,22 +364,32 @@ def test_train_prologue_is_the_separate_launches(dev):
         assert torch.equal(out["spacing"], spacing) and torch.equal(out["euclid"], euclid)
 
 
-@pytest.mark.parametrize("shape,span", [((11, 11), 1.0), ((64, 75), 1.0), ((64, 75), 0.55), ((203, 131), 1.0)])
-def test_image_metrics_kernel_matches_the_float64_oracle(dev, shape, span):
-    """fnr_image_metrics (csrc/image_metrics.hip) on synthetic images with structure (smooth ramps + noise, a prediction
-    with out-of-range values so that the clamp matters, saturated and near-zero logits): SSIM within 1e-5 and PSNR within
-    1e-4 dB of the float64 restatement of torchmetrics' algorithm, both IoUs exact; (11, 11) is the smallest image with an
-    SSIM value (one window), the others have ragged 32 x 32 tiles.  span < 1: both images squeezed into [0.2, 0.2 + span] —
-    the reference passes no data_range, so torchmetrics derives c1 / c2 from the images' own value range."""
-    import numpy as np
-    from fruitnerf_amd import _kernels as K
-    from oracle import image_metrics as oim
-    H, W = shape
+def _image_metrics_pair(H, W):
+    """image, rgb and the generator (for the semantics and the mask) of the image-metrics tests."""
     g = torch.Generator().manual_seed(H * 1000 + W)
     yy, xx = torch.meshgrid(torch.linspace(0, 1, H), torch.linspace(0, 1, W), indexing="ij")
     image = torch.stack([0.5 + 0.4 * torch.sin(6 * xx + 2 * yy), yy * xx, 0.3 + 0.2 * torch.cos(9 * yy)], dim=-1)
     image = (image + 0.05 * torch.rand(H, W, 3, generator=g)).clamp(0, 1)
     rgb = image + 0.15 * torch.randn(H, W, 3, generator=g)          # leaves [0, 1]: the metrics see clamp(rgb)
+    return image, rgb, g
+
+
+@pytest.mark.parametrize("shape,span", [((11, 11), 1.0), ((64, 75), 1.0), ((64, 75), 0.55), ((203, 131), 1.0),
+                                        ((520, 515), 1.0)])
+def test_image_metrics_kernel_matches_the_float64_oracle(dev, shape, span):
+    """fnr_image_metrics (csrc/image_metrics.hip) on synthetic images with structure (smooth ramps + noise, a prediction
+    with out-of-range values so that the clamp matters, saturated and near-zero logits): SSIM within 1e-5 and PSNR within
+    1e-4 dB of the float64 restatement of torchmetrics' algorithm, both IoUs exact; (11, 11) is the smallest image with an
+    SSIM value (one window), the others have ragged 32 x 32 tiles.  span < 1: both images squeezed into [0.2, 0.2 + span] —
+    the reference passes no data_range, so torchmetrics derives c1 / c2 from the images' own value range.
+    (520, 515): 267 800 pixels = 1047 blocks of 256, over pixel_blocks()'s cap of 1024, so the grid-stride loops of
+    k_image_range and k_image_pixels take a second trip; 3 * 16 * 16 = 768 SSIM tiles, so k_image_finish's 256 threads
+    stride three times over the partials; 3 column blocks.  The float64 oracle takes about 0.5 s at that size."""
+    import numpy as np
+    from fruitnerf_amd import _kernels as K
+    from oracle import image_metrics as oim
+    H, W = shape
+    image, rgb, g = _image_metrics_pair(H, W)
     if span != 1.0:
         image, rgb = 0.2 + span * image, 0.2 + span * rgb.clamp(0, 1)
     sem = 8.0 * torch.randn(H, W, 1, generator=g)
@@ -396,6 +406,42 @@ def test_image_metrics_kernel_matches_the_float64_oracle(dev, shape, span):
     # without semantics: only the image sums
     sums2 = K.image_metrics(rgb.to(dev), image.to(dev)).tolist()
     assert sums2[0] == sums[0] and sums2[1] == sums[1] and sums2[2:6] == [0.0, 0.0, 0.0, 0.0]
+
+
+def test_image_metrics_one_bad_tile_past_the_first_grid_trip_is_seen(dev):
+    """The means of the (520, 515) case could hide one dropped tile or a dropped grid-stride trip: here a 32 x 32 block of the
+    prediction, all channels, is off by +0.5 before the clamp.  The block is the SSIM tile (15, 7) — pixel rows 485..516,
+    columns 229..260 — whose partials have the indices 247, 503 and 759 (channels 0, 1, 2: two of them past
+    k_image_finish's first 256), and whose rows 510..516 are pixels past 1024 * 256 = 262 144, the second trip of
+    k_image_pixels and k_image_range.  (Only rows 510..519 of this image lie past the first trip, so no 32-row block can lie
+    there whole.)  Against the float64 oracle on the same pair SSIM and PSNR keep the 1e-5 and 1e-4 dB of the test above,
+    while the oracle's own values move by more than 10 and 1000 times that; PSNR without the second trip's pixels would be
+    off by more than 0.1 dB."""
+    import numpy as np
+    from fruitnerf_amd import _kernels as K
+    from oracle import image_metrics as oim
+    H, W = 520, 515
+    image, rgb, g = _image_metrics_pair(H, W)
+    sem = 8.0 * torch.randn(H, W, 1, generator=g)
+    mask = (torch.rand(H, W, 1, generator=g) > 0.6).float()
+    ty, tx = 15, 7
+    y0, x0 = 32 * ty + 5, 32 * tx + 5
+    assert y0 + 32 <= H - 3 and x0 + 32 <= W - 5 and (y0 + 31) * W + x0 > 1024 * 256 > y0 * W
+    assert min((c * 16 + ty) * 16 + tx for c in (1, 2)) > 256
+    bad = rgb.clone()
+    bad[y0:y0 + 32, x0:x0 + 32] += 0.5
+    clean = oim.image_metrics(rgb.numpy(), image.numpy(), sem.numpy(), mask.numpy())
+    want = oim.image_metrics(bad.numpy(), image.numpy(), sem.numpy(), mask.numpy())
+    assert abs(want["ssim"] - clean["ssim"]) > 1e-4 and abs(want["psnr"] - clean["psnr"]) > 0.1
+    err2 = (image.double() - bad.double().clamp(0, 1)).pow(2).reshape(-1, 3).sum(dim=1).numpy()
+    assert abs(-10.0 * np.log10(err2.sum() / (3 * H * W)) - want["psnr"]) < 1e-9
+    assert abs(10.0 * np.log10(err2[:1024 * 256].sum() / err2.sum())) > 0.1        # what a dropped second trip would cost
+    sums = K.image_metrics(bad.to(dev), image.to(dev), sem.to(dev)[..., 0], mask.to(dev)[..., 0]).tolist()
+    got = {"psnr": -10.0 * np.log10(sums[0] / sums[7]), "ssim": sums[1] / sums[6]}
+    print("[image metrics, one bad tile]", got, want, "unperturbed:", clean)
+    assert sums[6] == 3 * (H - 10) * (W - 10) and sums[7] == 3 * H * W
+    assert abs(got["ssim"] - want["ssim"]) <= 1e-5
+    assert abs(got["psnr"] - want["psnr"]) <= 1e-4
 
 
 @pytest.mark.parametrize("case", ["nan_in_render", "nan_in_image"])
