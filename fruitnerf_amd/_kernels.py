@@ -219,8 +219,24 @@ def sample_spaced(rays: RaysArg, spacing_kind: int, S: int, t_rand: Optional[Ten
     return spacing, euclid
 
 
+def edge_jitter(seed: int, offset: int, level: int, n_rays: int, n_edges: int, device, out: Optional[Tensor] = None) -> Tensor:
+    """use_single_jitter=False: [n_rays, n_edges] of U[0,1), the per-edge jitter of sampling `level` (0 = spaced sampler, 1.. =
+    PDF samplers) from the training prologue's generator (fnr_edge_jitter) — what fnr_train_prologue_edges and
+    fnr_weights_pdf_edges(draw) derive in their kernels on the same seed and offset."""
+    lib = L.load()
+    if out is None:
+        out = _empty(n_rays, n_edges, device=device)
+    L.check(lib.fnr_edge_jitter(int(seed) & ((1 << 64) - 1), int(offset) & ((1 << 64) - 1), int(level), n_rays, n_edges,
+                                L.ptr(out), L.stream_ptr(out.device)), "edge_jitter")
+    return out
+
+
 def weights_pdf(rays: RaysArg, spacing_kind: int, S_prev: int, S_new: int, density: Tensor, spacing_prev: Tensor,
-                euclid_prev: Tensor, anneal: float, rand: Optional[Tensor], want_depth: bool = True):
+                euclid_prev: Tensor, anneal: float, rand: Optional[Tensor], want_depth: bool = True,
+                per_edge: bool = False, draw: Optional[Tuple[int, int, int]] = None):
+    """rand: None (eval: centred u) or one number per ray, [R] / [R,1]; with per_edge (single_jitter=False,
+    fnr_weights_pdf_edges) one per new bin edge, [R, S_new+1], or None with draw = (seed, offset, level): the kernel draws
+    K.edge_jitter(seed, offset, level) itself."""
     lib = L.load()
     dev = rays.device
     weights = _empty(rays.n, S_prev, device=dev)
@@ -232,6 +248,16 @@ def weights_pdf(rays: RaysArg, spacing_kind: int, S_prev: int, S_new: int, densi
         spacing_new = _empty(rays.n, nb, device=dev)
         euclid_new = _empty(rays.n, nb, device=dev)
     rd = None if rand is None else _f32c(rand.reshape(-1))
+    if per_edge:
+        if rd is not None and rd.numel() != rays.n * (S_new + 1):
+            raise ValueError(f"rand has {rd.numel()} entries; expected {rays.n * (S_new + 1)} (per bin edge)")
+        seed, offset, level = draw if draw is not None else (0, 0, 0)
+        L.check(lib.fnr_weights_pdf_edges(rays.ref, spacing_kind, S_prev, S_new, L.ptr(density), L.ptr(spacing_prev),
+                                          L.ptr(euclid_prev), float(anneal), L.ptr(u_base), L.ptr(rd), L.ptr(weights),
+                                          L.ptr(depth), L.ptr(spacing_new), L.ptr(euclid_new),
+                                          int(seed) & ((1 << 64) - 1), int(offset) & ((1 << 64) - 1), int(level),
+                                          1 if draw is not None else 0, L.stream_ptr(dev)), "weights_pdf_edges")
+        return weights, depth, spacing_new, euclid_new
     L.check(lib.fnr_weights_pdf(rays.ref, spacing_kind, S_prev, S_new, L.ptr(density), L.ptr(spacing_prev),
                                 L.ptr(euclid_prev), float(anneal), L.ptr(u_base), L.ptr(rd), L.ptr(weights),
                                 L.ptr(depth), L.ptr(spacing_new), L.ptr(euclid_new), L.stream_ptr(dev)),
@@ -1138,16 +1164,17 @@ def camera_pose_grad_adam(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, 
 def train_prologue(image_set: ImageSetArg, train_ids: Tensor, n_rays: int, seed: int, offset: int,
                    pose_adjustment: Optional[Tensor], near: float, far: float, S0: int, n_jitter: int = 3,
                    spacing_kind: int = 1, cams: Optional[CameraTableArg] = None,
-                   pose_mode: int = L.FNR_POSE_SO3XR3) -> dict:
+                   pose_mode: int = L.FNR_POSE_SO3XR3, per_edge: bool = False) -> dict:
     """fnr_train_prologue: random numbers + camera adjust + pixel sampling + level-0 spaced sampling in one launch
-    (cams: rays through that camera table, fnr_train_prologue_cams; pose_mode: the exponential map of pose_adjustment)."""
+    (cams: rays through that camera table, fnr_train_prologue_cams; pose_mode: the exponential map of pose_adjustment;
+    per_edge: one jitter per level-0 bin edge drawn in the kernel, fnr_train_prologue_edges — no "jitter" rows)."""
     lib = L.load()
     dev = image_set.images.device
     R = int(n_rays)
     ids = train_ids.to(torch.int64).contiguous()
     n_train = ids.numel()
     out = {
-        "u": _empty(R, 3, device=dev), "jitter": _empty(n_jitter, R, device=dev),
+        "u": _empty(R, 3, device=dev), "jitter": None if per_edge else _empty(n_jitter, R, device=dev),
         "origins": _empty(R, 3, device=dev), "directions": _empty(R, 3, device=dev),
         "cam": _empty(R, dtype=torch.int32, device=dev), "image": _empty(R, 3, device=dev),
         "mask": _empty(R, device=dev), "spacing": _empty(R, S0 + 1, device=dev),
@@ -1156,6 +1183,14 @@ def train_prologue(image_set: ImageSetArg, train_ids: Tensor, n_rays: int, seed:
         "S0": S0, "near": float(near), "far": float(far), "spacing_kind": spacing_kind,
     }
     base = host_linspace(0.0, 1.0, S0 + 1, dev)
+    if per_edge:
+        L.check(lib.fnr_train_prologue_edges(
+            C.byref(image_set.c), _table_ref(cams, image_set), pose_mode, L.ptr(ids), n_train, R, int(seed) & (2 ** 64 - 1),
+            int(offset) & (2 ** 64 - 1), L.ptr(_f32c(pose_adjustment)) if pose_adjustment is not None else None,
+            L.ptr(out["c2w_adjusted"]), L.ptr(out["u"]), L.ptr(out["origins"]), L.ptr(out["directions"]), L.ptr(out["cam"]),
+            L.ptr(out["image"]), L.ptr(out["mask"]), float(near), float(far), spacing_kind, S0, L.ptr(base),
+            L.ptr(out["spacing"]), L.ptr(out["euclid"]), L.stream_ptr(dev)), "train_prologue_edges")
+        return out
     rest = (L.ptr(ids), n_train, R, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
             L.ptr(_f32c(pose_adjustment)) if pose_adjustment is not None else None,
             L.ptr(out["c2w_adjusted"]), L.ptr(out["u"]), L.ptr(out["jitter"]), n_jitter,

@@ -92,6 +92,8 @@ FNR_MAX_POSITION_SOURCES = 4         # fnr_position_grad_reduce_multi
 FNR_POSE_SO3XR3, FNR_POSE_SE3 = 0, 1     # pose_mode of the fnr_*_mode entry points (CameraOptimizerConfig.mode)
 POSE_MODES = {"SO3xR3": FNR_POSE_SO3XR3, "SE3": FNR_POSE_SE3}
 FNR_TRAIN_PROLOGUE_MAX_JITTER = 5    # fnr_train_prologue: n_jitter in 1..5
+FNR_EDGE_JITTER_MAX_LEVELS = 5       # fnr_edge_jitter / fnr_weights_pdf_edges: sampling levels 0..4
+FNR_EDGE_JITTER_MAX_EDGES = 262144   # ... and edges per ray and level
 FNR_TRAIN_LOSSES_ACCUM_FLOATS = 4 * FNR_LOSS_SLOTS + 33 * 32
 
 
@@ -235,6 +237,11 @@ SIGNATURES = {
     "fnr_camera_adjust_mode": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "fnr_train_prologue_mode": (_i, [P(fnr_image_set), P(fnr_camera_table), _i, _vp, _i, _i64, C.c_uint64, C.c_uint64, _vp,
                                      _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    "fnr_edge_jitter": (_i, [C.c_uint64, C.c_uint64, _i, _i64, _i, _vp, _vp]),
+    "fnr_train_prologue_edges": (_i, [P(fnr_image_set), P(fnr_camera_table), _i, _vp, _i, _i64, C.c_uint64, C.c_uint64, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    "fnr_weights_pdf_edges": (_i, [P(fnr_rays), _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                   C.c_uint64, _i, _i, _vp]),
     "fnr_camera_pose_grad_mode": (_i, [P(fnr_image_set), P(fnr_camera_table), _i, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp]),
     "fnr_camera_pose_grad_adam_mode": (_i, [P(fnr_image_set), P(fnr_camera_table), _i, _vp, _i, _i64, _vp, _vp, _vp, _vp,

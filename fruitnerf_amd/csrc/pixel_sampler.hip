@@ -6,6 +6,7 @@
 #include "camera_math.hpp"
 #include "sampler_math.hpp"
 #include "sequencer.hpp"
+#include "step_randoms.hpp"
 
 namespace fnr {
 
@@ -69,27 +70,7 @@ __global__ __launch_bounds__(256) void k_sample_pixels(ImageSetDev s, CameraTabl
 // Five launches of 4-7 us each before (random numbers for the pixels, camera adjust, pixel sampling, random numbers for
 // the sampler's jitter, level-0 spaced sampling), all latency: the random numbers come from a counter-based generator
 // (Philox4x32-10, Salmon et al. 2011; counter = (ray, word group, step offset), key = seed), so every role of the launch
-// derives the numbers it needs itself.
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0, c[1] = lo1, c[2] = n2, c[3] = lo0;
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-}
-__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-08f; }  // [0, 1), 24 bits
-// the step's random numbers of ray r: words 0-2 = (image, y, x) of the pixel, words 3-5 = the samplers' single jitters
-__device__ __forceinline__ void prologue_randoms(unsigned long long seed, unsigned long long offset, long long r, int group,
-                                                 float (&out)[4]) {
-  uint32_t c[4] = {(uint32_t)r, (uint32_t)((unsigned long long)r >> 32) ^ ((uint32_t)group << 24), (uint32_t)offset,
-                   (uint32_t)(offset >> 32)};
-  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-#pragma unroll
-  for (int i = 0; i < 4; ++i) out[i] = u01(c[i]);
-}
+// derives the numbers it needs itself (step_randoms.hpp).
 
 // background_color = "random" (fnr_random_background): the ray's background triple = words 0-2 of word group 2 of the step's
 // numbers — the prologue keeps groups 0 and 1, so drawing a background changes none of its numbers.
@@ -112,7 +93,7 @@ struct PrologueArgs {
   unsigned long long seed, offset;
   const float* pose;        // [n_train, 6] tangents of the kernel's MODE, or NULL (cameras as they are)
   float* c2w_adjusted;      // [n_train, 3, 4] out (with pose)
-  float *u, *jitter;        // [R, 3], [n_jitter, R] out
+  float *u, *jitter;        // [R, 3], [n_jitter, R] out (the per-edge form writes no jitter)
   int n_jitter;             // <= 5
   float *origins, *directions;
   int* cam_idx;
@@ -124,7 +105,9 @@ struct PrologueArgs {
   int nb_rays;              // workgroups of the per-ray role
 };
 
-template <bool CAMS, int MODE>
+// EDGES (use_single_jitter = False, fnr_train_prologue_edges): the per-ray role writes no jitter rows, and the level-0 role is
+// one thread per QUAD of bin edges — one Philox call gives the jitters of edges 4q .. 4q + 3 (step_randoms.hpp).
+template <bool CAMS, int MODE, bool EDGES = false>
 __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a, CameraTableDev cams) {
   if ((int)blockIdx.x < a.nb_rays) {
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -142,7 +125,8 @@ __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a, CameraTa
     const float rnd[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
 #pragma unroll
     for (int i = 0; i < 3; ++i) a.u[3 * r + i] = rnd[i];
-    for (int i = 0; i < a.n_jitter; ++i) a.jitter[(size_t)i * a.n_rays + r] = rnd[3 + i];
+    if constexpr (!EDGES)
+      for (int i = 0; i < a.n_jitter; ++i) a.jitter[(size_t)i * a.n_rays + r] = rnd[3 + i];
     // pixel sampling + ray generation: k_sample_pixels, with the ray's corrected camera formed in place
     int k = (int)(rnd[0] * (float)a.n_train);
     int y = (int)(rnd[1] * (float)a.set.H);
@@ -184,6 +168,27 @@ __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a, CameraTa
     a.mask[r] = (float)a.set.masks[pix];
     return;
   }
+  if constexpr (EDGES) {
+    // level-0 bins, one jitter per edge (k_sample_spaced with t_rand_per_bin on fnr_edge_jitter(level 0))
+    const int nq = (a.S0 + 4) >> 2;   // quads of S0 + 1 edges
+    const long long qidx = ((long long)blockIdx.x - a.nb_rays) * 256 + threadIdx.x;
+    if (qidx >= a.n_rays * (long long)nq) return;
+    const long long r = qidx / nq;
+    const int q = (int)(qidx - r * nq);
+    float t[4];
+    edge_jitter_quad(a.seed, a.offset, 0, r, q, t);
+    const float s_near = spacing_fn(a.kind, a.near), s_far = spacing_fn(a.kind, a.far);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = 4 * q + i;
+      if (j <= a.S0) {
+        const float b = spaced_bin_edge(a.base_bins, a.S0, j, true, t[i]);
+        a.spacing0[r * (a.S0 + 1) + j] = b;
+        a.euclid0[r * (a.S0 + 1) + j] = spacing_to_euclid(a.kind, b, s_near, s_far);
+      }
+    }
+    return;
+  }
   // level-0 bins of the proposal sampler (k_sample_spaced with one jitter per ray = word 3 of the ray's numbers)
   const long long idx = ((long long)blockIdx.x - a.nb_rays) * 256 + threadIdx.x;
   const long long total = a.n_rays * (long long)(a.S0 + 1);
@@ -196,6 +201,21 @@ __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a, CameraTa
   const float s_near = spacing_fn(a.kind, a.near), s_far = spacing_fn(a.kind, a.far);
   a.spacing0[idx] = b;
   a.euclid0[idx] = spacing_to_euclid(a.kind, b, s_near, s_far);
+}
+
+// fnr_edge_jitter: the numbers the per-edge forms draw, written out — one thread per quad of edges
+__global__ __launch_bounds__(256) void k_edge_jitter(unsigned long long seed, unsigned long long offset, int level,
+                                                     long long n_rays, int n_edges, float* __restrict__ out) {
+  const int nq = (n_edges + 3) >> 2;
+  const long long qidx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (qidx >= n_rays * (long long)nq) return;
+  const long long r = qidx / nq;
+  const int q = (int)(qidx - r * nq);
+  float t[4];
+  edge_jitter_quad(seed, offset, level, r, q, t);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (4 * q + i < n_edges) out[r * n_edges + 4 * q + i] = t[i];
 }
 
 // ---- full-image rays of ONE camera (fnr_camera_rays): rows [y0, y1) of its H x W pixels, one thread per pixel ----------
@@ -278,7 +298,8 @@ extern "C" int fnr_camera_rays(const float* c2w, const float* intrinsics, const 
 }
 
 // name: the entry point that was called, which is what a step program lists for the recorded call
-static int train_prologue(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
+// edges: the per-edge form (fnr_train_prologue_edges; jitter == NULL, n_jitter == 0)
+static int train_prologue(const char* name, bool edges, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
                           int pose_mode, const int64_t* train_ids,
                           int n_train, int64_t n_rays, uint64_t seed, uint64_t offset, const float* pose_adjustment,
                           float* c2w_adjusted, float* u, float* jitter, int n_jitter, float* origins, float* directions,
@@ -289,7 +310,7 @@ static int train_prologue(const char* name, const fnr_image_set* set, const fnr_
     const fnr_image_set set_ = *set;
     const fnr_camera_table cams_ = use_cams ? *cams : fnr_camera_table{nullptr, nullptr};
     seq::push(name, [=](const fnr_step_scalars* sc) {
-      return train_prologue(name, &set_, &cams_, use_cams, pose_mode, train_ids, n_train, n_rays, seed,
+      return train_prologue(name, edges, &set_, &cams_, use_cams, pose_mode, train_ids, n_train, n_rays, seed,
                             sc ? sc->prologue_offset : offset,
                             pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
                             fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
@@ -298,13 +319,15 @@ static int train_prologue(const char* name, const fnr_image_set* set, const fnr_
   FNR_CHECK_ARG(pose_mode == FNR_POSE_SO3XR3 || pose_mode == FNR_POSE_SE3, "train_prologue: pose_mode %d (0 = SO3xR3, 1 = SE3)",
                 pose_mode);
   FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "train_prologue_cams: null camera table");
-  FNR_CHECK_ARG(set && train_ids && u && jitter && origins && directions && camera_indices && image && fruit_mask &&
+  FNR_CHECK_ARG(set && train_ids && u && (jitter || edges) && origins && directions && camera_indices && image && fruit_mask &&
                     base_bins && spacing0 && euclid0,
                 "train_prologue: null argument");
   FNR_CHECK_ARG(set->images && set->masks && set->c2w && set->n_images > 0 && set->H > 0 && set->W > 0 && n_train > 0,
                 "train_prologue: bad image set");
-  FNR_CHECK_ARG(n_jitter >= 1 && n_jitter <= FNR_TRAIN_PROLOGUE_MAX_JITTER && S0 >= 1, "train_prologue: n_jitter %d (1..%d), S0 %d",
-                n_jitter, FNR_TRAIN_PROLOGUE_MAX_JITTER, S0);
+  FNR_CHECK_ARG(edges || (n_jitter >= 1 && n_jitter <= FNR_TRAIN_PROLOGUE_MAX_JITTER && S0 >= 1),
+                "train_prologue: n_jitter %d (1..%d), S0 %d", n_jitter, FNR_TRAIN_PROLOGUE_MAX_JITTER, S0);
+  FNR_CHECK_ARG(!edges || (S0 >= 1 && S0 < FNR_EDGE_JITTER_MAX_EDGES), "train_prologue_edges: S0 %d (1..%d)", S0,
+                FNR_EDGE_JITTER_MAX_EDGES - 1);
   FNR_CHECK_ARG((pose_adjustment == nullptr) == (c2w_adjusted == nullptr), "train_prologue: pose and c2w_adjusted go together");
   FNR_CHECK_ARG(n_rays >= n_train || !pose_adjustment, "train_prologue: fewer rays than cameras");
   if (n_rays == 0) return FNR_OK;
@@ -317,12 +340,17 @@ static int train_prologue(const char* name, const fnr_image_set* set, const fnr_
   a.near = near_plane, a.far = far_plane, a.kind = spacing_kind, a.S0 = S0, a.base_bins = base_bins;
   a.spacing0 = spacing0, a.euclid0 = euclid0;
   a.nb_rays = (int)((n_rays + 255) / 256);
-  const long long nb_bins = (n_rays * (long long)(S0 + 1) + 255) / 256;
+  // (per edge: one thread per quad of edges)
+  const long long nb_bins = ((edges ? n_rays * (long long)((S0 + 4) >> 2) : n_rays * (long long)(S0 + 1)) + 255) / 256;
   FNR_PROF(OP_SAMPLE_SPACED, n_rays * (long long)(S0 + 1));
   const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
-  const auto kernel = pose_mode == FNR_POSE_SE3
-                          ? (use_cams ? k_train_prologue<true, FNR_POSE_SE3> : k_train_prologue<false, FNR_POSE_SE3>)
-                          : (use_cams ? k_train_prologue<true, FNR_POSE_SO3XR3> : k_train_prologue<false, FNR_POSE_SO3XR3>);
+  const auto kernel =
+      edges ? (pose_mode == FNR_POSE_SE3
+                   ? (use_cams ? k_train_prologue<true, FNR_POSE_SE3, true> : k_train_prologue<false, FNR_POSE_SE3, true>)
+                   : (use_cams ? k_train_prologue<true, FNR_POSE_SO3XR3, true> : k_train_prologue<false, FNR_POSE_SO3XR3, true>))
+            : (pose_mode == FNR_POSE_SE3
+                   ? (use_cams ? k_train_prologue<true, FNR_POSE_SE3> : k_train_prologue<false, FNR_POSE_SE3>)
+                   : (use_cams ? k_train_prologue<true, FNR_POSE_SO3XR3> : k_train_prologue<false, FNR_POSE_SO3XR3>));
   hipLaunchKernelGGL(kernel, dim3((unsigned)(a.nb_rays + nb_bins)), dim3(256), 0, as_stream(stream), a, t);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
@@ -334,7 +362,7 @@ extern "C" int fnr_train_prologue(const fnr_image_set* set, const int64_t* train
                                   int32_t* camera_indices, float* image, float* fruit_mask, float near_plane,
                                   float far_plane, int spacing_kind, int S0, const float* base_bins, float* spacing0,
                                   float* euclid0, void* stream) {
-  return train_prologue("fnr_train_prologue", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, seed, offset,
+  return train_prologue("fnr_train_prologue", false, set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, seed, offset,
                         pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
                         fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
 }
@@ -346,7 +374,7 @@ extern "C" int fnr_train_prologue_cams(const fnr_image_set* set, const fnr_camer
                                        float* image, float* fruit_mask, float near_plane, float far_plane,
                                        int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
                                        void* stream) {
-  return train_prologue("fnr_train_prologue_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, seed, offset,
+  return train_prologue("fnr_train_prologue_cams", false, set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, seed, offset,
                         pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
                         fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
 }
@@ -358,9 +386,40 @@ extern "C" int fnr_train_prologue_mode(const fnr_image_set* set, const fnr_camer
                                        float* image, float* fruit_mask, float near_plane, float far_plane,
                                        int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
                                        void* stream) {
-  return train_prologue("fnr_train_prologue_mode", set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, seed,
+  return train_prologue("fnr_train_prologue_mode", false, set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, seed,
                         offset, pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices,
                         image, fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+}
+
+extern "C" int fnr_train_prologue_edges(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
+                                        const int64_t* train_ids, int n_train, int64_t n_rays, uint64_t seed, uint64_t offset,
+                                        const float* pose_adjustment, float* c2w_adjusted, float* u, float* origins,
+                                        float* directions, int32_t* camera_indices, float* image, float* fruit_mask,
+                                        float near_plane, float far_plane, int spacing_kind, int S0, const float* base_bins,
+                                        float* spacing0, float* euclid0, void* stream) {
+  return train_prologue("fnr_train_prologue_edges", true, set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, seed,
+                        offset, pose_adjustment, c2w_adjusted, u, nullptr, 0, origins, directions, camera_indices, image,
+                        fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+}
+
+extern "C" int fnr_edge_jitter(uint64_t seed, uint64_t offset, int level, int64_t n_rays, int n_edges, float* out,
+                               void* stream) {
+  if (seq::recording()) {
+    seq::push("fnr_edge_jitter", [=](const fnr_step_scalars* sc) {
+      return fnr_edge_jitter(seed, sc ? sc->prologue_offset : offset, level, n_rays, n_edges, out, stream);
+    });
+  }
+  FNR_CHECK_ARG(out && n_rays >= 0, "edge_jitter: null argument or negative ray count");
+  FNR_CHECK_ARG(level >= 0 && level < FNR_EDGE_JITTER_MAX_LEVELS, "edge_jitter: level %d (0..%d)", level,
+                FNR_EDGE_JITTER_MAX_LEVELS - 1);
+  FNR_CHECK_ARG(n_edges >= 1 && n_edges <= FNR_EDGE_JITTER_MAX_EDGES, "edge_jitter: n_edges %d (1..%d)", n_edges,
+                FNR_EDGE_JITTER_MAX_EDGES);
+  if (n_rays == 0) return FNR_OK;
+  const long long quads = n_rays * (long long)((n_edges + 3) >> 2);
+  hipLaunchKernelGGL(k_edge_jitter, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, as_stream(stream),
+                     (unsigned long long)seed, (unsigned long long)offset, level, (long long)n_rays, n_edges, out);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
 }
 
 extern "C" int fnr_random_background(uint64_t seed, uint64_t offset, int64_t n_rays, float* out, void* stream) {

@@ -6,6 +6,7 @@
 // dozens of small elementwise ops.
 #include "sampler_math.hpp"
 #include "sequencer.hpp"
+#include "step_randoms.hpp"
 
 namespace fnr {
 
@@ -34,22 +35,26 @@ static_assert(PDF_MAXE == RAY_MAX_LANE_ELEMS && PDF_MAX_PREV == 64 * PDF_MAXE, "
 // Everything the wave reads from memory is issued at the top — the resampling's inputs included, the previous level's bin
 // edges staged into LDS next to the CDF — so that a wave waits for memory once, not once per phase.  Six waves per SIMD (80
 // registers at most) keep a 4096-ray launch one resident generation of workgroups whatever ME.
-template <int ME>
-__global__ __launch_bounds__(256, 6) void k_weights_pdf(RaysDev rays, int kind, int S_prev, int S_new,
-                                                        const float* __restrict__ density,
-                                                        const float* __restrict__ spacing_prev,
-                                                        const float* __restrict__ euclid_prev, float anneal,
-                                                        const float* __restrict__ u_base, const float* __restrict__ rand,
-                                                        float* __restrict__ weights, float* __restrict__ median_depth,
-                                                        float* __restrict__ spacing_new, float* __restrict__ euclid_new) {
-  constexpr int CAP = 64 * ME;
-  __shared__ float s_cdf[4][CAP + 1];
-  __shared__ float s_ex[4][CAP + 1];
+// EDGES (use_single_jitter = False, fnr_weights_pdf_edges): one jitter per new bin edge instead of one per ray — read from
+// rand [R, S_new + 1], or with edges.draw drawn here from the step's generator (step_randoms.hpp: one Philox call per edge; a
+// wave's 64 lanes make their calls in one pass, so sharing a call among the four edges of a quad would save no instructions
+// below 256 edges and cost four cross-lane reads per pass; measured).  Only the resampling's `u` differs between
+// the two forms.
+struct EdgeDraw {
+  unsigned long long seed, offset;
+  int level, draw;
+};
+template <int ME, bool EDGES>
+__device__ __forceinline__ void weights_pdf_ray(float* cdf, float* ex, const RaysDev& rays, int kind, int S_prev, int S_new,
+                                                const float* __restrict__ density, const float* __restrict__ spacing_prev,
+                                                const float* __restrict__ euclid_prev, float anneal,
+                                                const float* __restrict__ u_base, const float* __restrict__ rand,
+                                                const EdgeDraw& edges, float* __restrict__ weights,
+                                                float* __restrict__ median_depth, float* __restrict__ spacing_new,
+                                                float* __restrict__ euclid_new) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long r = (long long)blockIdx.x * 4 + wave;
   if (r >= rays.n_rays) return;  // whole wave exits together
-  float* cdf = s_cdf[wave];
-  float* ex = s_ex[wave];
   const int E = (S_prev + 63) >> 6;
   const float* eb = euclid_prev + r * (S_prev + 1);
   const float* dn = density + r * S_prev;
@@ -57,6 +62,7 @@ __global__ __launch_bounds__(256, 6) void k_weights_pdf(RaysDev rays, int kind, 
 
   // ---- the resampling's inputs: asked for first, used last ------------------------------------------
   float near_r = 0.0f, far_r = 0.0f, rand_r = 0.0f, u0 = 0.0f, u1 = 0.0f;
+  [[maybe_unused]] float rand_1 = 0.0f;   // (EDGES: rand_r / rand_1 = the numbers of edges lane, lane + 64)
   float spv[ME + 1];
 #pragma unroll
   for (int q = 0; q <= ME; ++q) {
@@ -66,7 +72,17 @@ __global__ __launch_bounds__(256, 6) void k_weights_pdf(RaysDev rays, int kind, 
   if (S_new > 0) {
     near_r = rays.nears[r];
     far_r = rays.fars[r];
-    if (rand) rand_r = rand[r];
+    if constexpr (EDGES) {
+      if (rand) {
+        if (lane < nb) rand_r = rand[r * nb + lane];
+        if (lane + 64 < nb) rand_1 = rand[r * nb + lane + 64];
+      } else if (edges.draw) {   // drawn where the pointer form loads them, while the loads above are in flight
+        if (lane < nb) rand_r = edge_jitter(edges.seed, edges.offset, edges.level, r, lane);
+        if (lane + 64 < nb) rand_1 = edge_jitter(edges.seed, edges.offset, edges.level, r, lane + 64);
+      }
+    } else {
+      if (rand) rand_r = rand[r];
+    }
     if (lane < nb) u0 = u_base[lane];
     if (lane + 64 < nb) u1 = u_base[lane + 64];
   }
@@ -162,10 +178,17 @@ __global__ __launch_bounds__(256, 6) void k_weights_pdf(RaysDev rays, int kind, 
   __builtin_amdgcn_wave_barrier();
 
   // ---- inverse-CDF resampling ----------------------------------------------------------------------
-  const float u_shift = rand ? fdiv(rand_r, (float)nb) : (float)(1.0 / (2.0 * (double)nb));
+  const float u_centre = (float)(1.0 / (2.0 * (double)nb));
+  const float u_shift = EDGES ? u_centre : rand ? fdiv(rand_r, (float)nb) : u_centre;
   const float s_near = spacing_fn(kind, near_r), s_far = spacing_fn(kind, far_r);
   for (int jj = lane; jj < nb; jj += 64) {
-    const float u = fadd(jj == lane ? u0 : jj == lane + 64 ? u1 : u_base[jj], u_shift);
+    float shift = u_shift;
+    if constexpr (EDGES) {
+      if (rand || edges.draw)
+        shift = fdiv(jj == lane ? rand_r : jj == lane + 64 ? rand_1 : rand ? rand[r * nb + jj]
+                                 : edge_jitter(edges.seed, edges.offset, edges.level, r, jj), (float)nb);
+    }
+    const float u = fadd(jj == lane ? u0 : jj == lane + 64 ? u1 : u_base[jj], shift);
     // searchsorted(cdf, u, side="right"): number of entries <= u
     int lo = 0, hi = S_prev + 1;
     while (lo < hi) {
@@ -183,6 +206,39 @@ __global__ __launch_bounds__(256, 6) void k_weights_pdf(RaysDev rays, int kind, 
     spacing_new[r * nb + jj] = b;
     euclid_new[r * nb + jj] = spacing_to_euclid(kind, b, s_near, s_far);
   }
+}
+
+template <int ME>
+__global__ __launch_bounds__(256, 6) void k_weights_pdf(RaysDev rays, int kind, int S_prev, int S_new,
+                                                        const float* __restrict__ density,
+                                                        const float* __restrict__ spacing_prev,
+                                                        const float* __restrict__ euclid_prev, float anneal,
+                                                        const float* __restrict__ u_base, const float* __restrict__ rand,
+                                                        float* __restrict__ weights, float* __restrict__ median_depth,
+                                                        float* __restrict__ spacing_new, float* __restrict__ euclid_new) {
+  constexpr int CAP = 64 * ME;
+  __shared__ float s_cdf[4][CAP + 1];
+  __shared__ float s_ex[4][CAP + 1];
+  const int wave = threadIdx.x >> 6;
+  weights_pdf_ray<ME, false>(s_cdf[wave], s_ex[wave], rays, kind, S_prev, S_new, density, spacing_prev, euclid_prev, anneal,
+                             u_base, rand, EdgeDraw{}, weights, median_depth, spacing_new, euclid_new);
+}
+template <int ME>
+__global__ __launch_bounds__(256, 6) void k_weights_pdf_edges(RaysDev rays, int kind, int S_prev, int S_new,
+                                                              const float* __restrict__ density,
+                                                              const float* __restrict__ spacing_prev,
+                                                              const float* __restrict__ euclid_prev, float anneal,
+                                                              const float* __restrict__ u_base,
+                                                              const float* __restrict__ rand, EdgeDraw edges,
+                                                              float* __restrict__ weights, float* __restrict__ median_depth,
+                                                              float* __restrict__ spacing_new,
+                                                              float* __restrict__ euclid_new) {
+  constexpr int CAP = 64 * ME;
+  __shared__ float s_cdf[4][CAP + 1];
+  __shared__ float s_ex[4][CAP + 1];
+  const int wave = threadIdx.x >> 6;
+  weights_pdf_ray<ME, true>(s_cdf[wave], s_ex[wave], rays, kind, S_prev, S_new, density, spacing_prev, euclid_prev, anneal,
+                            u_base, rand, edges, weights, median_depth, spacing_new, euclid_new);
 }
 
 }  // namespace fnr
@@ -205,18 +261,28 @@ extern "C" int fnr_sample_spaced(const fnr_rays* rays, int spacing_kind, int S, 
   return FNR_OK;
 }
 
-extern "C" int fnr_weights_pdf(const fnr_rays* rays, int spacing_kind, int S_prev, int S_new, const float* density,
-                               const float* spacing_prev, const float* euclid_prev, float anneal, const float* u_base,
-                               const float* rand, float* weights, float* median_depth, float* spacing_new,
-                               float* euclid_new, void* stream) {
+// edges: NULL for fnr_weights_pdf (rand [R] or NULL), the generator's arguments of fnr_weights_pdf_edges otherwise (rand
+// [R, S_new + 1] or NULL)
+static int weights_pdf(const char* name, const EdgeDraw* edges, const fnr_rays* rays, int spacing_kind, int S_prev, int S_new,
+                       const float* density, const float* spacing_prev, const float* euclid_prev, float anneal,
+                       const float* u_base, const float* rand, float* weights, float* median_depth, float* spacing_new,
+                       float* euclid_new, void* stream) {
   if (seq::recording() && rays) {
     const fnr_rays rays_ = *rays;
-    seq::push("fnr_weights_pdf", [=](const fnr_step_scalars* sc) {
-      return fnr_weights_pdf(&rays_, spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev, sc ? sc->anneal : anneal,
-                             u_base, rand, weights, median_depth, spacing_new, euclid_new, stream);
+    const bool per_edge = edges != nullptr;
+    const EdgeDraw edges_ = per_edge ? *edges : EdgeDraw{};
+    seq::push(name, [=](const fnr_step_scalars* sc) {
+      EdgeDraw e = edges_;
+      if (sc && e.draw) e.offset = sc->prologue_offset;
+      return weights_pdf(name, per_edge ? &e : nullptr, &rays_, spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev,
+                         sc ? sc->anneal : anneal, u_base, rand, weights, median_depth, spacing_new, euclid_new, stream);
     });
   }
   FNR_CHECK_ARG(rays && density && euclid_prev && weights, "weights_pdf: null argument");
+  FNR_CHECK_ARG(!edges || !edges->draw ||
+                    (!rand && edges->level >= 1 && edges->level < FNR_EDGE_JITTER_MAX_LEVELS && S_new < FNR_EDGE_JITTER_MAX_EDGES),
+                "weights_pdf_edges: draw goes with rand == NULL, a level in 1..%d (level %d) and S_new below %d",
+                FNR_EDGE_JITTER_MAX_LEVELS - 1, edges->level, FNR_EDGE_JITTER_MAX_EDGES);
   FNR_CHECK_ARG(S_prev > 0 && S_prev <= PDF_MAX_PREV, "weights_pdf: S_prev %d out of range (1..%d)", S_prev,
                 PDF_MAX_PREV);
   FNR_CHECK_ARG(S_new == 0 || (spacing_prev && u_base && spacing_new && euclid_new),
@@ -225,10 +291,32 @@ extern "C" int fnr_weights_pdf(const fnr_rays* rays, int spacing_kind, int S_pre
   if (rays->n_rays == 0) return FNR_OK;
   FNR_PROF(OP_WEIGHTS_PDF, rays->n_rays * (long long)S_prev);
   with_lane_elems(S_prev, [&](auto me) {
-    hipLaunchKernelGGL(k_weights_pdf<decltype(me)::value>, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
-                       as_stream(stream), make_rays(rays), spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev,
-                       anneal, u_base, rand, weights, median_depth, spacing_new, euclid_new);
+    if (edges)
+      hipLaunchKernelGGL(k_weights_pdf_edges<decltype(me)::value>, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
+                         as_stream(stream), make_rays(rays), spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev,
+                         anneal, u_base, rand, *edges, weights, median_depth, spacing_new, euclid_new);
+    else
+      hipLaunchKernelGGL(k_weights_pdf<decltype(me)::value>, dim3((unsigned)((rays->n_rays + 3) / 4)), dim3(256), 0,
+                         as_stream(stream), make_rays(rays), spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev,
+                         anneal, u_base, rand, weights, median_depth, spacing_new, euclid_new);
   });
   FNR_LAUNCH_CHECK();
   return FNR_OK;
+}
+
+extern "C" int fnr_weights_pdf(const fnr_rays* rays, int spacing_kind, int S_prev, int S_new, const float* density,
+                               const float* spacing_prev, const float* euclid_prev, float anneal, const float* u_base,
+                               const float* rand, float* weights, float* median_depth, float* spacing_new,
+                               float* euclid_new, void* stream) {
+  return weights_pdf("fnr_weights_pdf", nullptr, rays, spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev, anneal,
+                     u_base, rand, weights, median_depth, spacing_new, euclid_new, stream);
+}
+
+extern "C" int fnr_weights_pdf_edges(const fnr_rays* rays, int spacing_kind, int S_prev, int S_new, const float* density,
+                                     const float* spacing_prev, const float* euclid_prev, float anneal, const float* u_base,
+                                     const float* rand, float* weights, float* median_depth, float* spacing_new,
+                                     float* euclid_new, uint64_t seed, uint64_t offset, int level, int draw, void* stream) {
+  const EdgeDraw edges{seed, offset, level, draw != 0 ? 1 : 0};
+  return weights_pdf("fnr_weights_pdf_edges", &edges, rays, spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev,
+                     anneal, u_base, rand, weights, median_depth, spacing_new, euclid_new, stream);
 }

@@ -212,7 +212,9 @@ class PixelBatcher:
         (fnr_train_prologue: counter-based random numbers, camera adjust, pixel sampling and the proposal sampler's
         level-0 bins); `last_presample` then holds what to hand to the model as RayBundle.presampled.  With
         level0["random_background"] (background_color="random") the rays' background colours are drawn behind the prologue
-        with its seed and offset (fnr_random_background) and travel as presampled["background"] [n_rays,3]."""
+        with its seed and offset (fnr_random_background) and travel as presampled["background"] [n_rays,3].  With
+        level0["per_edge"] (the sampler's single_jitter off) level 0 is jittered per bin edge (fnr_train_prologue_edges) and
+        `last_presample` carries per_edge, seed and offset — what the PDF levels' kernels draw from — instead of jitter rows."""
         d = self.data
         dev = d["images"].device
         if level0 is not None and dev.type == "cuda":
@@ -224,10 +226,15 @@ class PixelBatcher:
             self._offset = getattr(self, "_offset", 0) + 1
             out = K.train_prologue(self._set, self.image_ids, n_rays, self.gen.initial_seed(), self._offset, pose,
                                    level0["near"], level0["far"], level0["S"], n_jitter=level0.get("n_jitter", 3),
-                                   cams=self.camera_table(), pose_mode=pose_mode)
+                                   cams=self.camera_table(), pose_mode=pose_mode, per_edge=bool(level0.get("per_edge")))
             self.last_draw = {"u": out["u"], "cam": out["cam"], "c2w_adjusted": out["c2w_adjusted"]}
             self.last_presample = {"S0": out["S0"], "near": out["near"], "far": out["far"], "spacing": out["spacing"],
-                                   "euclid": out["euclid"], "jitter": [out["jitter"][i] for i in range(out["jitter"].shape[0])]}
+                                   "euclid": out["euclid"]}
+            if level0.get("per_edge"):
+                # one jitter per bin edge: the kernels of the PDF levels draw theirs from this seed and offset
+                self.last_presample.update(per_edge=True, seed=self.gen.initial_seed(), offset=self._offset)
+            else:
+                self.last_presample["jitter"] = [out["jitter"][i] for i in range(out["jitter"].shape[0])]
             if level0.get("random_background"):
                 self.last_presample["background"] = K.random_background(self.gen.initial_seed(), self._offset, n_rays, dev)
             return out["origins"], out["directions"], out["cam"][:, None], \

@@ -128,7 +128,9 @@ class HashMLPDensityField(nn.Module):
 
 
 class ProposalNetworkSampler(nn.Module):
-    """State of nerfstudio's ProposalNetworkSampler (fruit_nerf.py:151-158): anneal, update schedule."""
+    """State of nerfstudio's ProposalNetworkSampler (fruit_nerf.py:151-158): anneal, update schedule, and `single_jitter`
+    (fruit_nerf.py:149,155) — one stratified jitter number per ray and level, or (False, nerfstudio's default for this class)
+    one per bin edge.  A pass reads the attribute, not the config."""
 
     def __init__(self, num_proposal_samples_per_ray=(64,), num_nerf_samples_per_ray=32,
                  num_proposal_network_iterations=2, single_jitter=False, update_sched: Callable = lambda x: 1,
@@ -136,8 +138,7 @@ class ProposalNetworkSampler(nn.Module):
         super().__init__()
         if initial_sampler is not None:
             raise NotImplementedError("only the default piecewise initial sampler is built (fruit_nerf.py:140,157)")
-        if not single_jitter:
-            raise NotImplementedError("use_single_jitter=False is not built (Nerfacto default is True)")
+        self.single_jitter = bool(single_jitter)
         self.num_proposal_samples_per_ray = tuple(num_proposal_samples_per_ray)
         self.num_nerf_samples_per_ray = num_nerf_samples_per_ray
         self.num_proposal_network_iterations = num_proposal_network_iterations
@@ -152,6 +153,26 @@ class ProposalNetworkSampler(nn.Module):
     def step_cb(self, step):
         self._step = step
         self._steps_since_update += 1
+
+    def level_samples(self) -> Tuple[int, ...]:
+        """Samples per ray of every sampling level: the proposal levels, then the field's."""
+        n = self.num_proposal_network_iterations
+        return tuple(self.num_proposal_samples_per_ray[:n]) + (self.num_nerf_samples_per_ray,)
+
+    def check_jitter(self, jitter, n_rays: int) -> None:
+        """An explicit `jitter=` list of a training pass: per level [R] / [R,1] with single_jitter, [R, S_l + 1] without."""
+        counts = self.level_samples()
+        if len(jitter) != len(counts):
+            raise ValueError(f"jitter: {len(jitter)} tensors for {len(counts)} sampling levels")
+        for lvl, (j, S) in enumerate(zip(jitter, counts)):
+            if j is None:
+                continue
+            shape = tuple(j.shape)
+            if self.single_jitter and shape not in ((n_rays,), (n_rays, 1)):
+                raise ValueError(f"jitter[{lvl}] has shape {shape}; single_jitter=True expects ({n_rays},) or ({n_rays}, 1)")
+            if not self.single_jitter and shape != (n_rays, S + 1):
+                raise ValueError(f"jitter[{lvl}] has shape {shape}; single_jitter=False expects ({n_rays}, {S + 1}) "
+                                 "(one number per bin edge)")
 
     def updated_now(self) -> bool:
         return bool(self._steps_since_update > self.update_sched(self._step) or self._step < 10)
@@ -349,15 +370,16 @@ class FruitModel(nn.Module):
 
     def level0_spec(self) -> Optional[dict]:
         """What a datamanager needs to pre-sample the proposal sampler's level 0 in the launch that draws the rays
-        (PixelBatcher.sample(level0=...) -> RayBundle.presampled): training mode, piecewise spacing, single jitter."""
+        (PixelBatcher.sample(level0=...) -> RayBundle.presampled): training mode, piecewise spacing; "per_edge" (the sampler's
+        single_jitter off): one jitter per bin edge, drawn in the kernels of every level from the prologue's seed and offset."""
         sampler = self.proposal_sampler
         if not self.training or not isinstance(sampler, ProposalNetworkSampler):
             return None
-        if sampler.num_proposal_network_iterations + 1 > L.FNR_TRAIN_PROLOGUE_MAX_JITTER:
+        if sampler.num_proposal_network_iterations + 1 > min(L.FNR_TRAIN_PROLOGUE_MAX_JITTER, L.FNR_EDGE_JITTER_MAX_LEVELS):
             return None     # more jitters than fnr_train_prologue draws: the separate launches (torch.rand + sample_spaced)
         return {"S": sampler.num_proposal_samples_per_ray[0], "near": float(self.config.near_plane),
                 "far": float(self.config.far_plane), "n_jitter": sampler.num_proposal_network_iterations + 1,
-                "random_background": self.config.background_color == "random"}
+                "random_background": self.config.background_color == "random", "per_edge": not sampler.single_jitter}
 
     def _composite_options(self, ray_bundle: RayBundle, n_rays: int, dev) -> Optional["K.CompositeOptions"]:
         """background_color / use_gradient_scaling of one pass (fruit_nerf.py:164, 280-281, 322-323) as the `_opt` compositing
@@ -421,15 +443,24 @@ class FruitModel(nn.Module):
         updated = sampler.updated_now()
         jit = list(jitter) if jitter is not None else [None] * (n_prop + 1)
         S0 = sampler.num_proposal_samples_per_ray[0]
+        per_edge = training and not sampler.single_jitter     # (evaluation draws nothing: the same launches either way)
+        if training and jitter is not None:
+            sampler.check_jitter(jit, rays.n)
         # level 0 + the jitters may come with the rays (fnr_train_prologue drew them in the launch that sampled the
         # pixels): used when they match this sampler, the collider's planes and no explicit jitter was passed
         pre = getattr(ray_bundle, "presampled", None) if (training and jitter is None) else None
-        if pre is not None and not (pre.get("S0") == S0 and len(pre.get("jitter", ())) >= n_prop + 1
+        if pre is not None and not (pre.get("S0") == S0 and self._presample_matches(pre, per_edge, n_prop)
                                     and pre["spacing"].shape[0] == rays.n and pre.get("near") == float(cfg.near_plane)
                                     and pre.get("far") == float(cfg.far_plane)):
             pre = None
         if pre is not None:
-            jit = list(pre["jitter"][:n_prop + 1])
+            # (per edge: nothing travels — the PDF kernels draw their numbers from the prologue's seed and offset)
+            jit = [None] * (n_prop + 1) if per_edge else list(pre["jitter"][:n_prop + 1])
+        elif training and per_edge:
+            if any(j is None for j in jit):
+                sizes = [rays.n * (S_l + 1) for S_l in sampler.level_samples()]
+                fresh = torch.rand(sum(sizes), device=dev).split(sizes)  # one launch for all sampling levels
+                jit = [j if j is not None else fresh[i].view(rays.n, -1) for i, j in enumerate(jit)]
         elif training:
             if any(j is None for j in jit):
                 fresh = torch.rand(n_prop + 1, rays.n, device=dev)  # one launch for all sampling levels
@@ -444,7 +475,8 @@ class FruitModel(nn.Module):
             levels, spacing, euclid, S = list(ahead["levels"]), ahead["spacing"], ahead["euclid"], ahead["S"]
             self.__dict__["_ahead_used"] = self.__dict__.get("_ahead_used", 0) + 1   # (tests: the look-ahead is what ran)
         else:
-            levels, spacing, euclid, S = self._proposal_levels(rays, pre, jit, training and updated, sampler._anneal)
+            levels, spacing, euclid, S = self._proposal_levels(rays, pre, jit, training and updated, sampler._anneal,
+                                                               per_edge)
         if updated:
             sampler._steps_since_update = 0
         self._last_render_updated = bool(training and updated)   # did this pass keep the proposal nets' graph?
@@ -492,9 +524,19 @@ class FruitModel(nn.Module):
             outputs[f"prop_depth_{i}"] = levels[i]["depth"][:, None]
         return outputs, ctx
 
-    def _proposal_levels(self, rays, pre, jit, save_feats: bool, anneal: float):
+    @staticmethod
+    def _presample_matches(pre: dict, per_edge: bool, n_prop: int) -> bool:
+        """Was `pre` drawn in the sampler's jitter form?  Per ray it carries the levels' jitter rows, per edge the seed and
+        offset the kernels draw from."""
+        if bool(pre.get("per_edge", False)) != per_edge:
+            return False
+        return ("seed" in pre and "offset" in pre) if per_edge else len(pre.get("jitter") or ()) >= n_prop + 1
+
+    def _proposal_levels(self, rays, pre, jit, save_feats: bool, anneal: float, per_edge: bool = False):
         """ProposalNetworkSampler.generate_ray_samples: level-0 bins (taken from the prologue's `pre` when given), then
-        per proposal network density -> weights -> inverse-CDF bins of the next level -> (levels, spacing, euclid, S)."""
+        per proposal network density -> weights -> inverse-CDF bins of the next level -> (levels, spacing, euclid, S).
+        per_edge (single_jitter off, training): jit[l] is [R, S_l + 1]; with `pre` the PDF kernels draw level l's numbers
+        themselves from (pre["seed"], pre["offset"], l)."""
         cfg, sampler = self.config, self.proposal_sampler
         n_prop = sampler.num_proposal_network_iterations
         S = sampler.num_proposal_samples_per_ray[0]
@@ -505,8 +547,9 @@ class FruitModel(nn.Module):
             density, feats = K.prop_density_fwd(net.prop_struct(), net.warp_struct(), rays, euclid, S,
                                                 save_feats=save_feats)
             S_next = sampler.num_proposal_samples_per_ray[i + 1] if i + 1 < n_prop else sampler.num_nerf_samples_per_ray
+            draw = (pre["seed"], pre["offset"], i + 1) if (per_edge and pre is not None) else None
             weights, depth, spacing_n, euclid_n = K.weights_pdf(rays, 1, S, S_next, density, spacing, euclid,
-                                                                anneal, jit[i + 1])
+                                                                anneal, jit[i + 1], per_edge=per_edge, draw=draw)
             levels.append(dict(S=S, spacing=spacing, euclid=euclid, density=density, weights=weights, depth=depth,
                                feats=feats))
             spacing, euclid, S = spacing_n, euclid_n, S_next
@@ -531,15 +574,17 @@ class FruitModel(nn.Module):
         pre = ray_bundle.presampled
         cfg = self.config
         n_prop = sampler.num_proposal_network_iterations
+        per_edge = not sampler.single_jitter
         if pre is None or not (pre.get("S0") == sampler.num_proposal_samples_per_ray[0]
-                               and len(pre.get("jitter", ())) >= n_prop + 1
+                               and self._presample_matches(pre, per_edge, n_prop)
                                and pre["spacing"].shape[0] == ray_bundle.origins.shape[0]
                                and pre.get("near") == float(cfg.near_plane) and pre.get("far") == float(cfg.far_plane)):
             return False
         rays = K.RaysArg(ray_bundle.origins, ray_bundle.directions, ray_bundle.nears, ray_bundle.fars,
                          ray_bundle.camera_indices)
         updated, anneal = sampler.updated_after(step), self.anneal_at(step + 1)
-        levels, spacing, euclid, S = self._proposal_levels(rays, pre, list(pre["jitter"][:n_prop + 1]), updated, anneal)
+        jit = [None] * (n_prop + 1) if per_edge else list(pre["jitter"][:n_prop + 1])
+        levels, spacing, euclid, S = self._proposal_levels(rays, pre, jit, updated, anneal, per_edge)
         pre["ahead"] = dict(levels=levels, spacing=spacing, euclid=euclid, S=S, updated=updated, anneal=anneal,
                             param_version=self.lookahead_version())
         return True

@@ -59,7 +59,8 @@ class RayBundle:
     nears: Optional[Tensor] = None  # [R, 1]
     fars: Optional[Tensor] = None  # [R, 1]
     # Not a nerfstudio field: what fnr_train_prologue already produced for these rays in the launch that drew them
-    # (level-0 bins of the proposal sampler and the samplers' jitters; data/synthetic_apple.py::PixelBatcher.sample with
+    # (level-0 bins of the proposal sampler and the samplers' jitters — per ray, or with "per_edge" the seed and offset the
+    # later levels' kernels draw their per-edge numbers from; data/synthetic_apple.py::PixelBatcher.sample with
     # level0=).  FruitModel uses it when it matches its sampler configuration and ignores it otherwise.
     presampled: Optional[dict] = None
 

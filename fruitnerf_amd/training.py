@@ -1357,7 +1357,8 @@ class _StepProgram:
 
 class TrainingSteps:
     """The training loop's body for one model: batcher.sample -> fused_train_iteration, with the start of iteration
-    i + 1 — fnr_train_prologue (pixels, corrected cameras, rays, level-0 bins, jitters) and the proposal sampler's levels
+    i + 1 — fnr_train_prologue (pixels, corrected cameras, rays, level-0 bins, jitters; fnr_train_prologue_edges with the
+    sampler's single_jitter off, the PDF levels then drawing their per-edge numbers in their own kernels) and the proposal sampler's levels
     (FruitModel.sample_ahead) — enqueued at the END of iteration i, as soon as the proposal networks' and the cameras'
     optimiser steps are: with training.OVERLAP_PROPOSAL_BACKWARD on the second HIP stream, underneath the main table's
     scatter + optimiser step, which they do not depend on.  Same launches on the same values as sampling at the start
@@ -1465,7 +1466,9 @@ class TrainingSteps:
                 OVERLAP_PROPOSAL_BACKWARD, SERIALIZE_STREAMS, LOSSES_ON_SIDE, PAIR_PROPOSAL_LEVELS, FUSE_CAMERA_OPTIMIZER,
                 FUSE_WEIGHT_OPTIMIZER, FUSE_TABLE_OPTIMIZER, SPARSE_TOUCH_SKIPPING, STREAM_SAFE, FUSE_COMPOSITE_BACKWARD,
                 cfg.semantic_loss_weight, cfg.interlevel_loss_mult, cfg.near_plane, cfg.far_plane,
-                bool(cfg.pass_semantic_gradients), cfg.background_color, bool(cfg.use_gradient_scaling))
+                bool(cfg.pass_semantic_gradients), cfg.background_color, bool(cfg.use_gradient_scaling),
+                # (one jitter per ray or per bin edge: other prologue and PDF entry points, another program)
+                bool(getattr(model.proposal_sampler, "single_jitter", True)))
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def step(self, want_metrics: bool = True):
@@ -1495,8 +1498,11 @@ class TrainingSteps:
         if in_layout and self._next_layout[3] and model.training and SAMPLE_AHEAD and not L.profile_recording():
             ahead = self._next[1].presampled.get("ahead") if self._next[1].presampled else None
             updated = sampler.updated_now()
+            pre = self._next[1].presampled or {}
+            # (a look-ahead drawn before the sampler's single_jitter was flipped is the other form's: _render samples again)
             if ahead is not None and ahead["updated"] == updated and ahead["anneal"] == model.anneal_at(step) \
-                    and ahead.get("param_version") == model.lookahead_version():
+                    and ahead.get("param_version") == model.lookahead_version() \
+                    and bool(pre.get("per_edge", False)) == (not getattr(sampler, "single_jitter", True)):
                 # what the look-ahead of THIS step will see: sample_ahead() runs behind _render, which restarts the count
                 # of steps since the last update on a step that updates (ProposalNetworkSampler.updated_after)
                 since = 0 if updated else sampler._steps_since_update
@@ -1647,6 +1653,8 @@ class TrainingSteps:
             self.drop_programs()
             L.check(rc, "program_replay")
         rb, batch = prog.next
+        if rb.presampled.get("per_edge"):
+            rb.presampled["offset"] = batcher._offset       # what the replayed prologue and PDF kernels drew from
         ahead = rb.presampled["ahead"]
         ahead["anneal"] = anneal_next
         ahead["param_version"] = model.lookahead_version()

@@ -298,6 +298,43 @@ int fnr_weights_pdf(const fnr_rays* rays, int spacing_kind, int S_prev, int S_ne
                     const float* spacing_prev, const float* euclid_prev, float anneal, const float* u_base,
                     const float* rand, float* weights, float* median_depth, float* spacing_new, float* euclid_new, void* stream);
 
+/* ---- use_single_jitter = False: one stratified jitter per bin edge (fruit_nerf.py:149,155 pass the switch to
+ * ProposalNetworkSampler; components/ray_samplers.py:79-83: SpacedSampler t_rand [R,S+1], PDFSampler rand [R,S_new+1]) ---
+ * THE NUMBERS.  The jitter of edge j of ray r at sampling level l (0 = the spaced sampler, 1.. = the PDF samplers) is
+ *   u01(word (j & 3) of Philox4x32-10(counter, key)),
+ *   counter = (uint32 r, uint32(r >> 32) ^ ((3 + l) << 24) ^ ((j >> 2) << 8), uint32 offset, uint32(offset >> 32)),
+ *   key = (uint32 seed, uint32(seed >> 32)),  u01(x) = (x >> 8) * 2^-24,
+ * with seed and offset those of fnr_train_prologue.  Word groups 0 and 1 of the same (seed, offset) are the prologue's and
+ * group 2 is fnr_random_background's; levels 0..4 take groups 3..7.  A row has at most FNR_EDGE_JITTER_MAX_EDGES edges (the
+ * quad index stays below the group's bits).  Every kernel that consumes these numbers derives them itself. */
+#define FNR_EDGE_JITTER_MAX_LEVELS 5
+#define FNR_EDGE_JITTER_MAX_EDGES 262144
+/* out [n_rays, n_edges] = the numbers above for `level`: what torch.rand((R, S + 1)) is to the reference
+ * (components/ray_samplers.py:81-83, PDFSampler's rand likewise), for callers that hand them to fnr_sample_spaced
+ * (t_rand_per_bin) / fnr_weights_pdf_edges (rand) or to a comparand.  Recordable like fnr_random_background: a replayed call
+ * takes `offset` from fnr_step_scalars.prologue_offset. */
+int fnr_edge_jitter(uint64_t seed, uint64_t offset, int level, int64_t n_rays, int n_edges, float* out, void* stream);
+/* fnr_train_prologue_mode with one jitter per level-0 bin edge (SpacedSampler with single_jitter=False,
+ * components/ray_samplers.py:79-87): the arguments of fnr_train_prologue_mode without jitter / n_jitter.  Given u and
+ * fnr_edge_jitter(level 0, S0 + 1 edges), every output is bit-identical to fnr_camera_adjust_mode + fnr_sample_pixels[_cams] +
+ * fnr_sample_spaced(t_rand_per_bin = 1); u, rays, pixels and cameras are those of fnr_train_prologue_mode on the same seed
+ * and offset.  Recorded into step programs like the other prologues (offset from fnr_step_scalars.prologue_offset). */
+int fnr_train_prologue_edges(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode, const int64_t* train_ids,
+                             int n_train, int64_t n_rays, uint64_t seed, uint64_t offset, const float* pose_adjustment,
+                             float* c2w_adjusted, float* u, float* origins, float* directions, int32_t* camera_indices,
+                             float* image, float* fruit_mask, float near_plane, float far_plane, int spacing_kind, int S0,
+                             const float* base_bins, float* spacing0, float* euclid0, void* stream);
+/* fnr_weights_pdf with one jitter per new bin edge (PDFSampler with single_jitter=False: rand [R, S_new+1], u = u_base +
+ * rand / (S_new+1) per edge).  rand: [R, S_new+1] numbers of the caller, or NULL.  draw != 0 (requires rand == NULL and
+ * 1 <= level < FNR_EDGE_JITTER_MAX_LEVELS): the kernel draws fnr_edge_jitter(seed, offset, level) itself — the same bits as
+ * rand = that table.  rand == NULL and draw == 0: evaluation (centred u), the bits of fnr_weights_pdf(rand = NULL); seed,
+ * offset and level are then ignored.  Everything else is fnr_weights_pdf.  Recorded with fnr_step_scalars.anneal and, for
+ * draw != 0, offset from fnr_step_scalars.prologue_offset (the prologue of the same program drew the rays). */
+int fnr_weights_pdf_edges(const fnr_rays* rays, int spacing_kind, int S_prev, int S_new, const float* density,
+                          const float* spacing_prev, const float* euclid_prev, float anneal, const float* u_base,
+                          const float* rand, float* weights, float* median_depth, float* spacing_new, float* euclid_new,
+                          uint64_t seed, uint64_t offset, int level, int draw, void* stream);
+
 /* ---- proposal networks ---------------------------------------------------------------------- */
 /* HashMLPDensityField.density_fn at the S bin midpoints of every ray (fruit_nerf.py:111-129).
  * feat_save: optional [L][N][2] encoded features kept for fnr_prop_density_bwd. */
@@ -769,6 +806,7 @@ int fnr_adam_step_spans_dev(float* params, float* grads, float* exp_avg, float* 
  * fnr_field_mlp_fwd, fnr_composite_fwd, fnr_train_losses, fnr_composite_bwd_targets, fnr_field_mlp_bwd_adam,
  * fnr_composite_bwd_targets_semgrad, fnr_composite_fwd_bwd_targets_semgrad, fnr_field_mlp_bwd_semgrad (with weight_adam),
  * fnr_composite_fwd_opt, fnr_composite_bwd_targets_opt, fnr_composite_fwd_bwd_targets_opt, fnr_random_background,
+ * fnr_edge_jitter, fnr_train_prologue_edges, fnr_weights_pdf_edges,
  * fnr_hash_encode_bwd_adam, fnr_prop_density_bwd_pair(_split), fnr_position_grad_reduce_multi,
  * fnr_camera_pose_grad_adam and the stream operations below — run as usual AND append themselves (arguments by value,
  * host structs / host arrays copied) to the program; any other entry point that enqueues device work poisons the
@@ -777,7 +815,7 @@ int fnr_adam_step_spans_dev(float* params, float* grads, float* exp_avg, float* 
  * alive and unchanged in place for as long as it replays the program. */
 #define FNR_PROGRAM_ADAM_SLOTS 4
 typedef struct fnr_step_scalars {
-  uint64_t prologue_offset; /* fnr_train_prologue, fnr_random_background: `offset` (the step's random-number counter) */
+  uint64_t prologue_offset; /* fnr_train_prologue(_edges), fnr_random_background, fnr_edge_jitter, fnr_weights_pdf_edges(draw): `offset` (the step's random-number counter) */
   float anneal;             /* fnr_weights_pdf: `anneal` */
   int32_t reserved;
   struct {

@@ -8,6 +8,8 @@ Nothing here checks results: every knob is bit-identical by construction and cov
 usage: python tools/ab_quick.py [--method fruit_nerf] [--steps 200] [--pairs 3] knob=A,B [knob=A,B ...]
   knob = T.<NAME>        a module variable of fruitnerf_amd.training (values: 0 / 1 / int)
   knob = env.<NAME>      an environment variable (value `-` = unset)
+  knob = sampler.<NAME>  an attribute of the model's proposal sampler (sampler.single_jitter=1,0: one jitter per ray against
+                         one per bin edge — NOT bit-identical arms: other samples, the same work)
   several knobs switch together (arm A = every first value, arm B = every second)
   no knob: `pairs` windows of the default configuration (a library variant is selected with FNR_LIB_PATH outside)."""
 import argparse
@@ -24,8 +26,13 @@ import fruitnerf_amd.training as T  # noqa: E402
 from fruitnerf_amd.data import synthetic_apple as sa  # noqa: E402
 
 
+SAMPLER = None      # the run's ProposalNetworkSampler, once the model exists
+
+
 def set_knob(name, value):
-    if name.startswith("T."):
+    if name.startswith("sampler."):
+        setattr(SAMPLER, name[8:], type(getattr(SAMPLER, name[8:]))(int(value)))
+    elif name.startswith("T."):
         setattr(T, name[2:], type(getattr(T, name[2:]))(int(value)))
     elif name.startswith("env."):
         if value == "-":
@@ -51,6 +58,8 @@ def main():
     data = sa.render_dataset(scene, c2w, H=HW, W=HW, fx=focal, fy=focal)
     i_train, _ = bench.split_indices(bench.N_CAMERAS, bench.TRAIN_SPLIT)
     run = bench.MethodRun(args.method, "bf16x3", "SO3xR3", dev, 0, 1, data, torch.as_tensor(i_train, device=dev), len(i_train))
+    global SAMPLER
+    SAMPLER = run.model.proposal_sampler
     knobs = [(k.split("=")[0], k.split("=")[1].split(",")) for k in args.knobs]
     arms = ("A", "B") if knobs else ("A",)
     for name, vals in knobs:
