@@ -529,6 +529,26 @@ def distortion(S: int, spacing: Tensor, weights: Tensor, out: Optional[Tensor] =
     return slots.sum() if out is None else None
 
 
+def distortion_bwd(S: int, spacing: Tensor, euclid: Tensor, density: Tensor, weights: Tensor, mult: float,
+                   d_density: Tensor, upstream: Optional[Tensor] = None, gradient_scaling: bool = False,
+                   want_d_weights: bool = False) -> Optional[Tensor]:
+    """Backward of the distortion loss of the final level (fnr_distortion_bwd), IN PLACE on d_density [N]: the term's
+    d(loss)/d(density), scaled by clamp(midpoint^2, 0, 1) with gradient_scaling, is added to what the compositing backward
+    left there.  upstream: device scalar (None: 1).  -> d(loss)/d(weights) [R,S] if wanted, else None."""
+    lib = L.load()
+    dev = spacing.device
+    R = spacing.shape[0]
+    assert d_density.numel() == R * S and d_density.dtype == torch.float32, "d_density is float32 [N]"
+    d_w = _empty(R, S, device=dev) if want_d_weights else None
+    if R == 0:
+        return d_w
+    L.check(lib.fnr_distortion_bwd(R, S, L.ptr(spacing), L.ptr(euclid), L.ptr(density), L.ptr(weights), float(mult),
+                                   L.ptr(None if upstream is None else _f32c(upstream.reshape(1))),
+                                   1 if gradient_scaling else 0, L.ptr(d_w), L.ptr(d_density), L.stream_ptr(dev)),
+            "distortion_bwd")
+    return d_w
+
+
 def train_losses(rgb: Tensor, image: Tensor, semantics: Tensor, fruit_mask: Tensor, semantic_loss_weight: float,
                  S_f: int, spacing_f: Tensor, weights_f: Tensor, levels, interlevel_mult: float, want_distortion: bool,
                  accum: Tensor, fuse_weights_bwd: bool = False, want_ray_grads: bool = True):

@@ -160,6 +160,7 @@ SIGNATURES = {
     "fnr_losses_fwd": (_i, [_i64, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "fnr_interlevel_fwd": (_i, [_i64, _i, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     "fnr_distortion": (_i, [_i64, _i, _vp, _vp, _vp, _vp]),
+    "fnr_distortion_bwd": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp]),
     "fnr_composite_bwd": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fnr_composite_fwd_bwd_targets": (_i, [P(fnr_rays), _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp, _vp]),

@@ -135,9 +135,10 @@ __device__ __forceinline__ void composite_fwd_ray(long long r, int S, int lane, 
 //   dL/ds_k = d_k [ g_k T_{k+1} - sum_{i>k} g_i w_i ],  T_{k+1} = exp(-sum_{j<=k} d_j s_j)
 // from the wave scans to the stores, for a ray whose wave holds delta = the bin widths, gw = dL/dw_k, wk = the weights (all
 // zero beyond S) and the lane's sums of delta * density, gw * wk and wk.  COMPOSITE: d_rgb and d_logit too, from the per-ray
-// gradients (gr, gg, gb, gs).
+// gradients (gr, gg, gb, gs).  ACCUM (k_distortion_bwd): the finished (scaled) density term is ADDED to what d_density holds,
+// one float32 addition; false is the code it was.
 // ---------------------------------------------------------------------------------------------------
-template <bool COMPOSITE, bool BG, bool SCALE, int ME>
+template <bool COMPOSITE, bool BG, bool SCALE, int ME, bool ACCUM = false>
 __device__ __forceinline__ void weights_bwd_ray(long long r, int S, int lane, const float* eb, const float* dn,
                                                 const float (&delta)[ME], const float (&gw)[ME], const float (&wk)[ME],
                                                 float dd_local, float gww_local, float wsum_local, float gr, float gg,
@@ -168,7 +169,9 @@ __device__ __forceinline__ void weights_bwd_ray(long long r, int S, int lane, co
       float s = 1.0f;
       if constexpr (SCALE) s = distance_squared_scale(eb[k], eb[k + 1]);
       const auto leaving = [s](float g) { return SCALE ? s * g : g; };   // a gradient on its way to the field
-      d_density[r * S + k] = leaving(delta[e] * (gw[e] * T_next - suf[e]));
+      const float dk = leaving(delta[e] * (gw[e] * T_next - suf[e]));
+      if constexpr (ACCUM) d_density[r * S + k] = d_density[r * S + k] + dk;
+      else d_density[r * S + k] = dk;
       if (COMPOSITE) {
         float f = wk[e];
         if (!BG && k == S - 1) f += bgw;  // background = last sample's colour (RGBRenderer "last_sample")

@@ -55,6 +55,9 @@ class FruitNerfModelConfig:
     proposal_initial_sampler: str = "piecewise"
     interlevel_loss_mult: float = 1.0
     distortion_loss_mult: float = 0.002
+    # Nerfacto's distortion_loss term in get_loss_dict (the reference drops it and keeps the value as a metric, fruit_nerf.py:
+    # 359-372, 400): True trains the field with distortion_loss_mult * distortion of the final level (fnr_distortion_bwd)
+    use_distortion_loss: bool = False
     use_proposal_weight_anneal: bool = True
     use_average_appearance_embedding: bool = True
     proposal_weights_anneal_slope: float = 10.0

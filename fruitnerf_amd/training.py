@@ -77,9 +77,25 @@ def _composite_backward(rctx, semgrad: bool, *, given=None, targets=None):
     return fn(*args)
 
 
+def _distortion_on(model, rctx) -> bool:
+    """use_distortion_loss applies to this pass: the switch is on and the pass is a training pass with rays."""
+    return bool(getattr(model.config, "use_distortion_loss", False) and rctx.training and rctx.rays is not None)
+
+
+def _distortion_backward(model, rctx, d_density: Tensor, upstream: Optional[Tensor] = None) -> None:
+    """use_distortion_loss: d(distortion_loss)/d(density) of the final level, added IN PLACE to the compositing backward's
+    d_density ahead of the field's MLP backward (fnr_distortion_bwd; scaled like it under use_gradient_scaling).
+    upstream: device scalar, None = 1."""
+    cfg, lv = model.config, rctx.levels[-1]
+    K.distortion_bwd(lv["S"], lv["spacing"], lv["euclid"], rctx.sample_density, rctx.weights, cfg.distortion_loss_mult,
+                     d_density, upstream=upstream, gradient_scaling=bool(cfg.use_gradient_scaling))
+
+
 class _RenderFn(torch.autograd.Function):
-    """rays -> (rgb, semantics, accumulation, depth, prop depths); backward runs compositing-bwd,
-    field-MLP-bwd (MFMA) and the hash-grid scatter."""
+    """rays -> (rgb, semantics, accumulation, depth, prop depths[, distortion_loss]); backward runs compositing-bwd,
+    field-MLP-bwd (MFMA) and the hash-grid scatter.  use_distortion_loss (training): the last output is
+    distortion_loss_mult * distortion of the final level, differentiable — its upstream gradient joins d_density in the
+    SAME backward, so loss.backward() runs one field backward whatever the loss dict holds."""
 
     @staticmethod
     def forward(ctx, anchor, origins, directions, model, ray_bundle, jitter):
@@ -92,12 +108,17 @@ class _RenderFn(torch.autograd.Function):
         outs = [outputs["rgb"], outputs["semantics"], outputs["accumulation"], outputs["depth"]]
         outs += [outputs[f"prop_depth_{i}"] for i in range(n_prop)]
         ctx.mark_non_differentiable(*outs[2:])
+        ctx.has_distortion = _distortion_on(model, rctx)
+        if ctx.has_distortion:
+            fin = rctx.levels[-1]
+            rctx.distortion = K.distortion(fin["S"], fin["spacing"], fin["weights"])   # (get_metrics_dict reuses it)
+            outs.append(rctx.distortion * model.config.distortion_loss_mult)
         ctx.rctx_holder = rctx
         model._last_render_ctx = rctx
         return tuple(outs)
 
     @staticmethod
-    def backward(ctx, g_rgb, g_sem, *_):
+    def backward(ctx, g_rgb, g_sem, *rest):
         model, rctx = ctx.model, ctx.rctx
         arena = model.arena()
         arena.reattach_grads()
@@ -112,6 +133,9 @@ class _RenderFn(torch.autograd.Function):
             g_sem = torch.zeros(rays.n, 1, device=dev)
         semgrad = bool(model.config.pass_semantic_gradients)   # fruit_nerf.py:344-345: semantic weights not detached
         d_density, d_rgb, d_logit = _composite_backward(rctx, semgrad, given=(g_rgb.contiguous(), g_sem.contiguous()))
+        if ctx.has_distortion and rest[-1] is not None:
+            # (the upstream gradient stays on the device: a GradScaler's scale arrives through it without a host sync)
+            _distortion_backward(model, rctx, d_density, upstream=rest[-1])
         fld = model.field
         net, gnet = fld.net_struct(), fld.net_struct(grads=True)
         want_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
@@ -291,6 +315,8 @@ def render_with_grad(model, ray_bundle, jitter=None):
     outputs = {"rgb": outs[0], "semantics": outs[1], "accumulation": outs[2], "depth": outs[3]}
     for i in range(n_prop):
         outputs[f"prop_depth_{i}"] = outs[4 + i]
+    if len(outs) > 4 + n_prop:
+        rctx.distortion_loss = outs[4 + n_prop]     # (not an output of the model: get_loss_dict picks it up here)
     return outputs, rctx
 
 
@@ -310,6 +336,16 @@ def fused_losses(model, outputs, batch) -> Dict[str, Tensor]:
         rb = rctx.ray_bundle
         loss_dict["interlevel_loss"] = _InterlevelFn.apply(_anchor(model), rb.origins, rb.directions, model, rctx,
                                                            model.config.interlevel_loss_mult)
+        if getattr(model.config, "use_distortion_loss", False):
+            # Nerfacto's term: the differentiable last output of _RenderFn (a pass rendered without autograd has the value only)
+            dist_loss = getattr(rctx, "distortion_loss", None)
+            if dist_loss is None:
+                fin = rctx.levels[-1]
+                with torch.no_grad():
+                    dist = K.distortion(fin["S"], fin["spacing"], fin["weights"]) if rctx.rays is not None \
+                        else torch.zeros((), device=dev)
+                    dist_loss = dist * model.config.distortion_loss_mult
+            loss_dict["distortion_loss"] = dist_loss
     return loss_dict
 
 
@@ -324,7 +360,9 @@ def metrics(model, outputs, batch) -> Dict[str, Tensor]:
         outputs["_loss_cache"] = (losses, d_rgb, d_sem, batch, w)
         psnr = losses[2]
         fin = outputs["_ctx"].levels[-1]
-        dist = K.distortion(fin["S"], fin["spacing"], fin["weights"])
+        dist = getattr(outputs["_ctx"], "distortion", None)     # use_distortion_loss: summed by the render already
+        if dist is None:
+            dist = K.distortion(fin["S"], fin["spacing"], fin["weights"])
     return {"psnr": psnr, "distortion": dist}
 
 
@@ -897,7 +935,8 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
                            want_metrics: bool = True, exchange: Optional[_FieldGradientExchange] = None,
                            ray_grads: Optional[dict] = None, overlap_proposal_backward: bool = False,
                            table_adam=None, weight_adam=None, proposal_optimizer: Optional["FusedAdam"] = None,
-                           after_ray_grads=None, serialize_streams: bool = False, ahead=None, exchange_finish=None):
+                           after_ray_grads=None, serialize_streams: bool = False, ahead=None, exchange_finish=None,
+                           scale_distortion_loss: bool = True):
     """model(ray_bundle) -> get_metrics_dict -> get_loss_dict -> sum -> backward without the autograd engine:
     the same kernels in the same order, called directly.
 
@@ -915,7 +954,11 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
     (TrainingSteps' look-ahead), on the second stream.
     serialize_streams (with overlap_proposal_backward): the same launches on the same two streams (same allocator pools),
     but each stream waits for everything the other has enqueued — nothing runs concurrently (bench.py: the steps whose
-    launches it brackets with HIP events)."""
+    launches it brackets with HIP events).
+    use_distortion_loss (training): one fnr_distortion_bwd launch between the compositing backward and the field's MLP
+    backward adds the term to d_density in place; the losses launch sums the distortion also without metrics and
+    loss_dict["distortion_loss"] = distortion_loss_mult x that sum — or the sum itself with scale_distortion_loss=False, for a
+    caller that multiplies later (TrainingSteps: outside the recorded region)."""
     from . import _lib as L
     cfg = model.config
     semgrad = bool(cfg.pass_semantic_gradients)   # the `_semgrad` forms of the compositing / MLP backward, recordable like theirs
@@ -933,6 +976,7 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
                                       loss_targets=(image, mask, cfg.semantic_loss_weight) if fuse_composite else None)
         rays, fin = rctx.rays, rctx.levels[-1]
         S = fin["S"]
+        use_dist = _distortion_on(model, rctx)
         # one fill for everything this step accumulates into: the loss slots (+ completion counter) and, with a camera
         # optimiser, the ray gradients d(loss)/d(origins | directions); one launch for every loss and metric
         # the loss / metric accumulator is persistent: fnr_train_losses leaves it zeroed (its last workgroup cleans up),
@@ -961,11 +1005,13 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
         with torch.cuda.stream(side) if losses_on_side else contextlib.nullcontext():
             losses, d_rgb, d_sem, d_wps = K.train_losses(outputs["rgb"], image, outputs["semantics"], mask,
                                                          cfg.semantic_loss_weight, S, fin["spacing"], fin["weights"],
-                                                         prop_levels, cfg.interlevel_loss_mult, want_metrics,
+                                                         prop_levels, cfg.interlevel_loss_mult, want_metrics or use_dist,
                                                          accum, fuse_weights_bwd=prop_bwd,
                                                          want_ray_grads=not losses_on_side)
         loss_dict = {"rgb_loss": losses[0], "semantics_loss": losses[1], "interlevel_loss": losses[3]}
         metrics_dict = {"psnr": losses[2], "distortion": losses[4]} if want_metrics else {}
+        if use_dist:
+            loss_dict["distortion_loss"] = losses[4]     # (the sum: scaled on the way out)
 
         # ---- backward (what loss.backward() runs through _LossFn, _RenderFn, _InterlevelFn) ----
         arena = model.arena()
@@ -1017,6 +1063,8 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
                 rctx, semgrad, targets=(outputs["rgb"], image, outputs["semantics"], mask, cfg.semantic_loss_weight))
         else:
             d_density, d_rgb_s, d_logit = _composite_backward(rctx, semgrad, given=(d_rgb, d_sem))
+        if use_dist:
+            _distortion_backward(model, rctx, d_density)     # unit upstream, on the launch stream, in place
         fld = model.field
         net, gnet = fld.net_struct(), fld.net_struct(grads=True)
         d_pos = None
@@ -1105,13 +1153,13 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
             tail(first=False, last=True)
             fj.join()
             fj.check()
-            return loss_dict, metrics_dict
+            return _scaled_distortion_loss(model, loss_dict, scale_distortion_loss), metrics_dict
         scatter()
         if tail_on_side:
             tail()
             fj.join()                              # every local of this call outlives the second stream's launches
             fj.check()
-            return loss_dict, metrics_dict
+            return _scaled_distortion_loss(model, loss_dict, scale_distortion_loss), metrics_dict
         if side is not None:
             fj.join()                              # proposal gradients (and their ray-gradient sources) are final
             for src in ray_sources or ():
@@ -1128,7 +1176,14 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
         if ahead is not None:
             ahead()
         fj.check()
-    return loss_dict, metrics_dict
+    return _scaled_distortion_loss(model, loss_dict, scale_distortion_loss), metrics_dict
+
+
+def _scaled_distortion_loss(model, loss_dict: dict, scale: bool = True) -> dict:
+    """loss_dict["distortion_loss"] holds the losses launch's distortion sum -> distortion_loss_mult x it (one scalar op)."""
+    if scale and "distortion_loss" in loss_dict:
+        loss_dict["distortion_loss"] = loss_dict["distortion_loss"] * model.config.distortion_loss_mult
+    return loss_dict
 
 
 def _camera_table(batcher):
@@ -1195,8 +1250,9 @@ FUSE_TABLE_OPTIMIZER = True   # single process: the main hash table's Adam / RAd
 
 def fused_train_iteration(model, optimizer: FusedAdam, ray_bundle, batch, step: int, world_size: int = 1,
                           jitter: Optional[List[Tensor]] = None, want_metrics: bool = True, camera=None,
-                          fuse_table_optimizer: Optional[bool] = None, ahead=None):
-    """train_iteration() on fused_forward_backward(); returns the same (loss_dict, metrics_dict) tensors.
+                          fuse_table_optimizer: Optional[bool] = None, ahead=None, scale_distortion_loss: bool = True):
+    """train_iteration() on fused_forward_backward(); returns the same (loss_dict, metrics_dict) tensors
+    (scale_distortion_loss: see there).
 
     ahead: called with no arguments once the proposal networks' and the cameras' optimiser steps of this iteration are
     enqueued — the point from which the next iteration's rays and proposal sampling can be enqueued (TrainingSteps).
@@ -1284,7 +1340,8 @@ def fused_train_iteration(model, optimizer: FusedAdam, ray_bundle, batch, step: 
                                                      proposal_optimizer=prop_opt, after_ray_grads=camera_step,
                                                      serialize_streams=SERIALIZE_STREAMS,
                                                      ahead=ahead_early if exchange is None else ahead,
-                                                     exchange_finish=exchange_finish if exchange is not None else None)
+                                                     exchange_finish=exchange_finish if exchange is not None else None,
+                                                     scale_distortion_loss=scale_distortion_loss)
     with torch.no_grad():
         if exchange is None:
             optimizer.step(skip=skipped_groups(model, optimizer), done=done)
@@ -1467,6 +1524,7 @@ class TrainingSteps:
                 FUSE_WEIGHT_OPTIMIZER, FUSE_TABLE_OPTIMIZER, SPARSE_TOUCH_SKIPPING, STREAM_SAFE, FUSE_COMPOSITE_BACKWARD,
                 cfg.semantic_loss_weight, cfg.interlevel_loss_mult, cfg.near_plane, cfg.far_plane,
                 bool(cfg.pass_semantic_gradients), cfg.background_color, bool(cfg.use_gradient_scaling),
+                bool(getattr(cfg, "use_distortion_loss", False)), cfg.distortion_loss_mult,
                 # (one jitter per ray or per bin edge: other prologue and PDF entry points, another program)
                 bool(getattr(model.proposal_sampler, "single_jitter", True)))
 
@@ -1564,11 +1622,14 @@ class TrainingSteps:
             if rc != 0:
                 L.end_call_log(log)
                 L.check(rc, "program_begin")
+        # use_distortion_loss: the one scalar op that scales the loss value runs behind the recording, as in a replayed step
+        deferred = {"scale_distortion_loss": False} \
+            if getattr(getattr(self.model, "config", None), "use_distortion_loss", False) else {}
         prev = K.use_arena(arena)
         try:
             out = fused_train_iteration(self.model, self.optimizer, rb, batch, step, world_size=self.world_size,
                                         want_metrics=want_metrics, camera=self.camera,
-                                        ahead=ahead if (SAMPLE_AHEAD and self.model.training) else None)
+                                        ahead=ahead if (SAMPLE_AHEAD and self.model.training) else None, **deferred)
         except BaseException:
             if prog is not None:
                 L.end_call_log(log)
@@ -1578,6 +1639,8 @@ class TrainingSteps:
             K.use_arena(prev)
         if prog is not None:
             self._finish_recording(prog, log, record_key, rb, batch, arena, other, fresh_ws)
+        if deferred:
+            _scaled_distortion_loss(self.model, out[0])
         self.stats["interpreted"] += 1
         self.step_idx += 1
         return out
@@ -1666,8 +1729,10 @@ class TrainingSteps:
         self.stats["replayed"] += 1
         self.step_idx = step + 1
         l0, l1, l2, l3, l4 = losses.unbind(0)
-        return ({"rgb_loss": l0, "semantics_loss": l1, "interlevel_loss": l3},
-                {"psnr": l2, "distortion": l4} if want_metrics else {})
+        loss_dict = {"rgb_loss": l0, "semantics_loss": l1, "interlevel_loss": l3}
+        if getattr(model.config, "use_distortion_loss", False):   # (a program is only ever recorded from a training pass)
+            loss_dict["distortion_loss"] = l4
+        return (_scaled_distortion_loss(model, loss_dict), {"psnr": l2, "distortion": l4} if want_metrics else {})
 
 
 # entry points a recording does not contain: pure host queries, and the program API itself

@@ -414,6 +414,20 @@ int fnr_interlevel_fwd(int64_t n_rays, int S_f, const float* spacing_f, const fl
  * sum(out[0..FNR_LOSS_SLOTS)) += value. */
 int fnr_distortion(int64_t n_rays, int S, const float* spacing, const float* weights, float* out, void* stream);
 
+/* use_distortion_loss (Nerfacto's switch; nerfstudio 0.3.2 distortion_loss on the final level): the backward of
+ *   loss = mult * mean_r D_r,  D_r = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 ds_i,
+ * m_i / ds_i the midpoint / width of spacing bin i (detached), w the field's compositing weights.  One launch, one wave per ray:
+ *   d_weights[k] = (mult / n_rays) g (2 sum_j w_j |m_k - m_j| + (2/3) w_k ds_k),  g = *upstream (device scalar; NULL = 1),
+ * the sum taken directly (S terms >= 0); then the backward of RaySamples.get_weights (fnr_weights_bwd's arithmetic) on
+ * d_weights, and d_density[k] = d_density[k] + s_k term_k: ONE float32 addition of the value d_density holds (what the
+ * compositing backward left there) and the finished term, s_k = 1 or, with gradient_scaling != 0, clamp(m_k^2, 0, 1) of the
+ * Euclidean midpoint m_k = (euclid_bins[k] + euclid_bins[k+1]) / 2 as in fnr_composite_options (float32(s_k) x the unscaled
+ * term, bit for bit).  spacing, euclid_bins [R,S+1]; density, weights [N]; d_weights [N] out, NULL = not wanted;
+ * 1 <= S <= 512; n_rays == 0: nothing to do.  Recordable.  Pure addition at ABI 13. */
+int fnr_distortion_bwd(int64_t n_rays, int S, const float* spacing, const float* euclid_bins, const float* density,
+                       const float* weights, float mult, const float* upstream, int gradient_scaling, float* d_weights,
+                       float* d_density, void* stream);
+
 /* Backward of fnr_composite_fwd (training): g_rgb [R,3], g_semantics [R] -> per-sample d_density [N],
  * d_rgb [N,3], d_logit [N].  Semantic compositing weights are detached (fruit_nerf.py:343-345). */
 int fnr_composite_bwd(const fnr_rays* rays, int S, const float* euclid_bins, const float* density, const float* rgb,

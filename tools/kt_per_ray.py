@@ -5,7 +5,7 @@ rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Time
 agg = collections.defaultdict(list)
 for r in rows:
     k = re.sub(r"\(.*", "", r["Kernel_Name"]).replace("void ", "").replace("fnr::", "")
-    if not re.match(r"k_train_losses|k_weights_pdf|k_composite_fwd_bwd|k_composite_bwd|k_weights_bwd|k_composite_fwd\b", k):
+    if not re.match(r"k_train_losses|k_weights_pdf|k_composite_fwd_bwd|k_composite_bwd|k_weights_bwd|k_distortion_bwd|k_composite_fwd\b", k):
         continue
     agg[k].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
 def med(v):
