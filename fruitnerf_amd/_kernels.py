@@ -491,6 +491,27 @@ def export_compact(lat: Optional[LatticeArg], ray_begin: int, n_rays: int, posit
                                    L.ptr(ws), L.stream_ptr(dev)), "export_compact")
 
 
+def depth_points(origins: Tensor, directions: Tensor, depth: Tensor, rgb: Tensor, box_min, box_max, points: Tensor,
+                 colors: Tensor, count: Tensor) -> None:
+    """Appends origin + direction * depth (fp32, torch's bits) and rgb of the rays whose point lies strictly inside the
+    box (box_min / box_max: 3 floats each, or both None) to points / colors [capacity,3] in ray order; `count` (uint64,
+    stored as int64 [1] on the device) is the running total."""
+    lib = L.load()
+    dev = depth.device
+    R = depth.numel()
+    if R == 0:
+        return
+    o, d, t, c = _f32c(origins.reshape(-1, 3)), _f32c(directions.reshape(-1, 3)), _f32c(depth.reshape(-1)), \
+        _f32c(rgb.reshape(-1, 3))
+    assert o.shape[0] == d.shape[0] == c.shape[0] == R and points.shape == colors.shape and points.is_contiguous() \
+        and colors.is_contiguous() and points.dtype == colors.dtype == torch.float32
+    ws = _empty(lib.fnr_export_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    lo = None if box_min is None else (C.c_float * 3)(*[float(v) for v in box_min])
+    hi = None if box_max is None else (C.c_float * 3)(*[float(v) for v in box_max])
+    L.check(lib.fnr_depth_points(L.ptr(o), L.ptr(d), L.ptr(t), L.ptr(c), R, lo, hi, L.ptr(points), L.ptr(colors),
+                                 points.shape[0], L.ptr(count), L.ptr(ws), L.stream_ptr(dev)), "depth_points")
+
+
 # ---- training ---------------------------------------------------------------------------------------
 
 
@@ -1046,6 +1067,48 @@ def cloud_voxel_down_sample(xyz: Tensor, rgb: Optional[Tensor], voxel_size: floa
                                                  L.stream_ptr(xyz.device)), "cloud_voxel_down_sample")
     m = int(n_out.item())
     return xyz_out[:m], (None if rgb_out is None else rgb_out[:m])
+
+
+def _knn_args(xyz: Tensor, k: int):
+    xyz, n, _ = _cloud_args(xyz)
+    ws = torch.empty(L.load().fnr_cloud_knn_workspace_bytes(n, int(k)), dtype=torch.uint8, device=xyz.device)
+    return xyz, n, ws
+
+
+def cloud_knn(xyz: Tensor, k: int):
+    """-> (dist2 float64 [n,k], index int32 [n,k]): the k points nearest to every point (itself included), ascending by
+    (squared distance, input index); with n < k the tail of a row is +inf / -1."""
+    xyz, n, ws = _knn_args(xyz, k)
+    dist2 = torch.empty(n, int(k), dtype=torch.float64, device=xyz.device)
+    index = torch.empty(n, int(k), dtype=torch.int32, device=xyz.device)
+    lo, hi = _bounds(xyz) if n else ((C.c_double * 3)(), (C.c_double * 3)())
+    L.check(L.load().fnr_cloud_knn(L.ptr(xyz), n, lo, hi, int(k), L.ptr(dist2), L.ptr(index), L.ptr(ws), ws.numel(),
+                                   L.stream_ptr(xyz.device)), "cloud_knn")
+    return dist2, index
+
+
+def cloud_statistical_outlier(xyz: Tensor, nb_neighbors: int, std_ratio: float):
+    """Open3D RemoveStatisticalOutliers -> (avg_distance float64 [n], keep bool [n], stats float64 [3] = mean, std,
+    threshold; all on the device)."""
+    xyz, n, ws = _knn_args(xyz, nb_neighbors)
+    avg = torch.empty(n, dtype=torch.float64, device=xyz.device)
+    keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+    stats = torch.zeros(3, dtype=torch.float64, device=xyz.device)
+    lo, hi = _bounds(xyz) if n else ((C.c_double * 3)(), (C.c_double * 3)())
+    L.check(L.load().fnr_cloud_statistical_outlier(L.ptr(xyz), n, lo, hi, int(nb_neighbors), float(std_ratio),
+                                                   L.ptr(avg), L.ptr(keep), L.ptr(stats), L.ptr(ws), ws.numel(),
+                                                   L.stream_ptr(xyz.device)), "cloud_statistical_outlier")
+    return avg, keep.bool(), stats
+
+
+def cloud_estimate_normals(xyz: Tensor, knn: int) -> Tensor:
+    """Open3D EstimateNormals(KDTreeSearchParamKNN(knn)) -> float64 [n,3] unit normals (sign not oriented)."""
+    xyz, n, ws = _knn_args(xyz, knn)
+    normals = torch.empty(n, 3, dtype=torch.float64, device=xyz.device)
+    lo, hi = _bounds(xyz) if n else ((C.c_double * 3)(), (C.c_double * 3)())
+    L.check(L.load().fnr_cloud_estimate_normals(L.ptr(xyz), n, lo, hi, int(knn), L.ptr(normals), L.ptr(ws), ws.numel(),
+                                                L.stream_ptr(xyz.device)), "cloud_estimate_normals")
+    return normals
 
 
 # ---- eval-image metrics ------------------------------------------------------------------------------

@@ -265,7 +265,15 @@ SIGNATURES = {
     "fnr_export_workspace_bytes": (C.c_size_t, [_i64]),
     "fnr_export_compact": (_i, [P(fnr_lattice), _i64, _i64, _vp, _i64, _vp, _vp, _vp, P(_vp), P(_vp), _i64, _vp, _vp,
                                 _vp]),
+    "fnr_depth_points": (_i, [_vp, _vp, _vp, _vp, _i64, P(C.c_float), P(C.c_float), _vp, _vp, _i64, _vp, _vp, _vp]),
+    "fnr_cloud_knn_workspace_bytes": (C.c_size_t, [_i64, C.c_int32]),
+    "fnr_cloud_knn": (_i, [_vp, _i64, P(C.c_double), P(C.c_double), C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_cloud_statistical_outlier": (_i, [_vp, _i64, P(C.c_double), P(C.c_double), C.c_int32, C.c_double, _vp, _vp, _vp,
+                                           _vp, C.c_size_t, _vp]),
+    "fnr_cloud_estimate_normals": (_i, [_vp, _i64, P(C.c_double), P(C.c_double), C.c_int32, _vp, _vp, C.c_size_t, _vp]),
 }
+
+FNR_CLOUD_KNN_MAX = 32
 
 _lib: Optional[C.CDLL] = None
 

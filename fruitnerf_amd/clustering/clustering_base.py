@@ -23,7 +23,10 @@ from . import shapes
 
 
 class PointCloud:
-    """points / colors: float64 [n,3] device tensors (colours in [0,1], optional)."""
+    """points / colors: float64 [n,3] device tensors (colours in [0,1], optional); normals: float64 [n,3] once
+    estimate_normals has run (None before)."""
+
+    normals: Optional[torch.Tensor] = None
 
     def __init__(self, points, colors=None, device: Union[str, torch.device] = "cuda"):
         dev = torch.device(device)
@@ -36,8 +39,11 @@ class PointCloud:
     @classmethod
     def read(cls, path: str, device: Union[str, torch.device] = "cuda") -> "PointCloud":
         """o3d.io.read_point_cloud for the binary PLY layout the exporter writes."""
-        pts, cols = ply.read_point_cloud(path)
-        return cls(pts, cols, device)
+        pts, cols, *normals = ply.read_point_cloud(path)
+        out = cls(pts, cols, device)
+        if normals:
+            out.normals = torch.as_tensor(normals[0], dtype=torch.float64, device=out.points.device).contiguous()
+        return out
 
     def __len__(self) -> int:
         return self.points.shape[0]
@@ -46,7 +52,28 @@ class PointCloud:
         out = PointCloud.__new__(PointCloud)
         out.points = self.points[indices].contiguous()
         out.colors = None if self.colors is None else self.colors[indices].contiguous()
+        out.normals = None if self.normals is None else self.normals[indices].contiguous()
         return out
+
+    def remove_statistical_outlier(self, nb_neighbors: int, std_ratio: float) -> Tuple["PointCloud", torch.Tensor]:
+        """Open3D: keep the points whose mean distance to their nb_neighbors nearest points (itself included) is
+        positive and below mean + std_ratio * std of those means; -> (filtered cloud, kept indices in ascending order)."""
+        if nb_neighbors < 1 or std_ratio <= 0:
+            raise ValueError("Illegal input parameters, the number of neighbors and standard deviation ratio must be "
+                             "positive")                                                                 # Open3D's check
+        if len(self) == 0:
+            return self.select_by_index(torch.empty(0, dtype=torch.int64, device=self.points.device)), \
+                torch.empty(0, dtype=torch.int64, device=self.points.device)
+        _, keep, _ = K.cloud_statistical_outlier(self.points, nb_neighbors, std_ratio)
+        kept = torch.nonzero(keep).flatten()
+        return self.select_by_index(kept), kept
+
+    def estimate_normals(self, knn: int = 30) -> None:
+        """Open3D estimate_normals(KDTreeSearchParamKNN(knn)): sets `.normals` (float64 [n,3], unit length, sign not
+        oriented) from the covariance of every point's knn nearest points."""
+        if knn < 1:
+            raise ValueError("knn must be positive")
+        self.normals = K.cloud_estimate_normals(self.points, knn)
 
     def remove_radius_outlier(self, nb_points: int, radius: float) -> Tuple["PointCloud", torch.Tensor]:
         """Open3D: keep the points with MORE than nb_points points (itself included) strictly inside `radius`;

@@ -17,44 +17,12 @@
 // them in scikit-learn's index-ordered expansion), everything else is noise (-1).
 #include <cstring>
 
-#include "common.hpp"
+#include "cloud_grid.hpp"
 #include "sequencer.hpp"
 
 #include <rocprim/rocprim.hpp>
 
 namespace fnr {
-
-typedef unsigned long long u64;
-
-// one sorted point: position + what the sweeps need to know about it as a CANDIDATE, so that a candidate is one 32-byte
-// scalar load (input index and core flag ride in what would be padding)
-struct alignas(32) CloudPoint {
-  double x, y, z;
-  int index;   // input index (order[s])
-  int core;    // DBSCAN core flag, filled in after the count pass
-};
-
-struct CloudGrid {
-  double lo[3];
-  double cell;
-  long long dim[3];
-};
-
-struct CloudWs {
-  u64* keys_a;
-  u64* keys;      // sorted
-  int* idx_a;
-  int* order;     // sorted position -> input index
-  CloudPoint* sxyz;  // [n] points in sorted order
-  int* aux0;      // per sorted position: core flag / head flag
-  int* aux1;      // per input index: union-find parent
-  int* aux2;      // per input index: core flag, then root flag
-  int* aux3;      // scan output
-  int* cell_first;  // [n_cells + 1] first sorted position of every occupied cell
-  int* ctrl;      // [0] n_cells, [1..7] work counters of the cell sweeps
-  void* temp;
-  size_t temp_bytes;
-};
 
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -64,7 +32,7 @@ static size_t cloud_fixed_bytes(int64_t n) {
 }
 static size_t cloud_temp_reserve(int64_t n) { return (size_t)(n < 1 ? 1 : n) * 16 + ((size_t)8 << 20); }
 
-static bool carve_cloud(void* ws, size_t bytes, int64_t n, CloudWs* out) {
+bool carve_cloud(void* ws, size_t bytes, int64_t n, CloudWs* out) {
   if (!ws || bytes < cloud_fixed_bytes(n) + ((size_t)1 << 20)) return false;
   const size_t m = (size_t)(n < 1 ? 1 : n);
   char* p = static_cast<char*>(ws);
@@ -170,27 +138,6 @@ __global__ __launch_bounds__(256) void k_cloud_pack_core(const int* __restrict__
   if (s < n) sxyz[s].core = core_sorted[s];
 }
 
-__device__ inline int lower_bound_key(const u64* __restrict__ keys, int lo, int hi, u64 k) {
-  while (lo < hi) {
-    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-    if (keys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-__device__ inline int upper_bound_key(const u64* __restrict__ keys, int lo, int hi, u64 k) {
-  while (lo < hi) {
-    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-    if (keys[mid] <= k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// squared distance in the CPU libraries' operation order: ((dx*dx) + dy*dy) + dz*dz, every op rounded
-__device__ inline double pair_d2(const CloudPoint& p, const CloudPoint& q) {
-  const double dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-  return (dx * dx + dy * dy) + dz * dz;
-}
-
 // ---- cell-cooperative neighbourhood sweep ---------------------------------------------------------------------------
 // A wave takes one occupied cell at a time (dynamic: one atomic per cell).  The cell's 9 candidate runs are found once
 // (lanes 0..8 search one run each) and live in SGPRs; the lanes hold up to 64 of the cell's points (the targets) and
@@ -200,8 +147,6 @@ __device__ inline double pair_d2(const CloudPoint& p, const CloudPoint& q) {
 struct CellRuns {
   int b[9], e[9];
 };
-
-__device__ inline int wave_lane() { return (int)(threadIdx.x & 63u); }
 
 __device__ inline bool next_cell(int* counter, int n_cells, int* c) {
   int v = 0;
@@ -503,7 +448,7 @@ static int key_bits(const CloudGrid& g) {
   return bits;
 }
 
-static int sort_by_key(const CloudWs& w, int n, int bits, hipStream_t st) {
+int sort_by_key(const CloudWs& w, int n, int bits, hipStream_t st) {
   size_t need = 0;
   FNR_HIP(rocprim::radix_sort_pairs(nullptr, need, w.keys_a, w.keys, w.idx_a, w.order, (size_t)n, 0u, (unsigned)bits,
                                     st));
@@ -524,6 +469,12 @@ static int scan_flags(const CloudWs& w, const int* flags, int* out, int n, hipSt
   return FNR_OK;
 }
 
+int gather_sorted(const double* xyz, const CloudWs& w, int n, hipStream_t st) {
+  hipLaunchKernelGGL(k_cloud_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xyz, w.order, n, w.sxyz);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
 // neighbour grid for radius r: the cell edge is a hair above r so that rounding in (p - lo) / cell can never put two
 // points closer than r more than one cell apart
 static int build_search_grid(const double* xyz, int n, const double* lo, const double* hi, double radius,
@@ -535,8 +486,8 @@ static int build_search_grid(const double* xyz, int n, const double* lo, const d
   FNR_LAUNCH_CHECK();
   rc = sort_by_key(w, n, key_bits(*g), st);
   if (rc != FNR_OK) return rc;
-  hipLaunchKernelGGL(k_cloud_gather, dim3(blocks), dim3(256), 0, st, xyz, w.order, n, w.sxyz);
-  FNR_LAUNCH_CHECK();
+  rc = gather_sorted(xyz, w, n, st);
+  if (rc != FNR_OK) return rc;
   // occupied cells: head flags of the sorted keys -> ranks -> first position per cell
   hipLaunchKernelGGL(k_voxel_heads, dim3(blocks), dim3(256), 0, st, w.keys, n, w.aux0);
   FNR_LAUNCH_CHECK();

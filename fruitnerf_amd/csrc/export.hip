@@ -168,6 +168,89 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_export_write(long long N, int n_y
   }
 }
 
+// ---- depth point cloud (Nerfstudio generate_point_cloud): one stream of the same count -> scan -> write scheme ------
+struct DepthBox {
+  float lo[3], hi[3];
+  int on;
+};
+
+// origin + direction * depth, product and sum rounded separately; kept = strictly inside the box
+__device__ __forceinline__ bool depth_point(const float* __restrict__ origins, const float* __restrict__ directions,
+                                            const float* __restrict__ depth, long long r, const DepthBox& box,
+                                            float (&p)[3]) {
+  const float t = depth[r];
+  bool keep = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    p[a] = fadd(origins[3 * r + a], fmul(directions[3 * r + a], t));
+    if (box.on) keep = keep && p[a] > box.lo[a] && p[a] < box.hi[a];
+  }
+  return keep;
+}
+
+__global__ __launch_bounds__(EXP_BLOCK) void k_depth_count(long long R, const float* __restrict__ origins,
+                                                           const float* __restrict__ directions,
+                                                           const float* __restrict__ depth, DepthBox box,
+                                                           unsigned long long* __restrict__ block_counts) {
+  __shared__ unsigned s_cnt;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  const long long base = (long long)blockIdx.x * EXP_TILE + (long long)threadIdx.x * EXP_PER_THREAD;
+  unsigned c = 0;
+#pragma unroll
+  for (int q = 0; q < EXP_PER_THREAD; ++q) {
+    float p[3];
+    if (base + q < R) c += depth_point(origins, directions, depth, base + q, box, p) ? 1u : 0u;
+  }
+  if (c) atomicAdd(&s_cnt, c);
+  __syncthreads();
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = s_cnt;
+}
+
+__global__ __launch_bounds__(EXP_BLOCK) void k_depth_write(long long R, const float* __restrict__ origins,
+                                                           const float* __restrict__ directions,
+                                                           const float* __restrict__ depth,
+                                                           const float* __restrict__ rgb, DepthBox box,
+                                                           float* __restrict__ points, float* __restrict__ colors,
+                                                           long long capacity,
+                                                           const unsigned long long* __restrict__ block_offsets) {
+  __shared__ unsigned s_wave[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long base = (long long)blockIdx.x * EXP_TILE + (long long)threadIdx.x * EXP_PER_THREAD;
+  float p[EXP_PER_THREAD][3];
+  bool keep[EXP_PER_THREAD];
+  unsigned cnt = 0;
+#pragma unroll
+  for (int q = 0; q < EXP_PER_THREAD; ++q) {
+    keep[q] = base + q < R && depth_point(origins, directions, depth, base + q, box, p[q]);
+    cnt += keep[q] ? 1u : 0u;
+  }
+  unsigned incl = cnt;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned t = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += t;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  unsigned pre = incl - cnt;
+  for (int q = 0; q < wave; ++q) pre += s_wave[q];
+  unsigned long long pos = block_offsets[blockIdx.x] + pre;
+#pragma unroll
+  for (int q = 0; q < EXP_PER_THREAD; ++q) {
+    if (!keep[q]) continue;
+    const unsigned long long at = pos++;
+    if ((long long)at < capacity) {
+      const long long r = base + q;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        points[3 * at + a] = p[q][a];
+        colors[3 * at + a] = rgb[3 * r + a];
+      }
+    }
+  }
+}
+
 }  // namespace fnr
 
 using namespace fnr;
@@ -216,6 +299,39 @@ extern "C" int fnr_export_compact(const fnr_lattice* lat, int64_t ray_begin, int
   hipLaunchKernelGGL(k_export_write, dim3((unsigned)nblocks), dim3(EXP_BLOCK), 0, st, N, lat->n_y, lat->n_z,
                      (long long)ray_begin, lat->xs, lat->ys, lat->zs, positions, density, rgb, logit, out, (long long)capacity,
                      bc, nblocks);
+  FNR_LAUNCH_CHECK();
+  return FNR_OK;
+}
+
+extern "C" int fnr_depth_points(const float* origins, const float* directions, const float* depth, const float* rgb,
+                                int64_t n_rays, const float* box_min, const float* box_max, float* points,
+                                float* colors, int64_t capacity, uint64_t* count, void* workspace, void* stream) {
+  FNR_SEQ_UNRECORDABLE("fnr_depth_points");
+  FNR_CHECK_ARG(origins && directions && depth && rgb && points && colors && count && workspace,
+                "depth_points: null argument");
+  FNR_CHECK_ARG((box_min == nullptr) == (box_max == nullptr), "depth_points: box_min and box_max go together");
+  FNR_CHECK_ARG(n_rays >= 0 && capacity >= 0, "depth_points: n_rays / capacity < 0");
+  if (n_rays == 0) return FNR_OK;
+  const long long nblocks = (n_rays + EXP_TILE - 1) / EXP_TILE;
+  FNR_CHECK_ARG(nblocks < (1ll << 31), "depth_points: batch too large");
+  DepthBox box;
+  box.on = box_min != nullptr;
+  for (int a = 0; a < 3; ++a) {
+    box.lo[a] = box.on ? box_min[a] : 0.0f;
+    box.hi[a] = box.on ? box_max[a] : 0.0f;
+  }
+  unsigned long long* bc = reinterpret_cast<unsigned long long*>(workspace);
+  hipStream_t st = as_stream(stream);
+  FNR_PROF(OP_EXPORT_COMPACT, n_rays);
+  hipLaunchKernelGGL(k_depth_count, dim3((unsigned)nblocks), dim3(EXP_BLOCK), 0, st, (long long)n_rays, origins,
+                     directions, depth, box, bc);
+  FNR_LAUNCH_CHECK();
+  // the running total is advanced by export_compact's scan (one set)
+  hipLaunchKernelGGL(k_export_scan, dim3(1), dim3(1024), 0, st, bc, nblocks,
+                     reinterpret_cast<unsigned long long*>(count));
+  FNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_depth_write, dim3((unsigned)nblocks), dim3(EXP_BLOCK), 0, st, (long long)n_rays, origins,
+                     directions, depth, rgb, box, points, colors, (long long)capacity, bc);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }

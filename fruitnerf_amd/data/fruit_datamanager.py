@@ -111,3 +111,20 @@ class ExportDataManager:
         self.train_count += 1
         ray_bundle = self.orthographic_ray_generator(count=self.train_count)
         return ray_bundle, None
+
+
+class TrainRayDataManager:
+    """The slice of the train datamanager Nerfstudio's `pointcloud` export drives: `next_train(step)` -> (RayBundle,
+    batch) of `num_rays_per_batch` random training pixels, drawn by a data/synthetic_apple.py::PixelBatcher (pixel
+    sampling + ray generation in one launch on the device)."""
+
+    def __init__(self, batcher, num_rays_per_batch: int = 4096):
+        self.batcher = batcher
+        self.num_rays_per_batch = int(num_rays_per_batch)
+        self.train_count = 0
+
+    def next_train(self, step: int):
+        from ..rays import RayBundle
+        self.train_count += 1
+        origins, directions, camera_indices, batch = self.batcher.sample(self.num_rays_per_batch)
+        return RayBundle(origins, directions, None, camera_indices), batch

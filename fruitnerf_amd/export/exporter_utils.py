@@ -150,3 +150,67 @@ def sample_volume(pipeline, num_points: int, output_dir: Optional[Path] = None, 
             path = str(Path(output_dir) / config.load_dir.parts[-3] / f"{name}.ply")
         pcd_list[name] = {"points": p.numpy(), "colors": c.double().numpy()[:, :3], "path": path}
     return pcd_list
+
+
+def generate_point_cloud(pipeline, num_points: int = 1_000_000, remove_outliers: bool = True,
+                         estimate_normals: bool = False, rgb_output_name: str = "rgb",
+                         depth_output_name: str = "depth", use_bounding_box: bool = True,
+                         bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
+                         std_ratio: float = 10.0):
+    """Nerfstudio's generate_point_cloud (what `ns-export pointcloud` / the reference's `pointcloud` subcommand runs,
+    scripts/exporter.py:49,124-129): random training rays -> a point at origin + direction * depth per ray, coloured
+    with the rendered rgb -> the points strictly inside the bounding box -> Open3D's remove_statistical_outlier(20,
+    std_ratio) -> optionally estimate_normals().  -> clustering.PointCloud (float64 points / colours on the device).
+
+    `pipeline` needs `.datamanager.next_train(step)` -> (ray bundle, batch) (data/fruit_datamanager.py::
+    TrainRayDataManager) and `.model(ray_bundle)` -> outputs.  Batches are drawn until at least `num_points` points are
+    collected and the whole last batch is kept, as Nerfstudio does.  The points of a batch are formed, masked and
+    appended to a device buffer by fnr_depth_points; the host reads the running count once per batch (Nerfstudio
+    advances its progress bar there).  Nerfstudio's normal_method="model_output" has no counterpart: this field
+    predicts no normals, so the parameter is absent and normals always come from the cloud."""
+    from ..clustering.clustering_base import PointCloud
+    dev = pipeline.model.device
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    points = colors = None
+    have = 0
+    lo = bounding_box_min if use_bounding_box else None
+    hi = bounding_box_max if use_bounding_box else None
+    while have < num_points:
+        with torch.no_grad():
+            ray_bundle, _ = pipeline.datamanager.next_train(0)
+            outputs = pipeline.model(ray_bundle)
+        for name in (rgb_output_name, depth_output_name):
+            if name not in outputs:
+                raise KeyError(f"Could not find {name} in the model outputs; choose from {list(outputs.keys())}")
+        depth = outputs[depth_output_name].reshape(-1)
+        need = have + depth.numel()                      # a batch appends at most one point per ray
+        if points is None or need > points.shape[0]:
+            cap = max(need, 2 * (0 if points is None else points.shape[0]), num_points + depth.numel())
+            grown = [torch.empty(cap, 3, device=dev) for _ in range(2)]
+            if points is not None:
+                grown[0][:have], grown[1][:have] = points[:have], colors[:have]
+            points, colors = grown
+        K.depth_points(ray_bundle.origins, ray_bundle.directions, depth, outputs[rgb_output_name], lo, hi, points,
+                       colors, count)
+        got = int(count.item())
+        if got == have and depth.numel() == 0:
+            raise RuntimeError("generate_point_cloud: the datamanager returned an empty batch")
+        have = got
+    pcd = PointCloud(points[:have].double(), colors[:have].double(), dev)
+    if remove_outliers:
+        pcd, _ = pcd.remove_statistical_outlier(nb_neighbors=20, std_ratio=std_ratio)
+    if estimate_normals:
+        pcd.estimate_normals()
+    return pcd
+
+
+def export_point_cloud(pipeline, output_dir, **kwargs):
+    """ExportPointCloud.main: generate_point_cloud(pipeline, **kwargs) written to <output_dir>/point_cloud.ply (binary
+    PLY in Open3D's layout, colours quantised to uchar, normals when they were estimated).  -> the PointCloud."""
+    from . import ply
+    pcd = generate_point_cloud(pipeline, **kwargs)
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    ply.write_point_cloud(str(out / "point_cloud.ply"), pcd.points.cpu().numpy(), pcd.colors.cpu().numpy(),
+                          None if pcd.normals is None else pcd.normals.cpu().numpy())
+    return pcd

@@ -2,29 +2,38 @@
 PointCloud with points + colors (what /root/reference/fruit_nerf/scripts/exporter.py:116-119 calls on the three
 sets of `sample_volume`), so the reference's clustering stage (clustering/*.py: `o3d.io.read_point_cloud`) can read
 our exports unchanged.  open3d is not installed here: vertex = double x, y, z + uchar red, green, blue,
-little-endian, colours quantised as round(clamp(c, 0, 1) * 255)."""
+little-endian, colours quantised as round(clamp(c, 0, 1) * 255).  A cloud with normals (Nerfstudio's `pointcloud`
+export after estimate_normals) gains double nx, ny, nz between position and colour, as Open3D writes it."""
 from __future__ import annotations
 
 import os
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
 _VERTEX = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_VERTEX_NORMALS = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8"),
+                            ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 
 
-def write_point_cloud(path: str, points: np.ndarray, colors: np.ndarray) -> None:
+def write_point_cloud(path: str, points: np.ndarray, colors: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
     points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     colors = np.asarray(colors, dtype=np.float64).reshape(-1, 3)
     if points.shape[0] != colors.shape[0]:
         raise ValueError(f"{points.shape[0]} points but {colors.shape[0]} colours")
-    v = np.empty(points.shape[0], dtype=_VERTEX)
+    v = np.empty(points.shape[0], dtype=_VERTEX if normals is None else _VERTEX_NORMALS)
     v["x"], v["y"], v["z"] = points[:, 0], points[:, 1], points[:, 2]
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+        if normals.shape[0] != points.shape[0]:
+            raise ValueError(f"{points.shape[0]} points but {normals.shape[0]} normals")
+        v["nx"], v["ny"], v["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     q = np.rint(np.clip(colors, 0.0, 1.0) * 255.0).astype(np.uint8)
     v["red"], v["green"], v["blue"] = q[:, 0], q[:, 1], q[:, 2]
     header = ("ply\nformat binary_little_endian 1.0\ncomment Created by Open3D\n"
               f"element vertex {points.shape[0]}\n"
               "property double x\nproperty double y\nproperty double z\n"
+              + ("" if normals is None else "property double nx\nproperty double ny\nproperty double nz\n") +
               "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as f:
@@ -32,10 +41,12 @@ def write_point_cloud(path: str, points: np.ndarray, colors: np.ndarray) -> None
         f.write(v.tobytes())
 
 
-def read_point_cloud(path: str) -> Tuple[np.ndarray, np.ndarray]:
-    """Reader for files written by write_point_cloud (tests, count checks): points float64 [n,3], colours in [0,1]."""
+def read_point_cloud(path: str):
+    """Reader for files written by write_point_cloud (tests, count checks): points float64 [n,3], colours in [0,1];
+    a file with normals returns (points, colours, normals float64 [n,3])."""
     with open(path, "rb") as f:
         n = None
+        has_normals = False
         while True:
             line = f.readline()
             if not line:
@@ -45,11 +56,16 @@ def read_point_cloud(path: str) -> Tuple[np.ndarray, np.ndarray]:
                 raise ValueError(f"{path}: only binary_little_endian PLY is supported")
             if line.startswith("element vertex"):
                 n = int(line.split()[-1])
+            if line == "property double nx":
+                has_normals = True
             if line == "end_header":
                 break
-        v = np.frombuffer(f.read(n * _VERTEX.itemsize), dtype=_VERTEX, count=n)
+        dtype = _VERTEX_NORMALS if has_normals else _VERTEX
+        v = np.frombuffer(f.read(n * dtype.itemsize), dtype=dtype, count=n)
     pts = np.stack([v["x"], v["y"], v["z"]], axis=1)
     cols = np.stack([v["red"], v["green"], v["blue"]], axis=1).astype(np.float64) / 255.0
+    if has_normals:
+        return pts, cols, np.stack([v["nx"], v["ny"], v["nz"]], axis=1)
     return pts, cols
 
 

@@ -876,6 +876,14 @@ int fnr_export_compact(const fnr_lattice* lat, int64_t ray_begin, int64_t n_rays
                        int64_t n_positions, const float* density,
                        const float* rgb, const float* logit, float* const points[3], float* const colors[3],
                        int64_t capacity, uint64_t* counts, void* workspace, void* stream);
+/* Nerfstudio's generate_point_cloud, one batch: point = origins + directions * depth (fp32, the product and the sum
+ * rounded separately, like torch); kept when every coordinate lies strictly inside (box_min, box_max) — HOST pointers to
+ * 3 floats, both NULL: everything is kept.  Kept points and their rgb are appended in ray order to points / colors
+ * [capacity][3] at the running total *count (device uint64), which this call advances; entries beyond `capacity` are
+ * counted but not written.  workspace: >= fnr_export_workspace_bytes(n_rays) bytes. */
+int fnr_depth_points(const float* origins, const float* directions, const float* depth, const float* rgb,
+                     int64_t n_rays, const float* box_min, const float* box_max, float* points, float* colors,
+                     int64_t capacity, uint64_t* count, void* workspace, void* stream);
 
 /* ---- point-cloud front-end of the counting stage ---------------------------------------------- */
 /* FruitClustering.cluster (clustering/clustering_base.py:183-207) runs, on the exported cloud, Open3D's
@@ -903,6 +911,30 @@ int fnr_cloud_dbscan(const double* xyz, int64_t n, const double* lo, const doubl
 int fnr_cloud_voxel_down_sample(const double* xyz, const double* rgb, int64_t n, const double* min_bound,
                                 const double* max_bound, double voxel_size, double* xyz_out, double* rgb_out,
                                 int32_t* n_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- k nearest neighbours on a cloud: the Open3D calls of Nerfstudio's `pointcloud` export ----- */
+/* ExportPointCloud (the `pointcloud` subcommand scripts/exporter.py:49,124-129 registers) cleans its cloud with Open3D's
+ * remove_statistical_outlier(nb_neighbors=20, std_ratio) and estimate_normals(); both are kNN queries.  Clouds, lo / hi
+ * and the workspace are as above (workspace >= fnr_cloud_knn_workspace_bytes(n, k)); 1 <= k <= FNR_CLOUD_KNN_MAX.
+ * The search is exact and its results are functions of the input alone (csrc/cloud_knn.hip). */
+#define FNR_CLOUD_KNN_MAX 32
+size_t fnr_cloud_knn_workspace_bytes(int64_t n_points, int32_t k);
+/* Row i of dist2 [n][k] / index [n][k] (either nullable): the k points nearest to point i, itself included, ascending
+ * by squared distance ((dx*dx) + dy*dy) + dz*dz (fp64, every operation rounded), ties by ascending input index.
+ * n < k: the first n entries are valid, the rest +inf / -1.  n == 0 launches nothing. */
+int fnr_cloud_knn(const double* xyz, int64_t n, const double* lo, const double* hi, int32_t k, double* dist2,
+                  int32_t* index, void* workspace, size_t workspace_bytes, void* stream);
+/* Open3D RemoveStatisticalOutliers(nb_neighbors, std_ratio): avg_distance[n] = mean of the distances to the nb_neighbors
+ * nearest points (self included); over the points with avg > 0: mean, std (n_valid - 1 in the denominator), threshold =
+ * mean + std_ratio * std; keep[n] (uint8) = avg > 0 && avg < threshold; stats[3] (device) = mean, std, threshold.
+ * The global sums run in a fixed order: the same cloud gives the same bits.  nb_neighbors < 1 or std_ratio <= 0: error. */
+int fnr_cloud_statistical_outlier(const double* xyz, int64_t n, const double* lo, const double* hi,
+                                  int32_t nb_neighbors, double std_ratio, double* avg_distance, uint8_t* keep,
+                                  double* stats, void* workspace, size_t workspace_bytes, void* stream);
+/* Open3D EstimateNormals(KDTreeSearchParamKNN(knn)): normals[n][3] = unit eigenvector of the smallest eigenvalue of the
+ * covariance of the knn nearest points (self included); fewer than 3 of them: (0, 0, 1).  The sign is not oriented. */
+int fnr_cloud_estimate_normals(const double* xyz, int64_t n, const double* lo, const double* hi, int32_t knn,
+                               double* normals, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- eval-image metrics ------------------------------------------------------------------------ */
 /* FruitModel.get_image_metrics_and_images (fruit_nerf/fruit_nerf.py:403-458) on the device: everything the reference
