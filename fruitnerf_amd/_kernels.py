@@ -360,6 +360,35 @@ def field_mlp_fwd(net: L.fnr_field_net, rays: RaysArg, S: int, feats: Tensor, se
     return density, rgb, logit, geo
 
 
+def field_normals(net: L.fnr_field_net, feats: Tensor, jacobian: Tensor, selector: Tensor, want_gradient: bool = False):
+    """feats [L,N,2], jacobian [L,3,N,2], selector [N] of hash_encode_fwd(want_jacobian=True) -> normals [N,3]
+    (+ the unnormalised gradient [N,3])."""
+    lib = L.load()
+    dev = feats.device
+    N = selector.numel()
+    assert feats.shape == (net.grid.n_levels, N, 2) and jacobian.shape == (net.grid.n_levels, 3, N, 2) \
+        and feats.dtype == jacobian.dtype == torch.float32 and selector.dtype == torch.uint8
+    normals = _empty(N, 3, device=dev)
+    gradient = _empty(N, 3, device=dev) if want_gradient else None
+    L.check(lib.fnr_field_normals(C.byref(net), N, L.ptr(feats), L.ptr(jacobian), L.ptr(selector), L.ptr(normals),
+                                  L.ptr(gradient), L.stream_ptr(dev)), "field_normals")
+    return (normals, gradient) if want_gradient else normals
+
+
+def render_normals(weights: Tensor, normals: Tensor, S: int, shade: bool) -> Tensor:
+    """weights [R,S], normals [R*S,3] -> the rendered normal per ray [R,3] (shade: mapped to [0,1])."""
+    lib = L.load()
+    dev = weights.device
+    w, nr = _f32c(weights.reshape(-1, S)), _f32c(normals.reshape(-1, 3))
+    R = w.shape[0]
+    assert nr.shape[0] == R * S
+    out = _empty(R, 3, device=dev)
+    if R:
+        L.check(lib.fnr_render_normals(R, S, L.ptr(w), L.ptr(nr), int(bool(shade)), L.ptr(out), L.stream_ptr(dev)),
+                "render_normals")
+    return out
+
+
 def embedding_mean(embedding: Tensor) -> Tensor:
     lib = L.load()
     out = _empty(embedding.shape[1], device=embedding.device)
@@ -492,10 +521,12 @@ def export_compact(lat: Optional[LatticeArg], ray_begin: int, n_rays: int, posit
 
 
 def depth_points(origins: Tensor, directions: Tensor, depth: Tensor, rgb: Tensor, box_min, box_max, points: Tensor,
-                 colors: Tensor, count: Tensor) -> None:
+                 colors: Tensor, count: Tensor, normals: Optional[Tensor] = None,
+                 normals_out: Optional[Tensor] = None) -> None:
     """Appends origin + direction * depth (fp32, torch's bits) and rgb of the rays whose point lies strictly inside the
     box (box_min / box_max: 3 floats each, or both None) to points / colors [capacity,3] in ray order; `count` (uint64,
-    stored as int64 [1] on the device) is the running total."""
+    stored as int64 [1] on the device) is the running total.  normals [R,3] + normals_out [capacity,3] (together): the
+    per-ray attribute of fnr_depth_points_normals travels with its point."""
     lib = L.load()
     dev = depth.device
     R = depth.numel()
@@ -508,8 +539,17 @@ def depth_points(origins: Tensor, directions: Tensor, depth: Tensor, rgb: Tensor
     ws = _empty(lib.fnr_export_workspace_bytes(R), dtype=torch.uint8, device=dev)
     lo = None if box_min is None else (C.c_float * 3)(*[float(v) for v in box_min])
     hi = None if box_max is None else (C.c_float * 3)(*[float(v) for v in box_max])
-    L.check(lib.fnr_depth_points(L.ptr(o), L.ptr(d), L.ptr(t), L.ptr(c), R, lo, hi, L.ptr(points), L.ptr(colors),
-                                 points.shape[0], L.ptr(count), L.ptr(ws), L.stream_ptr(dev)), "depth_points")
+    if normals is None:
+        assert normals_out is None
+        L.check(lib.fnr_depth_points(L.ptr(o), L.ptr(d), L.ptr(t), L.ptr(c), R, lo, hi, L.ptr(points), L.ptr(colors),
+                                     points.shape[0], L.ptr(count), L.ptr(ws), L.stream_ptr(dev)), "depth_points")
+        return
+    nr = _f32c(normals.reshape(-1, 3))
+    assert nr.shape[0] == R and normals_out is not None and normals_out.shape == points.shape \
+        and normals_out.is_contiguous() and normals_out.dtype == torch.float32
+    L.check(lib.fnr_depth_points_normals(L.ptr(o), L.ptr(d), L.ptr(t), L.ptr(c), L.ptr(nr), R, lo, hi, L.ptr(points),
+                                         L.ptr(colors), L.ptr(normals_out), points.shape[0], L.ptr(count), L.ptr(ws),
+                                         L.stream_ptr(dev)), "depth_points_normals")
 
 
 # ---- training ---------------------------------------------------------------------------------------

@@ -266,6 +266,10 @@ SIGNATURES = {
     "fnr_export_compact": (_i, [P(fnr_lattice), _i64, _i64, _vp, _i64, _vp, _vp, _vp, P(_vp), P(_vp), _i64, _vp, _vp,
                                 _vp]),
     "fnr_depth_points": (_i, [_vp, _vp, _vp, _vp, _i64, P(C.c_float), P(C.c_float), _vp, _vp, _i64, _vp, _vp, _vp]),
+    "fnr_depth_points_normals": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, P(C.c_float), P(C.c_float), _vp, _vp, _vp, _i64, _vp,
+                                      _vp, _vp]),
+    "fnr_field_normals": (_i, [P(fnr_field_net), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fnr_render_normals": (_i, [_i64, _i, _vp, _vp, _i, _vp, _vp]),
     "fnr_cloud_knn_workspace_bytes": (C.c_size_t, [_i64, C.c_int32]),
     "fnr_cloud_knn": (_i, [_vp, _i64, P(C.c_double), P(C.c_double), C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fnr_cloud_statistical_outlier": (_i, [_vp, _i64, P(C.c_double), P(C.c_double), C.c_int32, C.c_double, _vp, _vp, _vp,

@@ -207,12 +207,15 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_depth_count(long long R, const fl
   if (threadIdx.x == 0) block_counts[blockIdx.x] = s_cnt;
 }
 
+// ATTR: one more per-ray attribute [R,3] (fnr_depth_points_normals) travels with rgb: same mask, order and running count
+template <bool ATTR>
 __global__ __launch_bounds__(EXP_BLOCK) void k_depth_write(long long R, const float* __restrict__ origins,
                                                            const float* __restrict__ directions,
                                                            const float* __restrict__ depth,
-                                                           const float* __restrict__ rgb, DepthBox box,
+                                                           const float* __restrict__ rgb,
+                                                           const float* __restrict__ attr, DepthBox box,
                                                            float* __restrict__ points, float* __restrict__ colors,
-                                                           long long capacity,
+                                                           float* __restrict__ attr_out, long long capacity,
                                                            const unsigned long long* __restrict__ block_offsets) {
   __shared__ unsigned s_wave[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -246,6 +249,7 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_depth_write(long long R, const fl
       for (int a = 0; a < 3; ++a) {
         points[3 * at + a] = p[q][a];
         colors[3 * at + a] = rgb[3 * r + a];
+        if constexpr (ATTR) attr_out[3 * at + a] = attr[3 * r + a];
       }
     }
   }
@@ -303,17 +307,17 @@ extern "C" int fnr_export_compact(const fnr_lattice* lat, int64_t ray_begin, int
   return FNR_OK;
 }
 
-extern "C" int fnr_depth_points(const float* origins, const float* directions, const float* depth, const float* rgb,
-                                int64_t n_rays, const float* box_min, const float* box_max, float* points,
-                                float* colors, int64_t capacity, uint64_t* count, void* workspace, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_depth_points");
-  FNR_CHECK_ARG(origins && directions && depth && rgb && points && colors && count && workspace,
-                "depth_points: null argument");
-  FNR_CHECK_ARG((box_min == nullptr) == (box_max == nullptr), "depth_points: box_min and box_max go together");
-  FNR_CHECK_ARG(n_rays >= 0 && capacity >= 0, "depth_points: n_rays / capacity < 0");
+// fnr_depth_points / fnr_depth_points_normals: attr and attr_out both NULL, or both set
+static int depth_points_launch(const char* who, const float* origins, const float* directions, const float* depth,
+                               const float* rgb, const float* attr, int64_t n_rays, const float* box_min,
+                               const float* box_max, float* points, float* colors, float* attr_out, int64_t capacity,
+                               uint64_t* count, void* workspace, void* stream) {
+  FNR_CHECK_ARG(origins && directions && depth && rgb && points && colors && count && workspace, "%s: null argument", who);
+  FNR_CHECK_ARG((box_min == nullptr) == (box_max == nullptr), "%s: box_min and box_max go together", who);
+  FNR_CHECK_ARG(n_rays >= 0 && capacity >= 0, "%s: n_rays / capacity < 0", who);
   if (n_rays == 0) return FNR_OK;
   const long long nblocks = (n_rays + EXP_TILE - 1) / EXP_TILE;
-  FNR_CHECK_ARG(nblocks < (1ll << 31), "depth_points: batch too large");
+  FNR_CHECK_ARG(nblocks < (1ll << 31), "%s: batch too large", who);
   DepthBox box;
   box.on = box_min != nullptr;
   for (int a = 0; a < 3; ++a) {
@@ -330,8 +334,30 @@ extern "C" int fnr_depth_points(const float* origins, const float* directions, c
   hipLaunchKernelGGL(k_export_scan, dim3(1), dim3(1024), 0, st, bc, nblocks,
                      reinterpret_cast<unsigned long long*>(count));
   FNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_depth_write, dim3((unsigned)nblocks), dim3(EXP_BLOCK), 0, st, (long long)n_rays, origins,
-                     directions, depth, rgb, box, points, colors, (long long)capacity, bc);
+  if (attr)
+    hipLaunchKernelGGL(k_depth_write<true>, dim3((unsigned)nblocks), dim3(EXP_BLOCK), 0, st, (long long)n_rays, origins,
+                       directions, depth, rgb, attr, box, points, colors, attr_out, (long long)capacity, bc);
+  else
+    hipLaunchKernelGGL(k_depth_write<false>, dim3((unsigned)nblocks), dim3(EXP_BLOCK), 0, st, (long long)n_rays, origins,
+                       directions, depth, rgb, attr, box, points, colors, attr_out, (long long)capacity, bc);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
+}
+
+extern "C" int fnr_depth_points(const float* origins, const float* directions, const float* depth, const float* rgb,
+                                int64_t n_rays, const float* box_min, const float* box_max, float* points,
+                                float* colors, int64_t capacity, uint64_t* count, void* workspace, void* stream) {
+  FNR_SEQ_UNRECORDABLE("fnr_depth_points");
+  return depth_points_launch("depth_points", origins, directions, depth, rgb, nullptr, n_rays, box_min, box_max, points,
+                             colors, nullptr, capacity, count, workspace, stream);
+}
+
+extern "C" int fnr_depth_points_normals(const float* origins, const float* directions, const float* depth,
+                                        const float* rgb, const float* normals, int64_t n_rays, const float* box_min,
+                                        const float* box_max, float* points, float* colors, float* normals_out,
+                                        int64_t capacity, uint64_t* count, void* workspace, void* stream) {
+  FNR_SEQ_UNRECORDABLE("fnr_depth_points_normals");
+  FNR_CHECK_ARG(normals && normals_out, "depth_points_normals: null argument");
+  return depth_points_launch("depth_points_normals", origins, directions, depth, rgb, normals, n_rays, box_min, box_max,
+                             points, colors, normals_out, capacity, count, workspace, stream);
 }

@@ -156,7 +156,7 @@ def generate_point_cloud(pipeline, num_points: int = 1_000_000, remove_outliers:
                          estimate_normals: bool = False, rgb_output_name: str = "rgb",
                          depth_output_name: str = "depth", use_bounding_box: bool = True,
                          bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
-                         std_ratio: float = 10.0):
+                         std_ratio: float = 10.0, normal_method: str = "open3d", normal_output_name: str = "normals"):
     """Nerfstudio's generate_point_cloud (what `ns-export pointcloud` / the reference's `pointcloud` subcommand runs,
     scripts/exporter.py:49,124-129): random training rays -> a point at origin + direction * depth per ray, coloured
     with the rendered rgb -> the points strictly inside the bounding box -> Open3D's remove_statistical_outlier(20,
@@ -166,12 +166,20 @@ def generate_point_cloud(pipeline, num_points: int = 1_000_000, remove_outliers:
     TrainRayDataManager) and `.model(ray_bundle)` -> outputs.  Batches are drawn until at least `num_points` points are
     collected and the whole last batch is kept, as Nerfstudio does.  The points of a batch are formed, masked and
     appended to a device buffer by fnr_depth_points; the host reads the running count once per batch (Nerfstudio
-    advances its progress bar there).  Nerfstudio's normal_method="model_output" has no counterpart: this field
-    predicts no normals, so the parameter is absent and normals always come from the cloud."""
+    advances its progress bar there).
+
+    normal_method (Nerfstudio's argument, as recalled): "open3d" — normals come from the cloud, if `estimate_normals`
+    asks for them (unoriented); "model_output" — the model output `normal_output_name` (FruitNerfModelConfig.
+    render_normals: analytic normals shaded to [0,1]) is mapped back by 2 n - 1 and travels with its point through the
+    bounding-box mask (fnr_depth_points_normals) and the outlier removal into `pcd.normals` (float64, oriented);
+    `estimate_normals` is then ignored.  A missing output is a KeyError, values outside [0,1] a ValueError."""
     from ..clustering.clustering_base import PointCloud
+    if normal_method not in ("open3d", "model_output"):
+        raise ValueError(f"normal_method {normal_method!r}: one of 'open3d', 'model_output'")
+    model_normals = normal_method == "model_output"
     dev = pipeline.model.device
     count = torch.zeros(1, dtype=torch.int64, device=dev)
-    points = colors = None
+    points = colors = normals = None
     have = 0
     lo = bounding_box_min if use_bounding_box else None
     hi = bounding_box_max if use_bounding_box else None
@@ -182,24 +190,38 @@ def generate_point_cloud(pipeline, num_points: int = 1_000_000, remove_outliers:
         for name in (rgb_output_name, depth_output_name):
             if name not in outputs:
                 raise KeyError(f"Could not find {name} in the model outputs; choose from {list(outputs.keys())}")
+        ray_normals = None
+        if model_normals:
+            if normal_output_name not in outputs:
+                raise KeyError(f"Could not find {normal_output_name} in the model outputs; choose from "
+                               f"{list(outputs.keys())}")
+            ray_normals = outputs[normal_output_name].reshape(-1, 3)
+            if ray_normals.numel() and not bool(((ray_normals >= 0.0) & (ray_normals <= 1.0)).all()):
+                raise ValueError(f"the model output {normal_output_name} must lie in [0, 1] (shaded normals)")
+            ray_normals = ray_normals * 2.0 - 1.0
         depth = outputs[depth_output_name].reshape(-1)
         need = have + depth.numel()                      # a batch appends at most one point per ray
         if points is None or need > points.shape[0]:
             cap = max(need, 2 * (0 if points is None else points.shape[0]), num_points + depth.numel())
-            grown = [torch.empty(cap, 3, device=dev) for _ in range(2)]
+            grown = [torch.empty(cap, 3, device=dev) for _ in range(3 if model_normals else 2)]
             if points is not None:
                 grown[0][:have], grown[1][:have] = points[:have], colors[:have]
-            points, colors = grown
+                if model_normals:
+                    grown[2][:have] = normals[:have]
+            points, colors = grown[:2]
+            normals = grown[2] if model_normals else None
         K.depth_points(ray_bundle.origins, ray_bundle.directions, depth, outputs[rgb_output_name], lo, hi, points,
-                       colors, count)
+                       colors, count, normals=ray_normals, normals_out=normals)
         got = int(count.item())
         if got == have and depth.numel() == 0:
             raise RuntimeError("generate_point_cloud: the datamanager returned an empty batch")
         have = got
     pcd = PointCloud(points[:have].double(), colors[:have].double(), dev)
+    if model_normals:
+        pcd.normals = normals[:have].double()
     if remove_outliers:
         pcd, _ = pcd.remove_statistical_outlier(nb_neighbors=20, std_ratio=std_ratio)
-    if estimate_normals:
+    if estimate_normals and not model_normals:
         pcd.estimate_normals()
     return pcd
 

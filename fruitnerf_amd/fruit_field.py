@@ -22,10 +22,12 @@ from .rays import RaySamples
 
 
 class FieldHeadNames(Enum):
-    """nerfstudio.field_components.field_heads.FieldHeadNames (the three members FruitField emits)."""
+    """nerfstudio.field_components.field_heads.FieldHeadNames (the members FruitField emits; NORMALS only on request:
+    forward(compute_normals=True))."""
     RGB = "rgb"
     DENSITY = "density"
     SEMANTICS = "semantics"
+    NORMALS = "normals"
 
 
 class SceneContraction(nn.Module):
@@ -317,12 +319,24 @@ class FruitField(nn.Module):
         return h[:, 0].reshape(*shape, 1)
 
     def get_normals(self) -> Tensor:
-        """nerfstudio Field.get_normals differentiates `_density_before_activation` with respect to `_sample_locations`
-        through autograd.  Here both are produced on demand by kernels (no autograd graph joins them), and no FruitNeRF
-        code path asks for normals (the reference constructs the field without predict_normals): unsupported, loudly."""
-        raise NotImplementedError("FruitField.get_normals: normals are not built (FruitNeRF never computes them; "
-                                  "_sample_locations / _density_before_activation are kernel outputs without an autograd "
-                                  "graph between them)")
+        """nerfstudio Field.get_normals: -normalize(d `_density_before_activation` / d `_sample_locations`) [..., 3] for the
+        ray samples of the last get_density / forward, detached.  Nerfstudio differentiates through autograd; here the
+        gradient is analytic (fnr_field_normals: the base MLP's input gradient of the density logit contracted with the
+        input Jacobian the encode saves), evaluated on demand like the two attributes — a field query that never asks
+        for normals pays nothing.  Samples outside the unit cube get 0."""
+        rs = getattr(self, "_last_ray_samples", None)
+        if rs is None:
+            raise AttributeError("get_normals needs the ray samples of a get_density / forward call")
+        with torch.no_grad():
+            if getattr(rs, "_structured", None) is not None:
+                rays, euclid, S = rs._structured
+                shape = (rays.n, S)
+            else:
+                rays, euclid, S, shape = self._flatten(rs)
+            net = self.net_struct()
+            feats, selector, jac = K.hash_encode_fwd(net.grid, self.warp_struct(), rays, euclid, S, want_jacobian=True)
+            normals = K.field_normals(net, feats, jac, selector)
+        return normals.view(*shape, 3)
 
     def release_last_samples(self) -> None:
         """Drop the references get_density keeps for _sample_locations / _density_before_activation / get_outputs (the
@@ -347,8 +361,13 @@ class FruitField(nn.Module):
                               render_rgb: bool = False):
         return self._outputs_from_last(ray_samples, density_embedding)
 
-    def forward(self, ray_samples: RaySamples) -> Dict[FieldHeadNames, Tensor]:
+    def forward(self, ray_samples: RaySamples, compute_normals: bool = False) -> Dict[FieldHeadNames, Tensor]:
         """fruit_field.py:283-301.  Differentiable w.r.t. the field's parameters in training mode (see get_density);
-        FruitModel's own training step uses the fused render function, which also covers compositing."""
+        FruitModel's own training step uses the fused render function, which also covers compositing.
+        compute_normals (nerfstudio Field.forward's argument): adds FieldHeadNames.NORMALS = get_normals() (detached);
+        the other entries are the same launches and bits."""
         density, rgb, logit, _ = self._evaluate(ray_samples, want_geo=False)
-        return {FieldHeadNames.SEMANTICS: logit, FieldHeadNames.RGB: rgb, FieldHeadNames.DENSITY: density}
+        out = {FieldHeadNames.SEMANTICS: logit, FieldHeadNames.RGB: rgb, FieldHeadNames.DENSITY: density}
+        if compute_normals:
+            out[FieldHeadNames.NORMALS] = self.get_normals()
+        return out

@@ -68,6 +68,9 @@ class FruitNerfModelConfig:
     eval_num_rays_per_chunk: int = 1 << 15
     mlp_precision: Optional[str] = None   # "auto" | "fp32" | "bf16x3" | "bf16" (FruitField.mlp_precision; None: env / auto)
     eval_outputs_on_cpu: bool = False   # True: full-image eval returns CPU tensors like the reference (fruit_nerf.py:245)
+    # Nerfacto's outputs["normals"] from ANALYTIC normals (the reference's predict_normals is off and it renders none):
+    # outside training, get_outputs and the 'inference' mode add "normals" [R,3] in [0,1] (FruitModel._render)
+    render_normals: bool = False
     # FruitNerfModelConfig proper
     semantic_loss_weight: float = 1.0
     pass_semantic_gradients: bool = False
@@ -432,7 +435,11 @@ class FruitModel(nn.Module):
         """ProposalNetworkSampler.generate_ray_samples + field + weights + renderers (fruit_nerf.py:316-357).
         loss_targets = (image [R,3], fruit_mask [R,1], semantic loss weight), training steps that do not train the proposal networks:
         the compositing launch also runs its own backward under the rgb / semantic losses of get_loss_dict (fnr_composite_fwd_bwd_targets) and the context carries
-        `composite_grads` = (d_density, d_rgb, d_logit) per sample."""
+        `composite_grads` = (d_density, d_rgb, d_logit) per sample.
+        config.render_normals and not training: outputs["normals"] [R,3] = NormalsRenderer over the final level's weights of
+        the field's analytic normals (FruitField.get_normals' kernels on this pass's features), shaded to [0,1] like
+        Nerfacto's outputs["normals"].  The key is ABSENT in training mode (losses on analytic normals would need second
+        derivatives) and in the 'export' mode, which does not render; every other output keeps its launches' bits."""
         self.arena()
         cfg = self.config
         sampler = self.proposal_sampler
@@ -487,8 +494,9 @@ class FruitModel(nn.Module):
         fld = self.field
         net = fld.net_struct()
         # rays with autograd history (camera-pose optimisation) need the encode's input Jacobian in the backward pass
-        want_jac = training and (save_input_jacobian or ray_bundle.origins.requires_grad
-                                 or ray_bundle.directions.requires_grad)
+        want_normals = bool(getattr(cfg, "render_normals", False)) and not training
+        want_jac = want_normals or (training and (save_input_jacobian or ray_bundle.origins.requires_grad
+                                                  or ray_bundle.directions.requires_grad))
         enc = K.hash_encode_fwd(net.grid, fld.warp_struct(), rays, euclid, S, want_jacobian=want_jac)
         feats, selector, jac = enc if want_jac else (enc[0], enc[1], None)
         mean_emb = fld._mean_embedding() if fld._uses_mean_embedding() else None
@@ -525,6 +533,8 @@ class FruitModel(nn.Module):
                    "semantics": sem[:, None]}
         for i in range(n_prop):
             outputs[f"prop_depth_{i}"] = levels[i]["depth"][:, None]
+        if want_normals:
+            outputs["normals"] = K.render_normals(weights, K.field_normals(net, feats, jac, selector), S, shade=True)
         return outputs, ctx
 
     @staticmethod
@@ -620,6 +630,8 @@ class FruitModel(nn.Module):
         outputs = {"rgb": z(0, 3), "accumulation": z(0, 1), "depth": z(0, 1), "semantics": z(0, 1)}
         for i in range(n_prop):
             outputs[f"prop_depth_{i}"] = z(0, 1)
+        if getattr(self.config, "render_normals", False) and not self.training:
+            outputs["normals"] = z(0, 3)
         return outputs, ctx
 
     def _samples_lists(self, ray_bundle: RayBundle, ctx: RenderContext):
@@ -765,6 +777,8 @@ class FruitModel(nn.Module):
             images_dict[f"prop_depth_{i}"] = outputs[f"prop_depth_{i}"].to(dev)
         sem = outputs["semantics"].to(dev)
         images_dict["semantics_colormap"] = torch.sigmoid(sem)
+        if "normals" in outputs:                # config.render_normals: already shaded to [0,1]
+            images_dict["normals"] = outputs["normals"].to(dev)
         mask = batch["fruit_mask"].to(dev)
         images_dict["fruit_mask"] = mask.repeat(1, 1, 3)
         if sem.dim() != 3 or sem.shape[-1] != 1:

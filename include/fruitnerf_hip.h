@@ -387,6 +387,28 @@ int fnr_field_mlp_fwd(const fnr_field_net* net, const fnr_rays* rays, int S, con
 /* embedding_appearance.mean(dim=0) (fruit_field.py:219,256): out [appearance_dim]. */
 int fnr_embedding_mean(const float* embedding, int n_images, int dim, float* out, void* stream);
 
+/* ---- analytic normals (inference side; not recordable: they never run inside a training step) -- */
+/* nerfstudio Field.get_normals (fields/base_field.py), for which FruitField.get_density keeps _sample_locations and
+ * _density_before_activation (fruit_field.py:180-186): autograd of the density logit h0 = mlp_base(x)[..., 0] with
+ * respect to the masked unit-cube sample location, then -F.normalize(gradient, dim=-1).  Per sample, with x [32] the
+ * hash features (column 2 l + j):
+ *   a1 = W_b0 x + b_b0,  v = 1[a1 > 0] * W_b1[0, :],  df = W_b0^T v,
+ *   g[a] = sum_{l,j} jacobian[l][a][n][j] * df[2 l + j],  normal = -g / max(||g||, 1e-12)
+ * feats [L][N][2], jacobian [L][3][N][2] and selector [N] are what fnr_hash_encode_fwd wrote for these samples; the
+ * gradient is with respect to the location AFTER contraction + (x + 2) / 4, or after the AABB normalisation (what
+ * nerfstudio differentiates against): no warp Jacobian enters.  normals [N,3]; gradient (optional) [N,3] receives g.
+ * Unselected samples: g = 0, normal = 0.  float32 fmaf chains whatever net->mlp_mode says (one arithmetic: the same
+ * bits in every mode and from run to run).  Both built shapes (geo_feat_dim 15 | 30; only the base MLP is read). */
+int fnr_field_normals(const fnr_field_net* net, int64_t n_samples, const float* feats, const float* jacobian,
+                      const uint8_t* selector, float* normals, float* gradient, void* stream);
+/* nerfstudio NormalsRenderer (model_components/renderers.py), as recalled: n = sum_s weights[r][s] * normals[r][s][:]
+ * (float32, every product rounded, added one after the other in sample order s = 0 .. S-1), then safe_normalize:
+ * n / (||n|| + 1e-10), ||n|| = sqrt((nx nx + ny ny) + nz nz).  shade != 0 additionally applies NormalsShader,
+ * (n + 1) / 2 (Nerfacto's outputs["normals"]): a ray of zero weights gives 0, shaded 0.5.
+ * weights [R][S] (fnr_composite_fwd's), normals [R][S][3], out [R][3]. */
+int fnr_render_normals(int64_t n_rays, int S, const float* weights, const float* normals, int shade, float* out,
+                       void* stream);
+
 /* ---- compositing ---------------------------------------------------------------------------- */
 /* RaySamples.get_weights + RGBRenderer("last_sample") + AccumulationRenderer + DepthRenderer("median")
  * + SemanticRenderer (fruit_nerf.py:325-348).  training=0 additionally applies nan_to_num / clamp. */
@@ -884,6 +906,14 @@ int fnr_export_compact(const fnr_lattice* lat, int64_t ray_begin, int64_t n_rays
 int fnr_depth_points(const float* origins, const float* directions, const float* depth, const float* rgb,
                      int64_t n_rays, const float* box_min, const float* box_max, float* points, float* colors,
                      int64_t capacity, uint64_t* count, void* workspace, void* stream);
+/* fnr_depth_points with one more per-ray attribute, normals [n_rays][3] (generate_point_cloud with
+ * normal_method="model_output": the rendered normal of a ray belongs to its point): appended to normals_out
+ * [capacity][3] under the same mask, in the same order and at the same running count.  points, colors and *count are
+ * bit-identical to fnr_depth_points on the same input. */
+int fnr_depth_points_normals(const float* origins, const float* directions, const float* depth, const float* rgb,
+                             const float* normals, int64_t n_rays, const float* box_min, const float* box_max,
+                             float* points, float* colors, float* normals_out, int64_t capacity, uint64_t* count,
+                             void* workspace, void* stream);
 
 /* ---- point-cloud front-end of the counting stage ---------------------------------------------- */
 /* FruitClustering.cluster (clustering/clustering_base.py:183-207) runs, on the exported cloud, Open3D's
