@@ -6,6 +6,7 @@ matrices before ray generation and trained from the ray gradients of the hot pat
 libfruitnerf_hip.so (camera_opt.hip); there is no CPU path."""
 from __future__ import annotations
 
+import itertools
 from dataclasses import dataclass
 from typing import Optional
 
@@ -14,6 +15,9 @@ from torch import Tensor, nn
 
 from .. import _kernels as K
 from .. import _lib as L
+
+
+_SERIALS = itertools.count(1)   # CameraAdam.serial
 
 
 def _padded_rows(num_cameras: int, device) -> Tensor:
@@ -123,6 +127,16 @@ class CameraAdam:
         p = camera_optimizer.pose_adjustment
         self.exp_avg = _padded_rows(p.shape[0], p.device)     # padded like the table: step() runs on the whole storages
         self.exp_avg_sq = _padded_rows(p.shape[0], p.device)
+        self.serial = next(_SERIALS)                          # never reused, unlike id()
+
+    def program_fingerprint(self) -> tuple:
+        """Everything a recorded step program (training.TrainingSteps) captures from this object and its CameraOptimizer by
+        value, the per-step scalars (learning rate, step count) aside: which optimiser this is, the addresses of the pose
+        table, its gradient and the two moments, and the hyper-parameters.  Host-only; in-place edits leave it alone."""
+        c = self.cfg
+        p = self.opt.pose_adjustment
+        return (self.serial, p.data_ptr(), None if p.grad is None else p.grad.data_ptr(), self.exp_avg.data_ptr(),
+                self.exp_avg_sq.data_ptr(), self.betas[0], self.betas[1], c.eps, c.weight_decay, self.algorithm)
 
     def fused_step_args(self, grad_scale: float = 1.0):
         """Advance the step count and return the fnr_table_adam of THIS update for a kernel that applies it itself

@@ -11,12 +11,15 @@ Everything is seeded; pure torch so it runs on the HIP device (bench) or the CPU
 """
 from __future__ import annotations
 
+import itertools
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
+
+_BATCHER_SERIALS = itertools.count(1)   # PixelBatcher.serial
 
 
 @dataclass
@@ -195,6 +198,15 @@ class PixelBatcher:
         self.gen = torch.Generator(device=data["images"].device)
         self.gen.manual_seed(seed)
         self._set = None
+        self.serial = next(_BATCHER_SERIALS)     # never reused, unlike id()
+
+    def program_fingerprint(self) -> tuple:
+        """What a recorded step program (training.TrainingSteps) captures from this batcher by value: which batcher it is,
+        the addresses of the image set (images, masks, cameras) and of the training indices, and the seed.  Host-only."""
+        s = self._set
+        d = self.data if s is None else {"images": s.images, "masks": s.masks, "c2w": s.c2w}
+        return (self.serial, d["images"].data_ptr(), d["masks"].data_ptr(), d["c2w"].data_ptr(),
+                self.image_ids.data_ptr(), self.gen.initial_seed())
 
     def camera_table(self):
         """K.CameraTableArg of `cameras` on the image batch's device (None without cameras): what every launch that takes

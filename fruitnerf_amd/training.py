@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import contextlib
 import functools
+import itertools
 import os
 
 from typing import Dict, List, Optional, Tuple
@@ -380,6 +381,7 @@ L_MAX_ADAM_SPANS = 8   # include/fruitnerf_hip.h: FNR_MAX_ADAM_SPANS
 # fnr_table_adam.touched: the fused table steps skip pairs of rows that never received a gradient (their update is exactly
 # zero).  FNR_SPARSE_TOUCH=0 sweeps every row (A/B; results are bit-identical either way, tests/test_gpu_training_parity.py)
 SPARSE_TOUCH_SKIPPING = os.environ.get("FNR_SPARSE_TOUCH", "1") != "0"
+_OPTIMIZER_SERIALS = itertools.count(1)   # FusedAdam.serial
 
 
 class FusedAdam:
@@ -416,7 +418,12 @@ class FusedAdam:
         # does NOT go through the fused table kernels (step_span / step: the exchange path, fuse_table_optimizer=False,
         # scaler_step) makes moments non-zero without setting bits, so those paths drop the span's bitmap and the next
         # fused step rebuilds it from the moments; rebuild_touched() after loading or editing moments from outside.
+        # _touched holds the bitmaps that are VALID; _bitmaps every bitmap ever built.  A dropped bitmap is rebuilt INTO its
+        # tensor (same length, same device), so its address — which a recorded step program holds — never changes;
+        # TrainingSteps calls ensure_touched() ahead of every step, a replayed one included, which never asks for a bitmap.
         self._touched: Dict[int, Tuple[int, Tensor]] = {}
+        self._bitmaps: Dict[int, Tuple[int, Tensor]] = {}
+        self.serial = next(_OPTIMIZER_SERIALS)                 # never reused, unlike id(): see program_fingerprint()
 
     def current_lr(self, name: str) -> float:
         g = self.groups[name]
@@ -443,6 +450,8 @@ class FusedAdam:
     def touched_bitmap(self, table: Tensor, a: int, n: int) -> Optional[Tensor]:
         """The persistent pair bitmap of `table` (arena span [a, a + n)); None when skipping does not apply."""
         if not SPARSE_TOUCH_SKIPPING or self.weight_decay != 0.0 or n % 128 != 0:
+            # the dense sweep this step takes instead sets no bits: whatever bitmap the span had stops covering its moments
+            self._touched.pop(a, None)
             return None
         hit = self._touched.get(a)
         bm = hit[1] if hit is not None and hit[0] == n else None
@@ -452,7 +461,10 @@ class FusedAdam:
             ever = ((m != 0) | (v != 0)).any(dim=1).view(-1, 32)           # [n / 128 words, 32 pairs]
             words = (ever.to(torch.int64) << torch.arange(32, device=ever.device, dtype=torch.int64)).sum(dim=1)
             bm = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()   # same 32 bits
-            self._touched[a] = (n, bm)
+            old = self._bitmaps.get(a)
+            if old is not None and old[0] == n and old[1].device == bm.device:
+                bm = old[1].copy_(bm)       # a dropped bitmap, rebuilt where it was
+            self._touched[a] = self._bitmaps[a] = (n, bm)
         return bm
 
     def _invalidate_touched(self, a: int, b: int) -> None:
@@ -462,9 +474,30 @@ class FusedAdam:
                 del self._touched[ta]
 
     def rebuild_touched(self) -> None:
-        """Forget the bitmaps: they are rebuilt from the moments at the next fused table step (after exp_avg / exp_avg_sq
-        were loaded or edited from outside)."""
+        """Forget the bitmaps: they are rebuilt from the moments ahead of the next fused table step — interpreted or
+        replayed — (after exp_avg / exp_avg_sq were loaded or edited IN PLACE from outside; moments that were assigned new
+        tensors are noticed without it, see program_fingerprint())."""
         self._touched.clear()
+
+    def ensure_touched(self) -> None:
+        """Rebuild, from the moments and in place, every bitmap that was dropped since it was built.  TrainingSteps calls
+        this ahead of every step: a replayed step never calls touched_bitmap(), it only holds the bitmap's address.  One
+        comparison when nothing was dropped; torch launches (outside any recording) only after a drop."""
+        if len(self._touched) != len(self._bitmaps) and SPARSE_TOUCH_SKIPPING and self.weight_decay == 0.0:
+            for a, (n, _) in list(self._bitmaps.items()):
+                if a not in self._touched:
+                    self.touched_bitmap(None, a, n)
+
+    def program_fingerprint(self) -> tuple:
+        """Everything a recorded step program (TrainingSteps) captures from this object by value — and that is not one of
+        the per-step scalars a replay patches (learning rates, step counts): which optimiser this is (a serial number;
+        id() is reused once an object is collected), the moments' addresses, the hyper-parameters, and which sparse-touch
+        bitmaps are valid at which address.  Host-only and cheap: it launches nothing and builds no bitmap.  In-place
+        edits of the moments leave it alone — rebuild_touched() is the call for those."""
+        sparse = SPARSE_TOUCH_SKIPPING and self.weight_decay == 0.0      # (else every table step sweeps densely: no bitmap)
+        return (self.serial, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                self.weight_decay, self.algorithm, bool(self.skip_groups_without_grad),
+                tuple(sorted((a, t[1].data_ptr()) for a, t in self._touched.items())) if sparse else ())
 
     def table_adam_args(self, table: Tensor, group: str = "fields", grad_scale: float = 1.0):
         """fnr_table_adam for the NEXT update of `table` (a parameter of `group` that lives in the arena): learning
@@ -1388,6 +1421,7 @@ NATIVE_SEQUENCER = os.environ.get("FNR_NATIVE_SEQUENCER", "1") != "0"
 # recording must not contain (a scatter workspace's first use is also caught per step: K.fresh_workspaces)
 RECORD_ON_OCCURRENCE = 1
 RECORD_FROM_STEP = 2
+MAX_PROGRAMS = 64          # recorded programs a loop keeps (TrainingSteps._forget_unreachable)
 
 
 class _StepProgram:
@@ -1442,6 +1476,7 @@ class TrainingSteps:
         self._arenas = None
         self._arena_version = 0
         self._next_layout = None        # (arena version, parity, offset behind the look-ahead, clean) of what _next points into
+        self._fingerprint = None        # _captured_fingerprint() of the last keyed step (_forget_unreachable)
         self._programs = {}             # key -> _StepProgram
         self._unrecordable = {}         # key -> reason
         self._seen = {}                 # key -> interpreted occurrences
@@ -1468,8 +1503,14 @@ class TrainingSteps:
         self._next_layout = None
 
     def drop_programs(self) -> None:
-        """Forget every recorded step program (anything a program captured BY VALUE was changed from outside: loss
-        weights, near / far planes, the batcher's image set ...; pointers and the scheduled scalars are tracked)."""
+        """Forget every recorded step program.  Tracked without this call, through _program_key: the model's configuration
+        (loss weights, near / far planes, background, arithmetic ...), the optimiser, camera optimiser and batcher OBJECTS
+        and what programs capture from them (_captured_fingerprint: moment / pose / image-set addresses, hyper-parameters,
+        sparse-touch bitmaps), the batcher's camera table, streams and the module switches; the scheduled scalars are
+        patched per replay.  Still needs the call: any other VALUE (not tensor contents, which a replay reads afresh) that
+        a program copied from an object that stays in place — the model's collider or scene box, the set-wide fx / fy / cx /
+        cy or a new tensor put into a batcher's `data` after its first draw, the image set of a custom batcher without
+        program_fingerprint()."""
         self._programs.clear()
         self._unrecordable.clear()
         self._seen.clear()
@@ -1508,6 +1549,36 @@ class TrainingSteps:
         self._seen.clear()
         self._next_layout = None
 
+    def _captured_fingerprint(self) -> tuple:
+        """(optimiser, camera, batcher): what the replaceable, mutable Python objects of the loop put into a recorded program
+        by value — FusedAdam / CameraAdam / PixelBatcher.program_fingerprint().  Each part starts with its object's serial
+        number.  Computed on every step: host-only, no launch, no bitmap built."""
+        cam, batcher = self.camera, self.batcher
+        fp = getattr(batcher, "program_fingerprint", None)
+        if cam is not None:
+            # (the pose table the rays go through is the one CameraAdam steps, unless somebody paired them otherwise)
+            pose = None if cam[0] is getattr(cam[1], "opt", None) else getattr(cam[0], "pose_adjustment", None)
+            cam = (cam[1].program_fingerprint(), None if pose is None else pose.data_ptr(),
+                   getattr(cam[2], "serial", None) if cam[2] is not batcher else None)
+        return (self.optimizer.program_fingerprint(), cam, fp() if fp is not None else (id(batcher),))
+
+    @staticmethod
+    def _same_objects(a: tuple, b: tuple) -> bool:
+        """Two _captured_fingerprint()s of the same optimiser and batcher objects and, where both have one, CameraAdam."""
+        return a[0][0] == b[0][0] and a[2][0] == b[2][0] and (a[1] is None or b[1] is None or a[1][0][0] == b[1][0][0])
+
+    def _forget_unreachable(self, fingerprint: tuple) -> None:
+        """The fingerprint changed: forget the programs (and what was noted per key) recorded with an optimiser, a camera
+        optimiser or a batcher that has been replaced — serial numbers do not come back, and such programs keep the old
+        objects' tensors alive — and bound what fingerprints that CAN come back (hyper-parameters set back and forth) leave
+        behind, oldest first."""
+        for d in (self._programs, self._unrecordable, self._seen):
+            for k in [k for k in d if not self._same_objects(k[0], fingerprint)]:
+                del d[k]
+            while len(d) > MAX_PROGRAMS:
+                del d[next(iter(d))]
+        self._fingerprint = fingerprint
+
     def _program_key(self, parity: int, start_offset: int, updated: bool, updated_next: bool, want_metrics: bool) -> tuple:
         model = self.model
         fld = model.field
@@ -1516,9 +1587,10 @@ class TrainingSteps:
         side = model.__dict__.get("_side_stream")
         cams = _camera_table(self.batcher)      # recorded by value: another table is another program
         # (the pose mode too: a camera optimiser of the other mode on the same loop is another program)
-        return (None if cams is None else cams.pointers(), self._arena_version, parity, start_offset, updated, updated_next,
+        return (self._captured_fingerprint(),
+                None if cams is None else cams.pointers(), self._arena_version, parity, start_offset, updated, updated_next,
                 bool(want_metrics), None if self.camera is None else getattr(self.camera[0], "pose_mode", 0),
-                getattr(fld, "mlp_precision", None), model.arena().params.data_ptr(), id(self.optimizer),
+                getattr(fld, "mlp_precision", None), model.arena().params.data_ptr(),
                 L.stream_ptr(dev), None if side is None else side.cuda_stream,
                 OVERLAP_PROPOSAL_BACKWARD, SERIALIZE_STREAMS, LOSSES_ON_SIDE, PAIR_PROPOSAL_LEVELS, FUSE_CAMERA_OPTIMIZER,
                 FUSE_WEIGHT_OPTIMIZER, FUSE_TABLE_OPTIMIZER, SPARSE_TOUCH_SKIPPING, STREAM_SAFE, FUSE_COMPOSITE_BACKWARD,
@@ -1544,6 +1616,9 @@ class TrainingSteps:
         sampler = model.proposal_sampler
         step = self.step_idx
         parity = step & 1
+        # sparse-touch bitmaps dropped since the last step (rebuild_touched(), an optimiser step outside the fused kernels)
+        # are rebuilt HERE, in place: outside any recording, and ahead of a replay, which holds only their addresses
+        self.optimizer.ensure_touched()
         self._ensure_arenas()
         arena = self._arenas[parity]
         have_next = self._next is not None and self._next[0] == step
@@ -1558,15 +1633,20 @@ class TrainingSteps:
             updated = sampler.updated_now()
             pre = self._next[1].presampled or {}
             # (a look-ahead drawn before the sampler's single_jitter was flipped is the other form's: _render samples again)
+            # (a step that trains no proposal network under skip_groups_without_grad=False ends in an unfused optimiser step
+            # over their span — an entry point no program can hold: interpreted without an attempt to record it)
             if ahead is not None and ahead["updated"] == updated and ahead["anneal"] == model.anneal_at(step) \
                     and ahead.get("param_version") == model.lookahead_version() \
-                    and bool(pre.get("per_edge", False)) == (not getattr(sampler, "single_jitter", True)):
+                    and bool(pre.get("per_edge", False)) == (not getattr(sampler, "single_jitter", True)) \
+                    and (updated or self.optimizer.skip_groups_without_grad):
                 # what the look-ahead of THIS step will see: sample_ahead() runs behind _render, which restarts the count
                 # of steps since the last update on a step that updates (ProposalNetworkSampler.updated_after)
                 since = 0 if updated else sampler._steps_since_update
                 updated_next = bool(since + 1 > sampler.update_sched(step) or step < 10)
                 key = self._program_key(parity, arena.offset, updated, updated_next, want_metrics)
         if key is not None:
+            if key[0] != self._fingerprint:
+                self._forget_unreachable(key[0])
             prog = self._programs.get(key)
             if prog is not None:
                 return self._replay(prog, step, want_metrics, updated)

@@ -763,9 +763,151 @@ def test_touched_bitmaps_are_keyed_by_arena_offset_and_dropped_by_unfused_steps(
     assert set(opt._touched) == {64, 64 + table_a.numel()} and launches == [64]
     opt.step_span(32, 64 + 16, 1e-2, group="fields")              # overlaps table a's head
     assert set(opt._touched) == {64 + table_a.numel()}
-    assert opt.touched_bitmap(table_a, 64, table_a.numel()) is not bm_a         # rebuilt from the moments
+    opt.exp_avg_sq[64 + 4 * 33] = 1.0                             # the unfused step "made" pair 33's moment non-zero
+    again = opt.touched_bitmap(table_a, 64, table_a.numel())      # rebuilt from the moments ...
+    assert int(again[0]) == 1 << 2 and int(again[1]) == 1 << 1 and int(again[2:].abs().sum()) == 0
+    assert again.data_ptr() == bm_a.data_ptr()                    # ... into the tensor recorded step programs point at
+    assert set(opt._touched) == {64, 64 + table_a.numel()}
+    opt.rebuild_touched()
+    assert not opt._touched
+    opt.exp_avg[64 + table_a.numel() + 4] = 1.0                   # pair 1 of table b
+    opt.ensure_touched()                                          # what TrainingSteps calls ahead of every step
+    assert set(opt._touched) == {64, 64 + table_a.numel()} and opt._touched[64][1].data_ptr() == bm_a.data_ptr()
+    assert opt._touched[64 + table_a.numel()][1].data_ptr() == bm_b.data_ptr() and int(bm_b[0]) == 1 << 1
     opt.rebuild_touched()
     assert not opt._touched
     # skipping does not apply with weight decay or to a span that is not a whole number of 128-float words
     assert T.FusedAdam(model, weight_decay=1e-3).touched_bitmap(table_a, 64, table_a.numel()) is None
     assert opt.touched_bitmap(table_a, 64, 100) is None
+
+
+def _keyed_loop(monkeypatch):
+    """training.TrainingSteps over real FusedAdam / CameraAdam / PixelBatcher objects on CPU tensors and a stub model: what
+    _program_key needs, nothing that launches."""
+    import types
+    import fruitnerf_amd.training as T
+    from fruitnerf_amd.cameras.camera_optimizers import CameraAdam, CameraOptimizerConfig
+    from fruitnerf_amd.data import synthetic_apple as sa
+    from fruitnerf_amd.fruit_nerf import FruitNerfModelConfig
+    monkeypatch.setattr(T, "SPARSE_TOUCH_SKIPPING", True)
+    monkeypatch.setattr(T.L, "stream_ptr", lambda dev: 0)
+    table_a, table_b = torch.zeros(256 * 2), torch.zeros(128 * 2)
+    params = torch.zeros(64 + table_a.numel() + table_b.numel())
+    arena = types.SimpleNamespace(params=params, grads=torch.zeros_like(params),
+                                  entries=[("w", None, 0, 64), ("a", table_a, 64, table_a.numel()),
+                                           ("b", table_b, 64 + table_a.numel(), table_b.numel())],
+                                  group_ranges={"fields": (0, params.numel())})
+    model = types.SimpleNamespace(arena=lambda: arena, field=types.SimpleNamespace(mlp_precision="bf16x3"),
+                                  config=FruitNerfModelConfig(), device=torch.device("cpu"),
+                                  proposal_sampler=types.SimpleNamespace(single_jitter=True))
+
+    def make_optimizer():
+        opt = T.FusedAdam(model)
+        opt.touched_bitmap(table_a, 64, table_a.numel())
+        opt.touched_bitmap(table_b, 64 + table_a.numel(), table_b.numel())
+        return opt
+
+    def make_camera(n=5):
+        cam_opt = CameraOptimizerConfig(mode="SO3xR3").setup(n, "cpu")
+        return cam_opt, CameraAdam(cam_opt)
+
+    def make_batcher(seed=1):
+        data = {"images": torch.zeros(2, 4, 4, 3, dtype=torch.uint8), "masks": torch.zeros(2, 4, 4, dtype=torch.uint8),
+                "c2w": torch.zeros(2, 3, 4), "H": 4, "W": 4, "fx": 4.0, "fy": 4.0, "cx": 2.0, "cy": 2.0}
+        return sa.PixelBatcher(data, torch.arange(2), seed=seed)
+    loop = T.TrainingSteps(model, make_optimizer(), make_batcher(), 8, camera=make_camera())
+    return loop, types.SimpleNamespace(optimizer=make_optimizer, camera=make_camera, batcher=make_batcher,
+                                       table_a=(64, 64 + table_a.numel()))
+
+
+_KEY_CHANGES = {
+    "exp_avg reassigned": lambda loop, make: setattr(loop.optimizer, "exp_avg", loop.optimizer.exp_avg.clone()),
+    "exp_avg_sq reassigned": lambda loop, make: setattr(loop.optimizer, "exp_avg_sq", loop.optimizer.exp_avg_sq.clone()),
+    "rebuild_touched": lambda loop, make: loop.optimizer.rebuild_touched(),
+    "_invalidate_touched over a table span": lambda loop, make: loop.optimizer._invalidate_touched(*make.table_a),
+    "betas": lambda loop, make: setattr(loop.optimizer, "betas", (0.8, 0.99)),
+    "eps": lambda loop, make: setattr(loop.optimizer, "eps", 1e-8),
+    "weight_decay": lambda loop, make: setattr(loop.optimizer, "weight_decay", 1e-4),
+    "algorithm": lambda loop, make: setattr(loop.optimizer, "algorithm", "radam"),
+    "skip_groups_without_grad": lambda loop, make: setattr(loop.optimizer, "skip_groups_without_grad", False),
+    "optimiser replaced": lambda loop, make: setattr(loop, "optimizer", make.optimizer()),
+    "camera optimiser replaced": lambda loop, make: setattr(loop, "camera", make.camera() + (loop.batcher,)),
+    "CameraAdam exp_avg reassigned": lambda loop, make: setattr(loop.camera[1], "exp_avg", loop.camera[1].exp_avg.clone()),
+    "CameraAdam exp_avg_sq reassigned":
+        lambda loop, make: setattr(loop.camera[1], "exp_avg_sq", loop.camera[1].exp_avg_sq.clone()),
+    "CameraAdam betas": lambda loop, make: setattr(loop.camera[1], "betas", (0.8, 0.99)),
+    "batcher image set replaced": lambda loop, make: setattr(loop.batcher, "data", make.batcher().data),
+    "batcher replaced": lambda loop, make: setattr(loop, "batcher", make.batcher()),
+}
+
+
+@pytest.mark.parametrize("change", sorted(_KEY_CHANGES))
+def test_program_key_notices_what_a_program_captures_from_replaceable_objects(monkeypatch, change):
+    """What selects a recorded step program holds everything the program copied from the optimiser, the camera optimiser and
+    the batcher: each change from outside gives another fingerprint and another key; an in-place copy_ into the moments
+    gives the same one (rebuild_touched() is the call for those)."""
+    loop, make = _keyed_loop(monkeypatch)
+
+    def keyed():
+        key = loop._program_key(0, 0, True, True, True)
+        assert key[0] == loop._captured_fingerprint()           # the key's first member: the seam this test looks through
+        return key
+    before = keyed()
+    assert keyed() == before
+    with torch.no_grad():
+        for moment in (loop.optimizer.exp_avg, loop.optimizer.exp_avg_sq, loop.camera[1].exp_avg, loop.camera[1].exp_avg_sq):
+            moment.copy_(torch.full_like(moment, 0.5))
+        loop.camera[0].pose_adjustment.copy_(torch.full_like(loop.camera[0].pose_adjustment, 0.25))
+    assert keyed() == before, "an in-place edit changed the key"
+    _KEY_CHANGES[change](loop, make)
+    after = keyed()
+    assert after[0] != before[0] and after != before, f"{change}: the key did not notice"
+    assert after[1:] == before[1:]
+
+
+def test_program_key_bitmap_state_and_forgotten_programs(monkeypatch):
+    """The bitmap part of the fingerprint: an unfused step over the MLP weights alone leaves it (such steps must not evict
+    programs); a dropped bitmap changes it until ensure_touched() has rebuilt the bitmap where it was — then the recorded
+    programs hold again.  Programs of replaced objects are forgotten, those of the same objects bounded."""
+    import fruitnerf_amd.training as T
+    loop, make = _keyed_loop(monkeypatch)
+    opt = loop.optimizer
+    before = loop._captured_fingerprint()
+    opt._invalidate_touched(0, 64)                                # the MLP weights: touches no table
+    assert loop._captured_fingerprint() == before and opt.program_fingerprint() == before[0]
+    opt._invalidate_touched(*make.table_a)
+    assert loop._captured_fingerprint() != before
+    opt.exp_avg[64 + 8] = 1.0
+    opt.ensure_touched()
+    assert loop._captured_fingerprint() == before and int(opt._touched[64][1][0]) == 1 << 2
+    opt.rebuild_touched()
+    assert loop._captured_fingerprint() != before
+    opt.ensure_touched()
+    assert loop._captured_fingerprint() == before
+    # with weight decay no table step reads a bitmap: their state is no part of the fingerprint
+    opt.weight_decay = 1e-4
+    with_decay = opt.program_fingerprint()
+    opt.rebuild_touched()
+    assert opt.program_fingerprint() == with_decay
+    opt.ensure_touched()
+    assert not opt._touched                                       # nothing is rebuilt that no step would read
+    opt.weight_decay = 0.0
+    opt.ensure_touched()
+    assert loop._captured_fingerprint() == before
+    # forgetting: keys are (fingerprint, ...)
+    loop._programs = {(before, i): object() for i in range(3)}
+    loop._seen = {(before, 0): 1}
+    opt.betas = (0.8, 0.99)
+    changed = loop._captured_fingerprint()
+    loop._forget_unreachable(changed)
+    assert len(loop._programs) == 3 and loop._fingerprint == changed     # same objects: betas can be set back
+    loop.camera = None
+    loop._forget_unreachable(loop._captured_fingerprint())
+    assert len(loop._programs) == 3                                       # camera off: it can be switched on again
+    for i in range(2 * T.MAX_PROGRAMS):
+        loop._programs[(changed, i)] = object()
+    loop._forget_unreachable(changed)
+    assert len(loop._programs) == T.MAX_PROGRAMS and (before, 0) not in loop._programs      # oldest first
+    loop.optimizer = make.optimizer()
+    loop._forget_unreachable(loop._captured_fingerprint())
+    assert not loop._programs and not loop._seen
