@@ -40,24 +40,34 @@ def _anchor(model) -> Tensor:
     return a
 
 
-def _field_ray_grads(model, rctx, d_feats: Tensor, d_origins: Tensor, d_directions: Tensor,
-                     d_position: Optional[Tensor] = None) -> None:
-    """d(loss)/d(ray origins, directions) through the main field's hash grid (position_grad.hip): the only path from
-    the losses to the rays — PDFSampler detaches its bins, SHEncoding runs under no_grad.
-    d_position [N,4]: the per-sample input gradient field_mlp_bwd(jacobian=...) already formed — only the warp /
-    frustum chain and the sum over each ray are left."""
-    fld = model.field
-    lv = rctx.levels[-1]
-    if d_position is not None:
-        K.position_grad_reduce(fld.warp_struct(), rctx.rays, lv["euclid"], lv["S"], d_position.view(1, -1, 4), d_origins,
-                               d_directions)
-        return
-    if rctx.field_jacobian is not None:   # saved by the forward encode: no table gathers here
-        K.position_grad_from_jacobian(fld.warp_struct(), rctx.rays, lv["euclid"], lv["S"], rctx.field_jacobian, d_feats,
-                                      d_origins, d_directions)
-        return
-    partial = K.hash_encode_input_grad(fld.net_struct().grid, fld.warp_struct(), rctx.rays, lv["euclid"], lv["S"], d_feats)
-    K.position_grad_reduce(fld.warp_struct(), rctx.rays, lv["euclid"], lv["S"], partial, d_origins, d_directions)
+def _field_backward(field, rays, euclid: Tensor, S: int, feats: Tensor, h_saved, selector: Tensor, d_density: Tensor,
+                    d_rgb: Tensor, d_logit: Tensor, *, semgrad: bool, weight_adam=None, want_position: bool = False,
+                    jacobian: Optional[Tensor] = None):
+    """The field's MLP backward of the per-sample (d_density, d_rgb, d_logit) -> (d_feats, ray-gradient source | None).
+    The source (want_position) is (warp, euclid, S, partial), what position_grad_reduce(_multi) sums over each ray into
+    d(loss)/d(ray origins, directions) — through the main field's hash grid, the only path from the losses to the rays
+    (PDFSampler detaches its bins, SHEncoding runs under no_grad: SURVEY Appendix A).  With the Jacobian the forward
+    encode saved, `partial` is the d_position [N,4] the MLP backward forms itself.  Without one (the model is not in
+    training mode) it comes from a gather over the TABLE, so that gather runs here: before any scatter or fused table step
+    of the caller, which may update the table in place.  The scatter of d_feats and the reduction of the source stay with
+    the caller (their order differs per path)."""
+    net, gnet = field.net_struct(), field.net_struct(grads=True)
+    if want_position and jacobian is not None:
+        d_feats, d_pos = K.field_mlp_bwd(net, gnet, rays, S, feats, h_saved, selector, d_density, d_rgb, d_logit,
+                                         jacobian=jacobian, weight_adam=weight_adam, semgrad=semgrad)
+        return d_feats, (field.warp_struct(), euclid, S, d_pos)
+    d_feats = K.field_mlp_bwd(net, gnet, rays, S, feats, h_saved, selector, d_density, d_rgb, d_logit,
+                              weight_adam=weight_adam, semgrad=semgrad)
+    if not want_position:
+        return d_feats, None
+    partial = K.hash_encode_input_grad(net.grid, field.warp_struct(), rays, euclid, S, d_feats)
+    return d_feats, (field.warp_struct(), euclid, S, partial)
+
+
+def _reduce_ray_source(source, rays, d_origins: Tensor, d_directions: Tensor) -> None:
+    """d_origins / d_directions [R,3] += one ray-gradient source (warp, euclid, S, partial)."""
+    warp, euclid, S, partial = source
+    K.position_grad_reduce(warp, rays, euclid, S, partial, d_origins, d_directions)
 
 
 def _composite_backward(rctx, semgrad: bool, *, given=None, targets=None):
@@ -67,15 +77,18 @@ def _composite_backward(rctx, semgrad: bool, *, given=None, targets=None):
     `targets` = (out_rgb, image, out_sem, mask, sem_weight), the loss targets the kernel forms them from."""
     opts = getattr(rctx, "composite_options", None)
     lv = rctx.levels[-1]
-    suffix = "_opt" if opts is not None else "_semgrad" if semgrad else ""
-    fn = getattr(K, ("composite_bwd" if targets is None else "composite_bwd_targets") + suffix)
-    args = [rctx.rays, lv["S"], lv["euclid"], rctx.sample_density, rctx.sample_rgb]
-    if suffix:
-        args.append(rctx.sample_logit)          # (the two plain calls take no per-sample logits)
-    args += [rctx.weights, *(given if targets is None else targets)]
+    head = (rctx.rays, lv["S"], lv["euclid"], rctx.sample_density, rctx.sample_rgb)
     if opts is not None:
-        args.append(opts)
-    return fn(*args)
+        if targets is None:
+            return K.composite_bwd_opt(*head, rctx.sample_logit, rctx.weights, *given, opts)
+        return K.composite_bwd_targets_opt(*head, rctx.sample_logit, rctx.weights, *targets, opts)
+    if semgrad:
+        if targets is None:
+            return K.composite_bwd_semgrad(*head, rctx.sample_logit, rctx.weights, *given)
+        return K.composite_bwd_targets_semgrad(*head, rctx.sample_logit, rctx.weights, *targets)
+    if targets is None:                         # (the two plain calls take no per-sample logits)
+        return K.composite_bwd(*head, rctx.weights, *given)
+    return K.composite_bwd_targets(*head, rctx.weights, *targets)
 
 
 def _distortion_on(model, rctx) -> bool:
@@ -138,24 +151,20 @@ class _RenderFn(torch.autograd.Function):
             # (the upstream gradient stays on the device: a GradScaler's scale arrives through it without a host sync)
             _distortion_backward(model, rctx, d_density, upstream=rest[-1])
         fld = model.field
-        net, gnet = fld.net_struct(), fld.net_struct(grads=True)
         want_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        d_pos = None
-        if want_rays and rctx.field_jacobian is not None:
-            d_feats, d_pos = K.field_mlp_bwd(net, gnet, rays, S, rctx.field_feats, rctx.field_h, rctx.field_selector,
-                                             d_density, d_rgb, d_logit, jacobian=rctx.field_jacobian, semgrad=semgrad)
-        else:
-            d_feats = K.field_mlp_bwd(net, gnet, rays, S, rctx.field_feats, rctx.field_h, rctx.field_selector, d_density,
-                                      d_rgb, d_logit, semgrad=semgrad)
+        d_feats, source = _field_backward(fld, rays, lv["euclid"], S, rctx.field_feats, rctx.field_h, rctx.field_selector,
+                                          d_density, d_rgb, d_logit, semgrad=semgrad, want_position=want_rays,
+                                          jacobian=rctx.field_jacobian)
         d_o = d_d = None
+        gathered = rctx.field_jacobian is None   # such a source is reduced ahead of the scatter, the MLP backward's behind it
         if want_rays:
             d_o = torch.zeros(rays.n, 3, device=dev)
             d_d = torch.zeros(rays.n, 3, device=dev)
-            if d_pos is None:   # no saved Jacobian: the gather path reads the table, so it runs BEFORE any table update
-                _field_ray_grads(model, rctx, d_feats, d_o, d_d)
-        K.hash_encode_bwd(gnet.grid, fld.warp_struct(), rays, lv["euclid"], S, d_feats)
-        if d_pos is not None:
-            _field_ray_grads(model, rctx, d_feats, d_o, d_d, d_pos)
+            if gathered:
+                _reduce_ray_source(source, rays, d_o, d_d)
+        K.hash_encode_bwd(fld.net_struct(grads=True).grid, fld.warp_struct(), rays, lv["euclid"], S, d_feats)
+        if want_rays and not gathered:
+            _reduce_ray_source(source, rays, d_o, d_d)
         return None, d_o, d_d, None, None, None
 
 
@@ -185,10 +194,9 @@ class _FieldFn(torch.autograd.Function):
         N = rays.n * S
         dev = rays.device
         z = lambda g, *shape: (torch.zeros(*shape, device=dev) if g is None else g.reshape(*shape).float().contiguous())  # noqa: E731
-        net, gnet = field.net_struct(), field.net_struct(grads=True)
-        d_feats = K.field_mlp_bwd(net, gnet, rays, S, feats, saved, selector, z(g_density, N), z(g_rgb, N, 3),
-                                  z(g_logit, N), semgrad=bool(field.pass_semantic_gradients))  # fruit_field.py:263-264
-        K.hash_encode_bwd(gnet.grid, field.warp_struct(), rays, ctx.euclid, S, d_feats)
+        d_feats, _ = _field_backward(field, rays, ctx.euclid, S, feats, saved, selector, z(g_density, N), z(g_rgb, N, 3),
+                                     z(g_logit, N), semgrad=bool(field.pass_semantic_gradients))  # fruit_field.py:263-264
+        K.hash_encode_bwd(field.net_struct(grads=True).grid, field.warp_struct(), rays, ctx.euclid, S, d_feats)
         return None, None, None, None, None, None
 
 
@@ -208,7 +216,6 @@ class _InterlevelFn(torch.autograd.Function):
     def forward(ctx, anchor, origins, directions, model, rctx, mult):
         fin = rctx.levels[-1]
         dev = rctx.rays.device
-        from . import _lib as L
         loss = torch.zeros(L.FNR_LOSS_SLOTS, device=dev)
         d_wps = []
         for lv in rctx.levels[:-1]:
@@ -377,7 +384,6 @@ def exponential_decay_lr(step: int, lr_init: float, lr_final: float, max_steps: 
     return float(np.exp(np.log(lr_init) * (1 - t) + np.log(lr_final) * t))
 
 
-L_MAX_ADAM_SPANS = 8   # include/fruitnerf_hip.h: FNR_MAX_ADAM_SPANS
 # fnr_table_adam.touched: the fused table steps skip pairs of rows that never received a gradient (their update is exactly
 # zero).  FNR_SPARSE_TOUCH=0 sweeps every row (A/B; results are bit-identical either way, tests/test_gpu_training_parity.py)
 SPARSE_TOUCH_SKIPPING = os.environ.get("FNR_SPARSE_TOUCH", "1") != "0"
@@ -425,11 +431,27 @@ class FusedAdam:
         self._bitmaps: Dict[int, Tuple[int, Tensor]] = {}
         self.serial = next(_OPTIMIZER_SERIALS)                 # never reused, unlike id(): see program_fingerprint()
 
-    def current_lr(self, name: str) -> float:
+    def scheduled_lr(self, name: str, step: int) -> float:
+        """The learning rate of group `name` after `step` scheduler steps (constant without an lr_final)."""
         g = self.groups[name]
         if g.get("lr_final") is None:
             return g["lr"]
-        return exponential_decay_lr(self.step_count, g["lr"], g["lr_final"], g["max_steps"])
+        return exponential_decay_lr(step, g["lr"], g["lr_final"], g["max_steps"])
+
+    def current_lr(self, name: str) -> float:
+        return self.scheduled_lr(name, self.step_count)
+
+    def next_update(self, name: str) -> Tuple[float, int]:
+        """(learning rate, step count) of the NEXT update of group `name`: what begin_step() will hand out and set — for
+        the kernels that take a parameter's update ahead of the optimiser's own step, and for a replayed step's scalars."""
+        return self.scheduled_lr(name, self.step_count), self.group_steps[name] + 1
+
+    def advance(self, skip=()) -> None:
+        """begin_step()'s counters alone (a replayed step, whose every update is fused: nothing asks for the rates)."""
+        self.step_count += 1
+        for name in self.group_steps:
+            if name not in skip:
+                self.group_steps[name] += 1
 
     def begin_step(self, skip=()) -> Dict[str, float]:
         """Advance the counters and return this update's learning rate per parameter group (scheduler.step() runs
@@ -440,12 +462,9 @@ class FusedAdam:
         their .grad = None (torch >= 2.0: set_to_none), and torch.optim.Adam / RAdam skip such parameters entirely —
         no moment decay, no movement, and their per-parameter `step` (bias correction, RAdam's rho_t) does not advance.
         The learning-rate schedulers still tick every iteration."""
-        self.step_count += 1
-        for name in self.group_steps:
-            if name not in skip:
-                self.group_steps[name] += 1
-        return {name: (exponential_decay_lr(self.step_count - 1, g["lr"], g["lr_final"], g["max_steps"])
-                       if g.get("lr_final") is not None else g["lr"]) for name, g in self.groups.items()}
+        lrs = {name: self.scheduled_lr(name, self.step_count) for name in self.groups}
+        self.advance(skip)
+        return lrs
 
     def touched_bitmap(self, table: Tensor, a: int, n: int) -> Optional[Tensor]:
         """The persistent pair bitmap of `table` (arena span [a, a + n)); None when skipping does not apply."""
@@ -503,16 +522,13 @@ class FusedAdam:
         """fnr_table_adam for the NEXT update of `table` (a parameter of `group` that lives in the arena): learning
         rate and step count as begin_step() will set them — the fused scatter (fnr_hash_encode_bwd_adam) runs before
         the optimiser's own step and takes this parameter's update with it.  -> (struct, (a, b) arena span)."""
-        from . import _lib as L
         hit = [(off, n) for _, p, off, n in self.arena.entries if p is table]
         if len(hit) != 1:
             raise RuntimeError("parameter not found in the arena")
         a, n = hit[0]
-        g = self.groups[group]
-        lr = (exponential_decay_lr(self.step_count, g["lr"], g["lr_final"], g["max_steps"])
-              if g.get("lr_final") is not None else g["lr"])
+        lr, step = self.next_update(group)
         args = L.table_adam(0 if self.algorithm == "adam" else 1, lr, self.betas[0], self.betas[1], self.eps,
-                            self.group_steps[group] + 1, grad_scale, self.weight_decay,
+                            step, grad_scale, self.weight_decay,
                             L.ptr(self.arena.params[a:a + n]), L.ptr(self.exp_avg[a:a + n]),
                             L.ptr(self.exp_avg_sq[a:a + n]), L.ptr(self.touched_bitmap(table, a, n)),
                             slot=L.ADAM_SLOTS.get(group, 0))
@@ -522,12 +538,9 @@ class FusedAdam:
         """fnr_table_adam for the NEXT update of `group`, addressed through the whole arenas (fnr_field_mlp_bwd_adam: the
         kernels that finish the gradients of the field's MLP weights and embedding take those parameters' step).
         -> ((struct, gradient arena), the group's arena span)."""
-        from . import _lib as L
-        g = self.groups[group]
-        lr = (exponential_decay_lr(self.step_count, g["lr"], g["lr_final"], g["max_steps"])
-              if g.get("lr_final") is not None else g["lr"])
+        lr, step = self.next_update(group)
         args = L.table_adam(0 if self.algorithm == "adam" else 1, lr, self.betas[0], self.betas[1], self.eps,
-                            self.group_steps[group] + 1, grad_scale, self.weight_decay,
+                            step, grad_scale, self.weight_decay,
                             L.ptr(self.arena.params), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), None,
                             slot=L.ADAM_SLOTS.get(group, 0))
         return (args, self.arena.grads), tuple(self.arena.group_ranges[group])
@@ -577,7 +590,7 @@ class FusedAdam:
         step (table_adam_args) — they are cut out of the launches."""
         lrs = self.begin_step(skip)
         runs = self.plan_runs(lrs, skip, done)
-        if len(runs) <= 1 or len(runs) > L_MAX_ADAM_SPANS:
+        if len(runs) <= 1 or len(runs) > L.FNR_MAX_ADAM_SPANS:
             for a, b, lr, name in runs:
                 self.step_span(a, b, lr, grad_scale, group=name)
         else:   # one launch for all of them (the groups' MLP weights are a few thousand floats each)
@@ -892,6 +905,19 @@ def _second_stream(model, dev):
     return side
 
 
+def _second_stream_and_events(model, dev):
+    """What a two-stream step of fused_forward_backward runs on, created on first use and kept with the model ->
+    (second stream, `pos_ready`: the proposal chain's ray-gradient sources are final, `tail_ready`: the launch stream has
+    enqueued what the second stream's last segment waits for)."""
+    events = []
+    for name in ("_pos_ready_event", "_tail_ready_event"):
+        ev = model.__dict__.get(name)
+        if ev is None:
+            ev = model.__dict__[name] = K.Event()
+        events.append(ev)
+    return (_second_stream(model, dev), *events)
+
+
 # FNR_STREAM_SAFE=1 (debug): every tensor that crosses between the launch stream and the second stream is ALSO registered
 # with the consuming stream (Tensor.record_stream), so the caching allocator itself refuses to recycle its block before that
 # stream is past it.  The default relies on the fork / join structure instead (see TrainingSteps.step and _ForkJoin below):
@@ -992,7 +1018,6 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
     backward adds the term to d_density in place; the losses launch sums the distortion also without metrics and
     loss_dict["distortion_loss"] = distortion_loss_mult x that sum — or the sum itself with scale_distortion_loss=False, for a
     caller that multiplies later (TrainingSteps: outside the recorded region)."""
-    from . import _lib as L
     cfg = model.config
     semgrad = bool(cfg.pass_semantic_gradients)   # the `_semgrad` forms of the compositing / MLP backward, recordable like theirs
     dev = model.device
@@ -1010,29 +1035,45 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
         rays, fin = rctx.rays, rctx.levels[-1]
         S = fin["S"]
         use_dist = _distortion_on(model, rctx)
-        # one fill for everything this step accumulates into: the loss slots (+ completion counter) and, with a camera
-        # optimiser, the ray gradients d(loss)/d(origins | directions); one launch for every loss and metric
         # the loss / metric accumulator is persistent: fnr_train_losses leaves it zeroed (its last workgroup cleans up),
         # so a step launches no fill; the ray gradients are WRITTEN by the one reduction over all their sources
-        n_slots = L.FNR_TRAIN_LOSSES_ACCUM_FLOATS
         accum = model.__dict__.get("_loss_accum")
         if accum is None or accum.device != dev:
-            accum = model.__dict__["_loss_accum"] = torch.zeros(n_slots, device=dev)
+            accum = model.__dict__["_loss_accum"] = torch.zeros(L.FNR_TRAIN_LOSSES_ACCUM_FLOATS, device=dev)
         # on steps that train the proposal networks their weights backward (unit upstream) rides along: the list
         # then holds d(loss)/d(density) per level instead of d(loss)/d(weights)
         prop_bwd = bool(rctx.training and rctx.updated)
         prop_levels = [(lv["S"], lv["spacing"], lv["weights"]) + ((lv["euclid"], lv["density"]) if prop_bwd else ())
                        for lv in rctx.levels[:-1]]
+
+        # ---- what goes to the second stream ----
+        # The proposal-network backward (interlevel loss) and the field backward (rgb + semantic losses) share no
+        # buffers.  overlap_proposal_backward=True runs the former on a second HIP stream so that its ~14 small/medium
+        # launches fill the gaps and tails of the field kernels (measured: -3 % on the steps that have one); bench.py
+        # serialises the two streams on the steps whose launches it brackets with HIP events (serialize_streams: a
+        # duration measured while another stream's kernels share the CUs describes neither kernel).
+        prop_on_side = bool(prop_bwd and overlap_proposal_backward)
+        # The ray gradients' sources are complete once the MLP backward is (its d_pos) and the proposal chain's MLP
+        # backwards have run; their reduction and the camera optimiser's ~30 us of small launches do not need the
+        # scatters: single process + second stream -> they run next to one
+        # ... and with a gradient exchange the same segment holds what follows the collectives of the small groups
+        # (after_ray_grads = fused_train_iteration's exchange_tail: pose gradient + its all-reduce, the proposal networks'
+        # all-reduce, their waits and optimiser steps), so that N > 1 keeps the schedule N = 1 has
+        tail_on_side = bool(overlap_proposal_backward and ((ray_grads is not None and exchange is None) or
+                                                           (exchange is not None and after_ray_grads is not None)))
+        main = torch.cuda.current_stream(dev)
+        fj = _ForkJoin(main)
+        side = pos_ready = tail_ready = None
+        if losses_on_side or prop_on_side or tail_on_side:
+            side, pos_ready, tail_ready = _second_stream_and_events(model, dev)
+
+        # ---- losses ----
         # The loss VALUES (five scalars for the log) and the interlevel loss with the proposal levels' weights backward feed
         # the second stream's work only; what the field backward needs from the losses — the per-ray gradients of MSE and
         # BCE — the composite backward forms itself (fnr_composite_bwd_targets: same expressions, same bits).  So with two
         # streams the losses launch (~30 us, latency-bound) opens the SECOND stream's segment, next to the composite + MLP
         # backward instead of ahead of them (round 5; LOSSES_ON_SIDE).
-        main = torch.cuda.current_stream(dev)
-        fj = _ForkJoin(main)
-        side = None
         if losses_on_side:
-            side = _second_stream(model, dev)
             fj.fork(side)                       # behind the forward pass
             crosses_to(side, outputs, image, mask, rctx, accum)
         with torch.cuda.stream(side) if losses_on_side else contextlib.nullcontext():
@@ -1057,38 +1098,19 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
         if ray_grads is not None:
             both = K._empty(2, rays.n, 3, device=dev)
             d_o, d_d = ray_grads["origins"], ray_grads["directions"] = both[0], both[1]
-        # The proposal-network backward (interlevel loss) and the field backward (rgb + semantic losses) share no
-        # buffers.  overlap_proposal_backward=True runs the former on a second HIP stream so that its ~14 small/medium
-        # launches fill the gaps and tails of the field kernels (measured: -3 % on the steps that have one); bench.py
-        # serialises the two streams on the steps whose launches it brackets with HIP events (serialize_streams: a
-        # duration measured while another stream's kernels share the CUs describes neither kernel).
-        up = None   # d_wps is d(loss)/d(density) already (fuse_weights_bwd above)
-        # The ray gradients' sources are complete once the MLP backward is (its d_pos) and the proposal chain's MLP
-        # backwards have run; their reduction and the camera optimiser's ~30 us of small launches do not need the
-        # scatters: single process + second stream -> they run next to one
-        # ... and with a gradient exchange the same segment holds what follows the collectives of the small groups
-        # (after_ray_grads = fused_train_iteration's exchange_tail: pose gradient + its all-reduce, the proposal networks'
-        # all-reduce, their waits and optimiser steps), so that N > 1 keeps the schedule N = 1 has
-        tail_on_side = bool(overlap_proposal_backward and ((ray_grads is not None and exchange is None) or
-                                                           (exchange is not None and after_ray_grads is not None)))
+        # (upstream None below: d_wps is d(loss)/d(density) already, fuse_weights_bwd above)
         sources_early = False   # the proposal chain recorded `pos_ready` ahead of its scatter
-        if prop_bwd:
-            if overlap_proposal_backward:
-                if not losses_on_side:          # (else: the segment is open already, the losses launch heads it)
-                    side = _second_stream(model, dev)
-                    fj.fork(side)
-                crosses_to(side, rctx, d_wps, d_o, d_d)
-                pos_ready = None
-                if tail_on_side and not serialize_streams and exchange is None:
-                    pos_ready = model.__dict__.get("_pos_ready_event")
-                    if pos_ready is None:
-                        pos_ready = model.__dict__["_pos_ready_event"] = K.Event()
-                with torch.cuda.stream(side):
-                    sources_early = bool(_proposal_backward(model, rctx, d_wps, up, d_o, d_d, collect=ray_sources,
-                                                            optimizer=proposal_optimizer, position_ready=pos_ready))
-                crosses_to(main, ray_sources)
-                if serialize_streams:
-                    K.stream_wait_stream(main, side)
+        if prop_on_side:
+            if not losses_on_side:          # (else: the segment is open already, the losses launch heads it)
+                fj.fork(side)
+            crosses_to(side, rctx, d_wps, d_o, d_d)
+            early = pos_ready if (tail_on_side and not serialize_streams and exchange is None) else None
+            with torch.cuda.stream(side):
+                sources_early = bool(_proposal_backward(model, rctx, d_wps, None, d_o, d_d, collect=ray_sources,
+                                                        optimizer=proposal_optimizer, position_ready=early))
+            crosses_to(main, ray_sources)
+            if serialize_streams:
+                K.stream_wait_stream(main, side)
         if getattr(rctx, "composite_grads", None) is not None:
             d_density, d_rgb_s, d_logit = rctx.composite_grads
         elif losses_on_side:
@@ -1099,115 +1121,89 @@ def fused_forward_backward(model, ray_bundle, batch, jitter: Optional[List[Tenso
         if use_dist:
             _distortion_backward(model, rctx, d_density)     # unit upstream, on the launch stream, in place
         fld = model.field
-        net, gnet = fld.net_struct(), fld.net_struct(grads=True)
-        d_pos = None
-        if ray_grads is not None and rctx.field_jacobian is not None:
-            d_feats, d_pos = K.field_mlp_bwd(net, gnet, rays, S, rctx.field_feats, rctx.field_h, rctx.field_selector,
-                                             d_density, d_rgb_s, d_logit, jacobian=rctx.field_jacobian,
-                                             weight_adam=weight_adam, semgrad=semgrad)
-        else:
-            d_feats = K.field_mlp_bwd(net, gnet, rays, S, rctx.field_feats, rctx.field_h, rctx.field_selector, d_density,
-                                      d_rgb_s, d_logit, weight_adam=weight_adam, semgrad=semgrad)
-        field_source = None
-        if ray_grads is not None:
-            if d_pos is not None:
-                field_source = (fld.warp_struct(), fin["euclid"], S, d_pos)
-            else:
-                # no saved Jacobian (the model is not in training mode): the gather path reads the TABLE, which the
-                # fused scatter below may update in place — gather now
-                partial = K.hash_encode_input_grad(net.grid, fld.warp_struct(), rays, fin["euclid"], S, d_feats)
-                field_source = (fld.warp_struct(), fin["euclid"], S, partial)
-        if tail_on_side and sources_early:
-            # a step that trains the proposal networks: the second stream is the longer chain (their backward, then the
-            # look-ahead that needs their step AND the cameras'), so the reduction + camera step go to THIS stream, between
-            # the MLP backward and the table scatter, and the look-ahead only waits for them and for the proposal scatter
-            K.stream_wait_event(main, pos_ready)
-            K.position_grad_reduce_multi(ray_sources + [field_source], rays, d_o, d_d, accumulate=False)
+        d_feats, field_source = _field_backward(fld, rays, fin["euclid"], S, rctx.field_feats, rctx.field_h,
+                                                rctx.field_selector, d_density, d_rgb_s, d_logit, semgrad=semgrad,
+                                                weight_adam=weight_adam, want_position=ray_grads is not None,
+                                                jacobian=rctx.field_jacobian)
+
+        def reduce_ray_grads_then_cameras():
+            if ray_grads is not None:
+                # one launch: proposal levels first, the field last (the order the separate launches added them in)
+                K.position_grad_reduce_multi(ray_sources + [field_source], rays, d_o, d_d, accumulate=False)
             if after_ray_grads is not None:
                 after_ray_grads()
-            tail_ready = model.__dict__.get("_tail_ready_event")
-            if tail_ready is None:
-                tail_ready = model.__dict__["_tail_ready_event"] = K.Event()
-            tail_ready.record(main)                # the cameras have taken their step
-        elif tail_on_side:
-            tail_ready = model.__dict__.get("_tail_ready_event")
-            if tail_ready is None:
-                tail_ready = model.__dict__["_tail_ready_event"] = K.Event()
-            tail_ready.record(main)                # the MLP backward (its d_pos) is enqueued
-        def scatter():
-            if exchange is None and table_adam is not None:
-                K.hash_encode_bwd_adam(gnet.grid, fld.warp_struct(), rays, fin["euclid"], S, d_feats, table_adam)
-            elif exchange is None:
-                K.hash_encode_bwd(gnet.grid, fld.warp_struct(), rays, fin["euclid"], S, d_feats)
-            else:
-                n_lv = int(gnet.grid.n_levels)
-                per = -(-n_lv // max(1, exchange.level_groups))
-                for lb in range(0, n_lv, per):
-                    cnt = min(per, n_lv - lb)
-                    K.hash_encode_bwd(gnet.grid, fld.warp_struct(), rays, fin["euclid"], S, d_feats, lb, cnt)
-                    exchange.levels_done(lb, cnt)      # this slice of the gradient table is final: all-reduce it now
-                exchange.field_done()
 
-        def tail(first=True, last=True):
-            """The second stream's segment; with a gradient exchange in two parts: first = up to the issue of the small
-            collectives (after_ray_grads), last = their waits + optimiser steps (exchange_finish) and the look-ahead."""
-            if side is None:                       # a step without a proposal backward: the event is the whole fork
-                side_ = _second_stream(model, dev)
-            else:
-                side_ = side
-            if first:
-                # behind the scatter (serialize_streams) instead of underneath it
-                fj.fork(side_, None if serialize_streams else tail_ready)
-                crosses_to(side_, ray_sources, field_source, d_o, d_d, rays)
-            with torch.cuda.stream(side_):
-                if first and not sources_early:
-                    if ray_grads is not None:
-                        K.position_grad_reduce_multi(ray_sources + [field_source], rays, d_o, d_d, accumulate=False)
-                    if after_ray_grads is not None:
-                        after_ray_grads()
-                if last:
-                    if exchange_finish is not None:
-                        exchange_finish()
-                    if ahead is not None:
-                        ahead()
+        def finish_small_groups_then_look_ahead():
+            if exchange_finish is not None:
+                exchange_finish()
+            if ahead is not None:
+                ahead()
 
-        if tail_on_side and exchange is not None and not serialize_streams and exchange.level_groups <= 1:
-            # Gradient exchange, host order (the host is only ~0.2 ms ahead of the GPU on this path, so what it enqueues
-            # first matters): (1) the scatter's launches — the critical chain; (2) the second stream's segment up to the
-            # ISSUE of the small collectives (proposal networks 10.5 MB, poses 2 KB), so that they precede the field's
+        if tail_on_side:
+            if sources_early:
+                # a step that trains the proposal networks: the second stream is the longer chain (their backward, then the
+                # look-ahead that needs their step AND the cameras'), so the reduction + camera step go to THIS stream, between
+                # the MLP backward and the table scatter, and the look-ahead only waits for them and for the proposal scatter
+                K.stream_wait_event(main, pos_ready)
+                reduce_ray_grads_then_cameras()
+            # what the second stream's segment waits for: the cameras' step (sources_early), else the MLP backward (its d_pos)
+            tail_ready.record(main)
+
+        # ---- the table scatter, on the launch stream ----
+        # (held: the collectives of the exchange are issued by the schedule below, not as each level group's scatter is enqueued)
+        held = bool(tail_on_side and exchange is not None and not serialize_streams and exchange.level_groups <= 1)
+        grid, warp = fld.net_struct(grads=True).grid, fld.warp_struct()
+        if exchange is None and table_adam is not None:
+            K.hash_encode_bwd_adam(grid, warp, rays, fin["euclid"], S, d_feats, table_adam)
+        elif exchange is None:
+            K.hash_encode_bwd(grid, warp, rays, fin["euclid"], S, d_feats)
+        else:
+            if held:
+                exchange.hold = True
+            n_lv = int(grid.n_levels)
+            per = -(-n_lv // max(1, exchange.level_groups))
+            for lb in range(0, n_lv, per):
+                cnt = min(per, n_lv - lb)
+                K.hash_encode_bwd(grid, warp, rays, fin["euclid"], S, d_feats, lb, cnt)
+                exchange.levels_done(lb, cnt)      # this slice of the gradient table is final: all-reduce it now
+            exchange.field_done()
+
+        # ---- what follows the scatter: one of three schedules ----
+        if not tail_on_side:
+            # Everything behind the scatter on the launch stream (one stream, or a second one that held the losses and the
+            # proposal backward only).
+            if side is not None:
+                fj.join()                              # proposal gradients (and their ray-gradient sources) are final
+                for src in ray_sources or ():
+                    src[3].record_stream(main)
+            elif prop_bwd:
+                _proposal_backward(model, rctx, d_wps, None, d_o, d_d, collect=ray_sources, optimizer=proposal_optimizer)
+            reduce_ray_grads_then_cameras()
+            finish_small_groups_then_look_ahead()
+        elif held:
+            # Two streams, gradient exchange, host order (the host is only ~0.2 ms ahead of the GPU on this path, so what it
+            # enqueues first matters): (1) the scatter's launches — the critical chain; (2) the second stream's segment up to
+            # the ISSUE of the small collectives (proposal networks 10.5 MB, poses 2 KB), so that they precede the field's
             # 67 MB on the communicator's stream, which runs collectives in issue order; (3) the field's collective — the
             # scatter is still running on the GPU; (4) the small groups' waits + optimiser steps and the look-ahead.
             # (Enqueueing the whole segment before the scatter left the launch stream idle for ~60 us per step, round 4
             # kernel trace profiles/r04_raw/kt_exchange_high_step.txt.)
-            exchange.hold = True
-            scatter()
-            tail(first=True, last=False)
-            exchange.issue()
-            tail(first=False, last=True)
-            fj.join()
-            fj.check()
-            return _scaled_distortion_loss(model, loss_dict, scale_distortion_loss), metrics_dict
-        scatter()
-        if tail_on_side:
-            tail()
-            fj.join()                              # every local of this call outlives the second stream's launches
-            fj.check()
-            return _scaled_distortion_loss(model, loss_dict, scale_distortion_loss), metrics_dict
-        if side is not None:
-            fj.join()                              # proposal gradients (and their ray-gradient sources) are final
-            for src in ray_sources or ():
-                src[3].record_stream(main)
-        elif prop_bwd:
-            _proposal_backward(model, rctx, d_wps, up, d_o, d_d, collect=ray_sources, optimizer=proposal_optimizer)
-        if ray_grads is not None:
-            # one launch: proposal levels first, the field last (the order the separate launches added them in)
-            K.position_grad_reduce_multi(ray_sources + [field_source], rays, d_o, d_d, accumulate=False)
-        if after_ray_grads is not None:
-            after_ray_grads()
-        if exchange_finish is not None:
-            exchange_finish()
-        if ahead is not None:
-            ahead()
+            fj.fork(side, tail_ready)
+            crosses_to(side, ray_sources, field_source, d_o, d_d, rays)
+            with torch.cuda.stream(side):
+                reduce_ray_grads_then_cameras()
+            exchange.issue()                           # from the launch stream: the field's collective follows the scatter
+            with torch.cuda.stream(side):
+                finish_small_groups_then_look_ahead()
+        else:
+            # Two streams: the second one's segment runs underneath the scatter — behind it with serialize_streams.
+            fj.fork(side, None if serialize_streams else tail_ready)
+            crosses_to(side, ray_sources, field_source, d_o, d_d, rays)
+            with torch.cuda.stream(side):
+                if not sources_early:
+                    reduce_ray_grads_then_cameras()
+                finish_small_groups_then_look_ahead()
+        fj.join()                                      # every local of this call outlives the second stream's launches
         fj.check()
     return _scaled_distortion_loss(model, loss_dict, scale_distortion_loss), metrics_dict
 
@@ -1763,26 +1759,18 @@ class TrainingSteps:
         model, opt, sampler, batcher = self.model, self.optimizer, self.model.proposal_sampler, self.batcher
         sc = self._scalars
         sampler._anneal = model.anneal_at(step)                          # set_anneal(step)
-        # optimiser scalars of THIS update (FusedAdam.table_adam_args / weight_adam_args: lr at the current scheduler step,
-        # step count + 1), then what optimizer.step(skip, done) does to the counters once everything is fused
-        groups, count = opt.groups, opt.step_count
-        for name, slot in (("fields", 0), ("proposal_networks", 1)):
-            g = groups[name]
-            sc.adam[slot].lr = (exponential_decay_lr(count, g["lr"], g["lr_final"], g["max_steps"])
-                                if g.get("lr_final") is not None else g["lr"])
-            sc.adam[slot].step = opt.group_steps[name] + 1
-        skip = () if (updated or not opt.skip_groups_without_grad) else ("proposal_networks",)
-        opt.step_count = count + 1
-        for name in opt.group_steps:
-            if name not in skip:
-                opt.group_steps[name] += 1
-        if self.camera is not None:
-            sc.adam[2].lr, sc.adam[2].step = self.camera[1].advance()
         # _render's bookkeeping
         model.__dict__["_ahead_used"] = model.__dict__.get("_ahead_used", 0) + 1
         if updated:
             sampler._steps_since_update = 0
         model._last_render_updated = bool(updated)
+        # optimiser scalars of THIS update (what FusedAdam.table_adam_args / weight_adam_args put into the fused kernels'
+        # structs), then what optimizer.step(skip, done) does to the counters once everything is fused
+        for name, slot in (("fields", 0), ("proposal_networks", 1)):
+            sc.adam[slot].lr, sc.adam[slot].step = opt.next_update(name)
+        opt.advance(skipped_groups(model, opt))
+        if self.camera is not None:
+            sc.adam[2].lr, sc.adam[2].step = self.camera[1].advance()
         # the look-ahead of iteration step + 1 (TrainingSteps._draw / FruitModel.sample_ahead)
         batcher._offset = getattr(batcher, "_offset", 0) + 1
         sc.prologue_offset = batcher._offset & 0xFFFFFFFFFFFFFFFF

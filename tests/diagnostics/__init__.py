@@ -2,7 +2,7 @@
 pytest.  Test infrastructure: some replay a step / an export in the CPU oracle next to the HIP path (they import oracle/),
 the others watch the HIP path itself.
 
-oracle next to HIP     spike_vs_oracle, trained_export_check, golden_big_dbg, golden_raygrad_dbg, adam_zero_grad_dbg
+oracle next to HIP     spike_vs_oracle, trained_export_check, golden_big_dbg, adam_zero_grad_dbg
 timing of the loop     early_steps (per-window step time, host enqueue time, allocator growth from step 0)
 reproducibility        big_determinism (fruit_nerf_big, one / two streams, sampling ahead, eval passes in between),
                        long_divergence (parameter digests every N steps of long runs, across modes and processes),
