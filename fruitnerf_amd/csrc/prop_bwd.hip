@@ -15,12 +15,67 @@ namespace fnr {
 //            with the samples on the K axis (3 MFMAs per 4 samples; operands are single conflict-light LDS
 //            reads).  A thread-per-weight loop over the 256 samples read two LDS words per FMA and was LDS-bound
 //            (~45 us of the 73 us this kernel took for 1 M samples).
-// Weight gradients leave the workgroup once, at the end (one atomicAdd per weight per workgroup).
+// Weight gradients leave the workgroup once, at the end (one partial vector per workgroup, summed by k_prop_reduce).
+//
+// Where things live (profiles/prop_bwd_diet.md):
+//   * the 16 (2L + 1) + 17 weights sit in LDS and are read as uniform-address broadcasts next to the FMAs that use them.  As
+//     uniform global reads the compiler wanted them in ~100 scalar registers, parked 302 of them in lanes of vector registers
+//     (a fifth of the loop was v_readlane) and fetched them through 158 scalar loads behind 122 waits on every launch.
+//     Every wave stores the WHOLE copy — the same values to the same words — and waits for its own stores: whichever store
+//     a later read sees, it sees the weight.  No workgroup barrier.
+//   * phase 2 of a wave reads only the 64 rows its own lanes wrote in phase 1 (row0 = 64 wave + g), so the two phases are
+//     ordered by wave_lds_fence(), in both directions (the next pass's writes come behind this pass's reads in the wave's
+//     in-order LDS queue).  Only the epilogue, which reuses s_dh across waves, has workgroup barriers: one in front of it
+//     (waves arrive at different times), one behind its writes.
+//   * the next pass's inputs (saved features, d_density, the ray) are loaded at the top of this pass and are in flight
+//     while it computes.  The position gradient's 8 L corner rows stay behind the MLP: gathered ahead of it they do not fit
+//     the 168 registers of three waves per SIMD (__launch_bounds__(256, 3): without the bound the scheduler took 256).
+// Every per-sample expression, the order in which a wave's MFMA accumulators take its samples, the per-thread db1 sum and
+// the (w0 + w1) + (w2 + w3) combination are what they were: tests/test_gpu_prop_bwd_same_bits.py.
 // ------------------------------------------------------------------------------------------------
 constexpr int PROP_PART = 320;   // floats per workgroup partial: dW0 tile 256 + dW1 16 + db0 16 + db1 (+ pad)
 
+// this wave's LDS traffic so far is done before anything behind this line starts (field_mlp_bwd.hip has the same)
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// what one sample of a pass reads from global memory, as loaded (zeros beyond N: such a sample contributes nothing)
+template <int L>
+struct PropInputs {
+  float2 f[L];
+  float dd, o[3], d[3], t0, t1;
+};
+template <int L>
+__device__ __forceinline__ void prop_load(PropInputs<L>& in, const RaySource& src, long long n, long long N,
+                                          const float2* __restrict__ feat_save, const float* __restrict__ d_density) {
+#pragma unroll
+  for (int l = 0; l < L; ++l) in.f[l] = make_float2(0.0f, 0.0f);
+  in.dd = in.t0 = in.t1 = 0.0f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) in.o[a] = in.d[a] = 0.0f;
+  if (n < N) {
+    const long long r = n / src.S;   // (RaySource::position's addresses)
+    const int k = (int)(n - r * src.S);
+    const float* b = src.euclid + r * (src.S + 1) + k;
+    in.t0 = b[0];
+    in.t1 = b[1];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      in.o[a] = src.rays.origins[3 * r + a];
+      in.d[a] = src.rays.directions[3 * r + a];
+    }
+#pragma unroll
+    for (int l = 0; l < L; ++l) in.f[l] = ntc_load<NT_PROP_FEATS>(&feat_save[(size_t)l * N + n]);
+    in.dd = d_density[n];
+  }
+}
+
 template <int L, int H, bool POSGRAD>
-__global__ __launch_bounds__(256) void k_prop_bwd(GridDev grid, float4* __restrict__ d_xw, Warp warp, RaySource src,
+__global__ __launch_bounds__(256, 3) void k_prop_bwd(GridDev grid, float4* __restrict__ d_xw, Warp warp, RaySource src,
                                                   long long N, const float* __restrict__ w0,
                                                   const float* __restrict__ b0, const float* __restrict__ w1,
                                                   const float* __restrict__ b1, const float2* __restrict__ feat_save,
@@ -30,78 +85,103 @@ __global__ __launch_bounds__(256) void k_prop_bwd(GridDev grid, float4* __restri
   __shared__ float s_dh[256][H + 1];   // d hidden (pre-activation)
   __shared__ float s_ha[256][H + 1];   // relu(hidden) * d_out  (for dW1)
   __shared__ float s_f[256][K + 1];    // input features
-  __shared__ float s_do[256];          // d_out
+  constexpr int W0 = 0, B0 = H * K, W1 = B0 + H, B1 = W1 + H, NW = B1 + 1;   // the weights' copy: w0 [H][K] | b0 | w1 | b1
+  __shared__ __attribute__((aligned(16))) float s_w[(NW + 3) / 4 * 4];
+  __shared__ float s_db1[4];           // the waves' db1 sums
   static_assert(H == 16 && K <= 16, "phase 2 is a single 16x16 MFMA tile");
   using f32x4 = __attribute__((ext_vector_type(4))) float;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int j = lane & 15, g = lane >> 4;
+  const int tid0 = threadIdx.x;
   // accumulators (C layout: lane holds column j, rows 4 g + r): dW0[o][k = j], db0[o] in column 0 of d3,
   // dW1[o] in column 0 of d2; db1 per thread
   f32x4 d1 = {0.f, 0.f, 0.f, 0.f}, d2 = {0.f, 0.f, 0.f, 0.f}, d3 = {0.f, 0.f, 0.f, 0.f};
   float db1 = 0.0f;
-  const float ones_col0 = (j == 0) ? 1.0f : 0.0f;  // B operand that sums over the samples into column 0
   const long long n_iter = (N + 255) / 256;
+#pragma unroll
+  for (int i = tid0 & 63; i < NW; i += 64) s_w[i] = i < B0 ? w0[i] : i < W1 ? b0[i - B0] : i < B1 ? w1[i - W1] : b1[0];
+  PropInputs<L> in;
+  prop_load(in, src, (long long)blockIdx.x * 256 + tid0, N, feat_save, d_density);
+  wave_lds_fence();
   for (long long it = blockIdx.x; it < n_iter; it += gridDim.x) {
+    asm volatile("" ::: "memory");   // the weights are loop-invariant LDS reads: keep them inside the loop (field_mlp.hip)
+    // ... and what hangs on the thread id: an opaque copy makes the LDS row addresses per-use VALU ops, not registers held
+    // across the pass (field_mlp_bwd.hip)
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 15, g = lane >> 4;
+    const float ones_col0 = (j == 0) ? 1.0f : 0.0f;  // B operand that sums over the samples into column 0
+    // ... and on N and the table size: 2 L + L per-level base addresses are scalar arithmetic per pass, not scalar registers
+    // held across it (the position-gradient forms ran out of them)
+    long long Ns = N;
+    int log2_T = grid.log2_T;
+    asm volatile("" : "+s"(Ns), "+s"(log2_T));
     const long long n = it * 256 + tid;
     float f[K], dout = 0.0f;
 #pragma unroll
-    for (int k = 0; k < K; ++k) f[k] = 0.0f;
+    for (int l = 0; l < L; ++l) {
+      f[2 * l] = in.f[l].x;
+      f[2 * l + 1] = in.f[l].y;
+    }
     bool sel = false;
     float x[3] = {0.f, 0.f, 0.f};
     if (n < N) {
       float px, py, pz;
-      src.position(n, px, py, pz);
+      ray_position(in.o, in.d, in.t0, in.t1, px, py, pz);
       sel = warp_position(warp, px, py, pz, x);
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        const float2 v = ntc_load<NT_PROP_FEATS>(&feat_save[(size_t)l * N + n]);
-        f[2 * l] = v.x;
-        f[2 * l + 1] = v.y;
-      }
     }
+    const float dd = in.dd;
+    // the next pass's inputs, in flight behind this pass's work (none beyond the last pass: n >= N there)
+    prop_load(in, src, n + gridDim.x * 256ll, Ns, feat_save, d_density);
     float a[H];
-    float out = b1[0];
+    float out = s_w[B1];
 #pragma unroll
     for (int o = 0; o < H; ++o) {
-      float t = b0[o];
+      float t = s_w[B0 + o];
 #pragma unroll
-      for (int k = 0; k < K; ++k) t = fmaf(w0[o * K + k], f[k], t);
+      for (int k = 0; k < K; ++k) t = fmaf(s_w[W0 + o * K + k], f[k], t);
       a[o] = t;
-      out = fmaf(w1[o], fmaxf(t, 0.0f), out);
+      out = fmaf(s_w[W1 + o], fmaxf(t, 0.0f), out);
     }
-    if (n < N && sel) dout = d_density[n] * expf(fminf(fmaxf(out, -15.0f), 15.0f));  // trunc_exp backward
+    __builtin_amdgcn_sched_barrier(0);   // phase boundaries for the scheduler (here and behind df): register pressure stays local
+    if (n < N && sel) dout = dd * expf(fminf(fmaxf(out, -15.0f), 15.0f));  // trunc_exp backward
+    asm volatile("" ::: "memory");   // (read w0 again below, not 16 K registers held from above)
     float df[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) df[k] = 0.0f;
 #pragma unroll
     for (int o = 0; o < H; ++o) {
-      const float dh = (a[o] > 0.0f) ? dout * w1[o] : 0.0f;
+      const float dh = (a[o] > 0.0f) ? dout * s_w[W1 + o] : 0.0f;
       s_dh[tid][o] = dh;
       s_ha[tid][o] = fmaxf(a[o], 0.0f) * dout;
 #pragma unroll
-      for (int k = 0; k < K; ++k) df[k] = fmaf(dh, w0[o * K + k], df[k]);
+      for (int k = 0; k < K; ++k) df[k] = fmaf(dh, s_w[W0 + o * K + k], df[k]);
     }
+    __builtin_amdgcn_sched_barrier(0);
+    // df is formed HERE, by every lane: its only readers sit behind `n < N`, and the compiler sank the 16 K FMAs there and held
+    // all of w0 in registers for them (the loads do not sink past the stores above)
+#pragma unroll
+    for (int k = 0; k < K; ++k) asm volatile("" : "+v"(df[k]));
 #pragma unroll
     for (int k = 0; k < K; ++k) s_f[tid][k] = f[k];
     db1 += dout;
     if (n < N) {
 #pragma unroll
-      for (int l = 0; l < L; ++l) ntc_store<NT_PROP_DFEATS_ST>(&d_feats[(size_t)l * N + n], make_float2(df[2 * l], df[2 * l + 1]));
+      for (int l = 0; l < L; ++l) ntc_store<NT_PROP_DFEATS_ST>(&d_feats[(size_t)l * Ns + n], make_float2(df[2 * l], df[2 * l + 1]));
     }
     if constexpr (POSGRAD) {
       // gradient w.r.t. the unit-cube position (camera-pose optimisation): re-gather the corner rows of every level
       // and contract with d(blend weights)/d(offset) (position_grad.hip has the main-field version)
       if (n < N) {
-        const uint32_t hmask = (1u << grid.log2_T) - 1u;
+        const uint32_t hmask = (1u << log2_T) - 1u;
         float gx = 0.0f, gy = 0.0f, gz = 0.0f;
 #pragma unroll
         for (int l = 0; l < L; ++l) {
-          const int scaling = grid.scalings[l];
+          int scaling = grid.scalings[l];
+          asm volatile("" : "+s"(scaling));   // (float)scaling formed here, not eight vector registers held across the loop
           const GridLevel gl = grid_cell(x, scaling);
           uint32_t hh[8];
           grid_corners(gl, hmask, hh);
-          const float2* lt = grid.table + ((size_t)l << grid.log2_T);
+          const float2* lt = grid.table + ((size_t)l << log2_T);
           float dk[8];
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
@@ -114,11 +194,13 @@ __global__ __launch_bounds__(256) void k_prop_bwd(GridDev grid, float4* __restri
           gx += s * (oz * (oy * (dk[0] - dk[3]) + my * (dk[1] - dk[2])) + mz * (oy * (dk[4] - dk[7]) + my * (dk[5] - dk[6])));
           gy += s * (oz * (ox * (dk[0] - dk[1]) + mx * (dk[3] - dk[2])) + mz * (ox * (dk[4] - dk[5]) + mx * (dk[7] - dk[6])));
           gz += s * (oy * (ox * (dk[0] - dk[4]) + mx * (dk[3] - dk[7])) + my * (ox * (dk[1] - dk[5]) + mx * (dk[2] - dk[6])));
+          // L > 5: the gathers in two groups of at most four levels (all 16 L rows in flight at once do not fit 168 registers)
+          if (L > 5 && l + 1 == (L + 1) / 2) __builtin_amdgcn_sched_barrier(0);
         }
         d_xw[n] = make_float4(gx, gy, gz, 0.0f);
       }
     }
-    __syncthreads();
+    wave_lds_fence();   // this wave's rows are written
     // phase 2: this wave's 64 samples, 4 per MFMA step.  A[i = o][kk] = dh / ha of sample 4 step + kk,
     // B[kk][j = k] = feature k of that sample (0 beyond K)
     const int row0 = 64 * wave + g;
@@ -131,9 +213,14 @@ __global__ __launch_bounds__(256) void k_prop_bwd(GridDev grid, float4* __restri
       d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, ones_col0, d2, 0, 0, 0);
       d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, ones_col0, d3, 0, 0, 0);
     }
-    __syncthreads();
+    wave_lds_fence();   // ... and read: the next pass may overwrite them
   }
-  // combine the 4 waves through LDS (reusing s_dh), then one atomicAdd per weight per workgroup
+  // combine the 4 waves through LDS (reusing s_dh: rows of EVERY wave, so all of them must have left the loop)
+  __syncthreads();
+  int tid = tid0;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, g = lane >> 4;
   float* red = &s_dh[0][0];  // [4 waves][3][16 rows][16 cols]
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -142,7 +229,7 @@ __global__ __launch_bounds__(256) void k_prop_bwd(GridDev grid, float4* __restri
     red[((wave * 3 + 2) * 16 + 4 * g + r) * 16 + j] = d3[r];
   }
   db1 = wave_sum(db1);
-  if (lane == 0) s_do[wave] = db1;
+  if (lane == 0) s_db1[wave] = db1;
   __syncthreads();
   {
     // one partial vector per workgroup: [dW0 16x16 | dW1 16 | db0 16 | db1], summed by k_prop_reduce.  Atomics
@@ -158,7 +245,7 @@ __global__ __launch_bounds__(256) void k_prop_bwd(GridDev grid, float4* __restri
       part[256 + o] = total(1);
       part[272 + o] = total(2);
     }
-    if (tid == 0) part[288] = (s_do[0] + s_do[1]) + (s_do[2] + s_do[3]);
+    if (tid == 0) part[288] = (s_db1[0] + s_db1[1]) + (s_db1[2] + s_db1[3]);
   }
 }
 
