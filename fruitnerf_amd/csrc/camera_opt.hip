@@ -11,6 +11,7 @@
 // shared rows.
 // mode="SE3" (MODE = FNR_POSE_SE3): delta[k] = exp_map_SE3(pose_adjustment[k]) — camera_math.hpp::se3_exp, whose translation
 // depends on the rotation part; composition, ray generation and the ray gradients that feed the tail are the same.
+#include "adam.hpp"
 #include "camera_math.hpp"
 #include "sequencer.hpp"
 

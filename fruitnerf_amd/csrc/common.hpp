@@ -380,78 +380,4 @@ static inline RaysDev make_rays(const fnr_rays* r) {
   return d;
 }
 
-
-// Optimiser step fused into the kernel that produces a gradient (single-process training).  Hash table: the accumulate
-// workgroup that owns a bin has the bin's summed gradient in LDS, so it applies torch.optim.Adam / RAdam to those rows
-// right there (hash_scatter.hip); camera poses: the workgroup of a camera finishes its 6 gradients (camera_opt.hip).  The gradient table
-// is then neither read-modify-written here nor read and zeroed by the optimiser pass: 40 -> 24 bytes of HBM traffic
-// per table parameter and step.  Same operations in the same order as k_adam / k_radam (train.hip): bit-identical
-// parameters and moments.
-struct TableAdam {
-  float2 *p, *m, *v;  // the table's slices of the parameter / exp_avg / exp_avg_sq arenas, [L << log2_T] rows
-  float lr, b1, b2, eps, bc1, bc2_sqrt, rect, grad_scale, weight_decay;
-  int radam;
-  unsigned* touched;  // one bit per pair of rows: ever received a gradient (nullable; fnr_table_adam.touched)
-};
-__device__ __forceinline__ void table_adam_update(const TableAdam& a, float g, float& P, float& M, float& V) {
-  float gr = g * a.grad_scale;
-  if (a.weight_decay != 0.0f) gr = gr + a.weight_decay * P;
-  M = M + (gr - M) * (1.0f - a.b1);
-  V = V * a.b2 + (1.0f - a.b2) * gr * gr;
-  if (!a.radam) {
-    const float step_size = a.lr / a.bc1;
-    const float denom = sqrtf(V) / a.bc2_sqrt + a.eps;
-    P = P - step_size * (M / denom);
-  } else {
-    const float mhat = M / a.bc1;
-    if (a.rect >= 0.0f) {
-      const float adaptive = a.bc2_sqrt / (sqrtf(V) + a.eps);
-      P = P - a.lr * (mhat * a.rect * adaptive);
-    } else {
-      P = P - a.lr * mhat;
-    }
-  }
-}
-// The optimiser step of a parameter taken by the thread that finishes its gradient entry (k_reduce_dw,
-// k_embedding_grad, k_prop_reduce in prop_bwd.hip: single writers): the parameter / moment arrays parallel the gradient arena.
-struct WeightAdam {
-  TableAdam t;               // hyper-parameters and step-dependent scalars (its p / m / v pointers are unused here)
-  long long p_off, m_off, v_off;   // element offsets from a GRADIENT address to the parameter / exp_avg / exp_avg_sq entry
-};
-__device__ __forceinline__ void weight_adam_entry(const WeightAdam& wa, float* __restrict__ g_entry, float s) {
-  const float g = *g_entry + s;
-  float P = g_entry[wa.p_off], M = g_entry[wa.m_off], V = g_entry[wa.v_off];
-  table_adam_update(wa.t, g, P, M, V);
-  g_entry[wa.p_off] = P;
-  g_entry[wa.m_off] = M;
-  g_entry[wa.v_off] = V;
-  *g_entry = 0.0f;
-}
-// host side of TableAdam: the step-dependent scalars exactly as fnr_adam_step / fnr_radam_step compute them (double)
-static inline int make_table_adam(const fnr_table_adam* a, TableAdam& t) {
-  FNR_CHECK_ARG(a && a->params && a->exp_avg && a->exp_avg_sq, "table adam: null argument");
-  FNR_CHECK_ARG(a->algorithm == 0 || a->algorithm == 1, "table adam: algorithm %d (0 = Adam, 1 = RAdam)", a->algorithm);
-  FNR_CHECK_ARG(a->step >= 1, "table adam: step must be >= 1");
-  t.p = reinterpret_cast<float2*>(a->params);
-  t.m = reinterpret_cast<float2*>(a->exp_avg);
-  t.v = reinterpret_cast<float2*>(a->exp_avg_sq);
-  t.lr = a->lr, t.b1 = a->beta1, t.b2 = a->beta2, t.eps = a->eps, t.grad_scale = a->grad_scale, t.weight_decay = a->weight_decay;
-  t.radam = a->algorithm;
-  t.touched = a->touched;
-  FNR_CHECK_ARG(!a->touched || a->weight_decay == 0.0f, "table adam: sparse-touch skipping needs weight_decay = 0");
-  const double bc1 = 1.0 - pow((double)a->beta1, (double)a->step);
-  const double b2t = pow((double)a->beta2, (double)a->step);
-  const double bc2 = 1.0 - b2t;
-  t.bc1 = (float)bc1;
-  t.bc2_sqrt = (float)sqrt(bc2);
-  t.rect = -1.0f;
-  if (a->algorithm == 1) {
-    const double rho_inf = 2.0 / (1.0 - (double)a->beta2) - 1.0;
-    const double rho_t = rho_inf - 2.0 * (double)a->step * b2t / bc2;
-    if (rho_t > 5.0)
-      t.rect = (float)sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
-  }
-  return FNR_OK;
-}
-
 }  // namespace fnr

@@ -23,6 +23,7 @@
 //     of 4 waves x <= 512 registers with all four layers in LDS: SEM_A owns dW of sem0, sem2 and the head (208
 //     registers), SEM_B owns the 128 x 128 layer (256 registers); SEM_B repeats the forward up to s2 and the dX chain
 //     down to Gs2 (1.35x the algorithmic MACs of the branch, no activations through HBM).
+#include "adam.hpp"
 #include "field_layers.hpp"
 #include "field_bf16.hpp"
 #include "sequencer.hpp"

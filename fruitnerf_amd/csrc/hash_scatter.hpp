@@ -1,11 +1,12 @@
 // hash_scatter.hpp — the binned scatter of hash_scatter.hip as the proposal networks' backward (prop_bwd.hip) uses it.
 // Plain host functions: every scatter kernel is instantiated in hash_scatter.hip and nowhere else.
 #pragma once
+#include "adam.hpp"
 #include "hash_sources.hpp"
 
 namespace fnr {
 
-// (TableAdam / table_adam_update: common.hpp — the optimiser step fused into the accumulate kernel)
+// (TableAdam / table_adam_update: adam.hpp — the optimiser step fused into the accumulate kernel)
 // everything one accumulate launch needs about one scatter call (a launch can serve two calls: k_scatter_accumulate2)
 struct AccArgs {
   GridDev grid;

@@ -1,8 +1,7 @@
-// train.hip — losses, their gradients and the fused Adam step for gfx950.
+// train.hip — losses and their gradients for gfx950.
 //   get_loss_dict (fruit_nerf.py:359-372): MSELoss, BCEWithLogitsLoss, interlevel_loss
 //   get_metrics_dict (fruit_nerf.py:396-401): distortion_loss (metric only)
-//   optimiser: torch.optim.Adam semantics (fruit_nerf_config.py:47-56)
-// (the backward of RaySamples.get_weights + renderers: composite_bwd.hip)
+// (the optimiser's sweeps: optim.hip; the backward of RaySamples.get_weights + renderers: composite_bwd.hip)
 // One wave per ray for the per-ray scans; everything here is bandwidth-trivial next to the field kernels.
 #include "common.hpp"
 #include "composite_math.hpp"
@@ -465,240 +464,6 @@ __global__ __launch_bounds__(256, ME <= 4 ? 8 : 1) void k_train_losses(long long
   }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Adam (torch.optim.Adam incl. its L2 weight_decay, no amsgrad), whole arena in one launch; optionally zeroes grads
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_adam(float4* __restrict__ p, float4* __restrict__ g, float4* __restrict__ m,
-                                              float4* __restrict__ v, long long n4, float lr, float b1, float b2,
-                                              float eps, float bc1, float bc2_sqrt, float grad_scale, float weight_decay,
-                                              int zero_grad) {
-  const float step_size = lr / bc1;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    // moments and gradient: read once, written once per step — streaming, so that the sweep (the exchange path's 88 us over the
-    // main table) leaves the table's parameters in the caches for the next encode (round 5's hints, now on the unfused sweep too)
-    float4 P = p[i], G = ntc_load<NT_MOMENT_LD>(&g[i]), M = ntc_load<NT_MOMENT_LD>(&m[i]), V = ntc_load<NT_MOMENT_LD>(&v[i]);
-    float* pp = reinterpret_cast<float*>(&P);
-    float* gp = reinterpret_cast<float*>(&G);
-    float* mp = reinterpret_cast<float*>(&M);
-    float* vp = reinterpret_cast<float*>(&V);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float gr = gp[c] * grad_scale;
-      if (weight_decay != 0.0f) gr = gr + weight_decay * pp[c];   // grad.add(param, alpha=weight_decay)
-      mp[c] = mp[c] + (gr - mp[c]) * (1.0f - b1);           // exp_avg.lerp_(grad, 1 - beta1)
-      vp[c] = vp[c] * b2 + (1.0f - b2) * gr * gr;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-      const float denom = sqrtf(vp[c]) / bc2_sqrt + eps;    // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-      pp[c] = pp[c] - step_size * (mp[c] / denom);          // param.addcdiv_(exp_avg, denom, value=-step_size)
-    }
-    p[i] = P;
-    ntc_store<NT_MOMENT_ST>(&m[i], M);
-    ntc_store<NT_MOMENT_ST>(&v[i], V);
-    if (zero_grad) ntc_store<NT_MOMENT_ST>(&g[i], make_float4(0.f, 0.f, 0.f, 0.f));
-  }
-}
-
-// torch.optim.RAdam (fruit_nerf_big / fruit_nerf_huge use it for every group, fruit_nerf_config.py:97-106,148-160):
-// same moments as Adam; the update is rectified once the variance estimate is tractable (rho_t > 5), plain momentum
-// before.  `rect` < 0 encodes "not rectified"; all step-dependent scalars are computed on the host in double.
-__global__ __launch_bounds__(256) void k_radam(float4* __restrict__ p, float4* __restrict__ g, float4* __restrict__ m,
-                                               float4* __restrict__ v, long long n4, float lr, float b1, float b2,
-                                               float eps, float bc1, float bc2_sqrt, float rect, float grad_scale,
-                                               float weight_decay, int zero_grad) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    // moments and gradient: read once, written once per step — streaming, so that the sweep (the exchange path's 88 us over the
-    // main table) leaves the table's parameters in the caches for the next encode (round 5's hints, now on the unfused sweep too)
-    float4 P = p[i], G = ntc_load<NT_MOMENT_LD>(&g[i]), M = ntc_load<NT_MOMENT_LD>(&m[i]), V = ntc_load<NT_MOMENT_LD>(&v[i]);
-    float* pp = reinterpret_cast<float*>(&P);
-    float* gp = reinterpret_cast<float*>(&G);
-    float* mp = reinterpret_cast<float*>(&M);
-    float* vp = reinterpret_cast<float*>(&V);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float gr = gp[c] * grad_scale;
-      if (weight_decay != 0.0f) gr = gr + weight_decay * pp[c];
-      mp[c] = mp[c] + (gr - mp[c]) * (1.0f - b1);
-      vp[c] = vp[c] * b2 + (1.0f - b2) * gr * gr;
-      const float mhat = mp[c] / bc1;                        // bias_corrected_exp_avg
-      if (rect >= 0.0f) {
-        const float adaptive = bc2_sqrt / (sqrtf(vp[c]) + eps);   // sqrt(bias_correction2) / (exp_avg_sq.sqrt() + eps)
-        pp[c] = pp[c] - lr * (mhat * rect * adaptive);
-      } else {
-        pp[c] = pp[c] - lr * mhat;
-      }
-    }
-    p[i] = P;
-    ntc_store<NT_MOMENT_ST>(&m[i], M);
-    ntc_store<NT_MOMENT_ST>(&v[i], V);
-    if (zero_grad) ntc_store<NT_MOMENT_ST>(&g[i], make_float4(0.f, 0.f, 0.f, 0.f));
-  }
-}
-
-// Adam / RAdam over several spans of one arena in one launch (fnr_adam_step_spans): the spans' float4 chunks are
-// numbered consecutively, a thread finds its span by scanning the (<= 8) cumulative counts.  Per element the same
-// operations in the same order as k_adam / k_radam.
-struct AdamSpansDev {
-  int n;
-  long long cum4[FNR_MAX_ADAM_SPANS + 1];  // chunk index at which span k starts; cum4[n] = total
-  long long off4[FNR_MAX_ADAM_SPANS];      // first float4 of span k in the arena
-  float lr[FNR_MAX_ADAM_SPANS], bc1[FNR_MAX_ADAM_SPANS], bc2_sqrt[FNR_MAX_ADAM_SPANS], rect[FNR_MAX_ADAM_SPANS];
-};
-template <bool RADAM>
-__global__ __launch_bounds__(256) void k_adam_spans(float4* __restrict__ p, float4* __restrict__ g,
-                                                    float4* __restrict__ m, float4* __restrict__ v, AdamSpansDev sp,
-                                                    float b1, float b2, float eps, float grad_scale,
-                                                    float weight_decay, int zero_grad) {
-  const long long total = sp.cum4[sp.n];
-  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < total; c += (long long)gridDim.x * 256) {
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < FNR_MAX_ADAM_SPANS; ++q)
-      if (q < sp.n && c >= sp.cum4[q]) k = q;
-    const long long i = sp.off4[k] + (c - sp.cum4[k]);
-    const float lr = sp.lr[k], bc1 = sp.bc1[k], bc2_sqrt = sp.bc2_sqrt[k], rect = sp.rect[k];
-    const float step_size = lr / bc1;
-    // moments and gradient: read once, written once per step — streaming, so that the sweep (the exchange path's 88 us over the
-    // main table) leaves the table's parameters in the caches for the next encode (round 5's hints, now on the unfused sweep too)
-    float4 P = p[i], G = ntc_load<NT_MOMENT_LD>(&g[i]), M = ntc_load<NT_MOMENT_LD>(&m[i]), V = ntc_load<NT_MOMENT_LD>(&v[i]);
-    float* pp = reinterpret_cast<float*>(&P);
-    float* gp = reinterpret_cast<float*>(&G);
-    float* mp = reinterpret_cast<float*>(&M);
-    float* vp = reinterpret_cast<float*>(&V);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float gr = gp[e] * grad_scale;
-      if (weight_decay != 0.0f) gr = gr + weight_decay * pp[e];
-      mp[e] = mp[e] + (gr - mp[e]) * (1.0f - b1);
-      vp[e] = vp[e] * b2 + (1.0f - b2) * gr * gr;
-      if (!RADAM) {
-        const float denom = sqrtf(vp[e]) / bc2_sqrt + eps;
-        pp[e] = pp[e] - step_size * (mp[e] / denom);
-      } else {
-        const float mhat = mp[e] / bc1;
-        if (rect >= 0.0f) {
-          const float adaptive = bc2_sqrt / (sqrtf(vp[e]) + eps);
-          pp[e] = pp[e] - lr * (mhat * rect * adaptive);
-        } else {
-          pp[e] = pp[e] - lr * mhat;
-        }
-      }
-    }
-    p[i] = P;
-    ntc_store<NT_MOMENT_ST>(&m[i], M);
-    ntc_store<NT_MOMENT_ST>(&v[i], V);
-    if (zero_grad) ntc_store<NT_MOMENT_ST>(&g[i], make_float4(0.f, 0.f, 0.f, 0.f));
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// fnr_adam_step_spans_dev: the spans step with everything a torch.amp.GradScaler decides per step — the loss scale, the
-// "found inf" flag — and the spans' step counters in DEVICE memory, so that the call needs no host round trip.
-//
-// Two launches on the caller's stream, the first of the two choices that keep the counters free of races:
-//   1. k_adam_dev_prologue, ONE workgroup, thread k < n owns span k: reads *found_inf, *grad_scale and steps[k]; unless
-//      the step is skipped it bumps steps[k] and derives the span's step-dependent scalars from the post-increment count,
-//      in double, rounded to float where fnr_adam_step_spans rounds them; writes them to the caller's scalar block.
-//   2. k_adam_spans_dev, the sweep: reads the scalar block only (never a counter), per element the operations of
-//      k_adam_spans in the same order.  A skipped step touches neither parameters nor moments; with zero_grad it still
-//      zeroes the gradient spans, so that an inf / NaN does not leak into the next backward's accumulation.
-// No workgroup reads a counter that another workgroup of the same launch writes: the prologue is one workgroup whose
-// threads own one counter each, the sweep reads what the (stream-ordered) prologue left in the block.
-// ---------------------------------------------------------------------------------------------------
-struct AdamDevScalars {   // the caller's scalar block (FNR_ADAM_DEV_SCALAR_FLOATS floats)
-  float skip, inv_scale;
-  float bc1[FNR_MAX_ADAM_SPANS], bc2_sqrt[FNR_MAX_ADAM_SPANS], rect[FNR_MAX_ADAM_SPANS];
-};
-static_assert(sizeof(AdamDevScalars) <= FNR_ADAM_DEV_SCALAR_FLOATS * sizeof(float), "scalar block too small");
-
-__global__ __launch_bounds__(64) void k_adam_dev_prologue(int n, int radam, float b1, float b2,
-                                                          const float* __restrict__ grad_scale,
-                                                          const float* __restrict__ found_inf,
-                                                          long long* __restrict__ steps,
-                                                          AdamDevScalars* __restrict__ out) {
-  const int k = threadIdx.x;
-  const bool skip = found_inf != nullptr && *found_inf != 0.0f;
-  if (k == 0) {
-    out->skip = skip ? 1.0f : 0.0f;
-    // GradScaler.unscale_: scale.double().reciprocal().float()
-    out->inv_scale = grad_scale != nullptr ? (float)(1.0 / (double)*grad_scale) : 1.0f;
-  }
-  if (k >= n || skip) return;
-  const long long step = steps[k] + 1;
-  steps[k] = step;
-  const double bc1 = 1.0 - pow((double)b1, (double)step);
-  const double b2t = pow((double)b2, (double)step);
-  const double bc2 = 1.0 - b2t;
-  double rect = -1.0;  // not rectified
-  if (radam) {
-    const double rho_inf = 2.0 / (1.0 - (double)b2) - 1.0;
-    const double rho_t = rho_inf - 2.0 * (double)step * b2t / bc2;
-    if (rho_t > 5.0)
-      rect = sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
-  }
-  out->bc1[k] = (float)bc1;
-  out->bc2_sqrt[k] = (float)sqrt(bc2);
-  out->rect[k] = (float)rect;
-}
-
-struct AdamSpansHost {   // what the host knows of the spans: their layout and learning rates
-  int n;
-  long long cum4[FNR_MAX_ADAM_SPANS + 1];
-  long long off4[FNR_MAX_ADAM_SPANS];
-  float lr[FNR_MAX_ADAM_SPANS];
-};
-template <bool RADAM>
-__global__ __launch_bounds__(256) void k_adam_spans_dev(float4* __restrict__ p, float4* __restrict__ g,
-                                                        float4* __restrict__ m, float4* __restrict__ v,
-                                                        AdamSpansHost sp, const AdamDevScalars* __restrict__ sc,
-                                                        float b1, float b2, float eps, float weight_decay,
-                                                        int zero_grad) {
-  const long long total = sp.cum4[sp.n];
-  const bool skip = sc->skip != 0.0f;
-  if (skip && !zero_grad) return;
-  const float grad_scale = sc->inv_scale;
-  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < total; c += (long long)gridDim.x * 256) {
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < FNR_MAX_ADAM_SPANS; ++q)
-      if (q < sp.n && c >= sp.cum4[q]) k = q;
-    const long long i = sp.off4[k] + (c - sp.cum4[k]);
-    if (skip) {   // the step is not taken; its (non-finite) gradient must not reach the next backward
-      ntc_store<NT_MOMENT_ST>(&g[i], make_float4(0.f, 0.f, 0.f, 0.f));
-      continue;
-    }
-    const float lr = sp.lr[k], bc1 = sc->bc1[k], bc2_sqrt = sc->bc2_sqrt[k], rect = sc->rect[k];
-    const float step_size = lr / bc1;
-    // moments and gradient: read once, written once per step — streaming, as in k_adam_spans
-    float4 P = p[i], G = ntc_load<NT_MOMENT_LD>(&g[i]), M = ntc_load<NT_MOMENT_LD>(&m[i]), V = ntc_load<NT_MOMENT_LD>(&v[i]);
-    float* pp = reinterpret_cast<float*>(&P);
-    float* gp = reinterpret_cast<float*>(&G);
-    float* mp = reinterpret_cast<float*>(&M);
-    float* vp = reinterpret_cast<float*>(&V);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float gr = gp[e] * grad_scale;
-      if (weight_decay != 0.0f) gr = gr + weight_decay * pp[e];
-      mp[e] = mp[e] + (gr - mp[e]) * (1.0f - b1);
-      vp[e] = vp[e] * b2 + (1.0f - b2) * gr * gr;
-      if (!RADAM) {
-        const float denom = sqrtf(vp[e]) / bc2_sqrt + eps;
-        pp[e] = pp[e] - step_size * (mp[e] / denom);
-      } else {
-        const float mhat = mp[e] / bc1;
-        if (rect >= 0.0f) {
-          const float adaptive = bc2_sqrt / (sqrtf(vp[e]) + eps);
-          pp[e] = pp[e] - lr * (mhat * rect * adaptive);
-        } else {
-          pp[e] = pp[e] - lr * mhat;
-        }
-      }
-    }
-    p[i] = P;
-    ntc_store<NT_MOMENT_ST>(&m[i], M);
-    ntc_store<NT_MOMENT_ST>(&v[i], V);
-    if (zero_grad) ntc_store<NT_MOMENT_ST>(&g[i], make_float4(0.f, 0.f, 0.f, 0.f));
-  }
-}
-
 }  // namespace fnr
 
 using namespace fnr;
@@ -738,160 +503,6 @@ extern "C" int fnr_distortion(int64_t n_rays, int S, const float* spacing, const
   FNR_PROF(OP_DISTORTION, n_rays * (long long)S);
   hipLaunchKernelGGL(k_distortion, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, as_stream(stream),
                      (long long)n_rays, S, spacing, weights, out);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                             float beta1, float beta2, float eps, int64_t step, float grad_scale, float weight_decay,
-                             int zero_grad, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_adam_step");
-  FNR_CHECK_ARG(params && grads && exp_avg && exp_avg_sq, "adam_step: null argument");
-  FNR_CHECK_ARG(n % 4 == 0 && step >= 1, "adam_step: n must be a multiple of 4 (arena is padded) and step >= 1");
-  if (n == 0) return FNR_OK;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  long long n4 = n / 4;
-  long long blocks = (n4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  FNR_PROF(OP_ADAM, n);
-  hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
-                     reinterpret_cast<float4*>(params), reinterpret_cast<float4*>(grads),
-                     reinterpret_cast<float4*>(exp_avg), reinterpret_cast<float4*>(exp_avg_sq), n4, lr, beta1, beta2,
-                     eps, (float)bc1, (float)sqrt(bc2), grad_scale, weight_decay, zero_grad);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_radam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                              float beta1, float beta2, float eps, int64_t step, float grad_scale, float weight_decay,
-                              int zero_grad, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_radam_step");
-  FNR_CHECK_ARG(params && grads && exp_avg && exp_avg_sq, "radam_step: null argument");
-  FNR_CHECK_ARG(n % 4 == 0 && step >= 1, "radam_step: n must be a multiple of 4 (arena is padded) and step >= 1");
-  if (n == 0) return FNR_OK;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double b2t = pow((double)beta2, (double)step);
-  const double bc2 = 1.0 - b2t;
-  const double rho_inf = 2.0 / (1.0 - (double)beta2) - 1.0;
-  const double rho_t = rho_inf - 2.0 * (double)step * b2t / bc2;
-  double rect = -1.0;  // not rectified
-  if (rho_t > 5.0)
-    rect = sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
-  long long n4 = n / 4;
-  long long blocks = (n4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  FNR_PROF(OP_ADAM, n);
-  hipLaunchKernelGGL(k_radam, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), reinterpret_cast<float4*>(params),
-                     reinterpret_cast<float4*>(grads), reinterpret_cast<float4*>(exp_avg),
-                     reinterpret_cast<float4*>(exp_avg_sq), n4, lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2),
-                     (float)rect, grad_scale, weight_decay, zero_grad);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_adam_step_spans(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int n_spans,
-                                   const fnr_adam_span* spans, int algorithm, float beta1, float beta2, float eps,
-                                   float grad_scale, float weight_decay, int zero_grad, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_adam_step_spans");
-  FNR_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && spans, "adam_step_spans: null argument");
-  FNR_CHECK_ARG(n_spans >= 1 && n_spans <= FNR_MAX_ADAM_SPANS, "adam_step_spans: %d spans (1..%d)", n_spans,
-                FNR_MAX_ADAM_SPANS);
-  FNR_CHECK_ARG(algorithm == 0 || algorithm == 1, "adam_step_spans: algorithm %d (0 = Adam, 1 = RAdam)", algorithm);
-  AdamSpansDev sp;
-  sp.n = n_spans;
-  sp.cum4[0] = 0;
-  long long total_floats = 0;
-  for (int k = 0; k < FNR_MAX_ADAM_SPANS; ++k) {
-    if (k >= n_spans) {
-      sp.cum4[k + 1] = sp.cum4[k];
-      sp.off4[k] = 0;
-      sp.lr[k] = 0.0f, sp.bc1[k] = 1.0f, sp.bc2_sqrt[k] = 1.0f, sp.rect[k] = -1.0f;
-      continue;
-    }
-    const fnr_adam_span& s = spans[k];
-    FNR_CHECK_ARG(s.offset >= 0 && s.count >= 0 && s.offset % 4 == 0 && s.count % 4 == 0 && s.step >= 1,
-                  "adam_step_spans: span %d: offset / count must be multiples of 4, step >= 1", k);
-    // the step-dependent scalars exactly as fnr_adam_step / fnr_radam_step compute them (double)
-    const double bc1 = 1.0 - pow((double)beta1, (double)s.step);
-    const double b2t = pow((double)beta2, (double)s.step);
-    const double bc2 = 1.0 - b2t;
-    double rect = -1.0;
-    if (algorithm == 1) {
-      const double rho_inf = 2.0 / (1.0 - (double)beta2) - 1.0;
-      const double rho_t = rho_inf - 2.0 * (double)s.step * b2t / bc2;
-      if (rho_t > 5.0)
-        rect = sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
-    }
-    sp.off4[k] = s.offset / 4;
-    sp.cum4[k + 1] = sp.cum4[k] + s.count / 4;
-    sp.lr[k] = s.lr, sp.bc1[k] = (float)bc1, sp.bc2_sqrt[k] = (float)sqrt(bc2), sp.rect[k] = (float)rect;
-    total_floats += s.count;
-  }
-  const long long total4 = sp.cum4[n_spans];
-  if (total4 == 0) return FNR_OK;
-  long long blocks = (total4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  FNR_PROF(OP_ADAM, total_floats);
-  float4 *p4 = reinterpret_cast<float4*>(params), *g4 = reinterpret_cast<float4*>(grads);
-  float4 *m4 = reinterpret_cast<float4*>(exp_avg), *v4 = reinterpret_cast<float4*>(exp_avg_sq);
-  if (algorithm == 0)
-    hipLaunchKernelGGL(k_adam_spans<false>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), p4, g4, m4, v4, sp,
-                       beta1, beta2, eps, grad_scale, weight_decay, zero_grad);
-  else
-    hipLaunchKernelGGL(k_adam_spans<true>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), p4, g4, m4, v4, sp,
-                       beta1, beta2, eps, grad_scale, weight_decay, zero_grad);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
-}
-
-extern "C" int fnr_adam_step_spans_dev(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int n_spans,
-                                       const fnr_adam_span* spans, int64_t* steps, int algorithm, float beta1,
-                                       float beta2, float eps, const float* grad_scale, const float* found_inf,
-                                       float weight_decay, int zero_grad, float* scalars, void* stream) {
-  FNR_SEQ_UNRECORDABLE("fnr_adam_step_spans_dev");
-  FNR_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && spans && steps && scalars,
-                "adam_step_spans_dev: null argument");
-  FNR_CHECK_ARG(n_spans >= 1 && n_spans <= FNR_MAX_ADAM_SPANS, "adam_step_spans_dev: %d spans (1..%d)", n_spans,
-                FNR_MAX_ADAM_SPANS);
-  FNR_CHECK_ARG(algorithm == 0 || algorithm == 1, "adam_step_spans_dev: algorithm %d (0 = Adam, 1 = RAdam)", algorithm);
-  AdamSpansHost sp;
-  sp.n = n_spans;
-  sp.cum4[0] = 0;
-  long long total_floats = 0;
-  for (int k = 0; k < FNR_MAX_ADAM_SPANS; ++k) {
-    if (k >= n_spans) {
-      sp.cum4[k + 1] = sp.cum4[k];
-      sp.off4[k] = 0;
-      sp.lr[k] = 0.0f;
-      continue;
-    }
-    const fnr_adam_span& s = spans[k];
-    FNR_CHECK_ARG(s.offset >= 0 && s.count >= 0 && s.offset % 4 == 0 && s.count % 4 == 0,
-                  "adam_step_spans_dev: span %d: offset / count must be multiples of 4", k);
-    sp.off4[k] = s.offset / 4;
-    sp.cum4[k + 1] = sp.cum4[k] + s.count / 4;
-    sp.lr[k] = s.lr;
-    total_floats += s.count;
-  }
-  const long long total4 = sp.cum4[n_spans];
-  long long blocks = (total4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  FNR_PROF(OP_ADAM, total_floats);
-  AdamDevScalars* sc = reinterpret_cast<AdamDevScalars*>(scalars);
-  // the counters advance even over empty spans: they count optimiser steps, not elements
-  hipLaunchKernelGGL(k_adam_dev_prologue, dim3(1), dim3(64), 0, as_stream(stream), n_spans, algorithm, beta1, beta2,
-                     grad_scale, found_inf, reinterpret_cast<long long*>(steps), sc);
-  FNR_LAUNCH_CHECK();
-  if (total4 == 0) return FNR_OK;
-  float4 *p4 = reinterpret_cast<float4*>(params), *g4 = reinterpret_cast<float4*>(grads);
-  float4 *m4 = reinterpret_cast<float4*>(exp_avg), *v4 = reinterpret_cast<float4*>(exp_avg_sq);
-  if (algorithm == 0)
-    hipLaunchKernelGGL(k_adam_spans_dev<false>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), p4, g4, m4, v4,
-                       sp, sc, beta1, beta2, eps, weight_decay, zero_grad);
-  else
-    hipLaunchKernelGGL(k_adam_spans_dev<true>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), p4, g4, m4, v4,
-                       sp, sc, beta1, beta2, eps, weight_decay, zero_grad);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }

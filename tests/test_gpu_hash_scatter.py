@@ -658,7 +658,7 @@ def _update_reference(case, p, g, m, v):
 
 
 def _update_float32(case, p, g, m, v):
-    """k_adam / k_radam's operations in their order, float32 on the CPU (the yardstick of C_P, C_M, C_V)."""
+    """table_adam_update's (adam.hpp) operations in their order, float32 on the CPU (the yardstick of C_P, C_M, C_V)."""
     h = _hyper(case)
     f = lambda x: torch.tensor(x, dtype=torch.float32)   # noqa: E731
     gr = g * f(h["gs"])

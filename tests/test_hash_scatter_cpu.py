@@ -1,6 +1,6 @@
 """tests/test_gpu_hash_scatter.py without a GPU: where its constants and the CPU column of its docstring come from.
 
-The GPU file's tests take the float32 CPU evaluation of their own reference (index_add_ in float32, k_adam / k_radam's
+The GPU file's tests take the float32 CPU evaluation of their own reference (index_add_ in float32, table_adam_update's
 operations in float32) in place of the kernel when handed `FLOAT32` for a device.  Over the GPU file's own inputs that
 evaluation stays within 1/4 of every bound — the factor 4 the kernel gets for its other order of summation — except the
 accumulate test, whose worst rows are the final rounding of prefill + sum alone (outside the constant; round-to-nearest

@@ -141,9 +141,9 @@ def test_streaming_accesses_share_partial_waits_only_in_known_kernels():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_nt_scan
-    known = ("k_scatter_accumulate", "k_prop_bwd", "k_scatter_emit", "k_hash_encode", "k_prop_density", "k_adam", "k_radam")
+    known = ("k_scatter_accumulate", "k_prop_bwd", "k_scatter_emit", "k_hash_encode", "k_prop_density", "k_adam_sweep")
     seen = set()
-    for src in ("hash_scatter.hip", "prop_bwd.hip", "hashgrid.hip", "field_mlp_bf16.hip", "field_mlp_bwd_pw.hip", "position_grad.hip", "train.hip", "composite_bwd.hip"):
+    for src in ("hash_scatter.hip", "prop_bwd.hip", "hashgrid.hip", "field_mlp_bf16.hip", "field_mlp_bwd_pw.hip", "position_grad.hip", "train.hip", "optim.hip", "composite_bwd.hip"):
         for k, r in isa_nt_scan.scan_source(os.path.join(CSRC, src)).items():
             if r["mixed"]:
                 fam = [f for f in known if f in k]
