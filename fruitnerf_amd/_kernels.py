@@ -1151,6 +1151,104 @@ def cloud_estimate_normals(xyz: Tensor, knn: int) -> Tensor:
     return normals
 
 
+def _fit_points(t: Tensor, name: str) -> Tensor:
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3 or not t.is_cuda:
+        raise ValueError(f"{name}: point sets are [n,3] float64 device tensors")
+    return t.contiguous()
+
+
+def _host_ints(values, ctype):
+    values = [int(v) for v in values]
+    return (ctype * max(len(values), 1))(*values), values
+
+
+def cloud_icp(tgt_xyz: Tensor, tgt_offsets, src_xyz: Tensor, src_offsets, src_id, init: Tensor,
+              max_correspondence_distance: float, with_scaling: bool = True, max_iteration: int = 30,
+              relative_fitness: float = 1e-6, relative_rmse: float = 1e-6):
+    """shapes.registration_icp for B problems in one launch: problem b registers source segment src_id[b] of src_xyz
+    (segments src_offsets[s] .. src_offsets[s+1]) onto target segment b of tgt_xyz (tgt_offsets, B + 1 entries); the
+    offsets and ids are host sequences, init is [B,4,4] float64 on the device.
+    -> (transformation [B,4,4], fitness [B], inlier_rmse [B], iterations int32 [B], correspondences int32 [sum of the
+    problems' source sizes], corr_offsets: list of B + 1 ints); all tensors on the device."""
+    tgt_xyz, src_xyz = _fit_points(tgt_xyz, "cloud_icp target"), _fit_points(src_xyz, "cloud_icp source")
+    dev = tgt_xyz.device
+    t_off, t_list = _host_ints(tgt_offsets, C.c_int64)
+    s_off, s_list = _host_ints(src_offsets, C.c_int64)
+    ids, id_list = _host_ints(src_id, C.c_int32)
+    B, S = len(t_list) - 1, len(s_list) - 1
+    if B < 0 or S < 0 or len(id_list) != B:
+        raise ValueError("cloud_icp: tgt_offsets has B + 1 entries, src_id B, src_offsets at least one")
+    if init.dtype != torch.float64 or init.numel() != 16 * B or init.device != dev:
+        raise ValueError("cloud_icp: init is [B,4,4] float64 on the points' device")
+    init = init.contiguous()
+    corr_offsets = [0]
+    for s in id_list:
+        if not 0 <= s < S:
+            raise ValueError(f"cloud_icp: src_id {s} outside 0 .. {S - 1}")
+        corr_offsets.append(corr_offsets[-1] + max(s_list[s + 1] - s_list[s], 0))
+    T = torch.empty(B, 4, 4, dtype=torch.float64, device=dev)
+    fitness = torch.empty(B, dtype=torch.float64, device=dev)
+    rmse = torch.empty(B, dtype=torch.float64, device=dev)
+    iterations = torch.empty(B, dtype=torch.int32, device=dev)
+    corr = torch.empty(corr_offsets[-1], dtype=torch.int32, device=dev)
+    lib = L.load()
+    ws = torch.empty(max(lib.fnr_cloud_icp_workspace_bytes(B), 1), dtype=torch.uint8, device=dev)
+    L.check(lib.fnr_cloud_icp(L.ptr(tgt_xyz), tgt_xyz.shape[0], t_off, B, L.ptr(src_xyz), src_xyz.shape[0], s_off, S, ids,
+                              L.ptr(init), float(max_correspondence_distance), 1 if with_scaling else 0,
+                              int(max_iteration), float(relative_fitness), float(relative_rmse), L.ptr(T),
+                              L.ptr(fitness), L.ptr(rmse), L.ptr(iterations), L.ptr(corr), L.ptr(ws), ws.numel(),
+                              L.stream_ptr(dev)), "cloud_icp")
+    return T, fitness, rmse, iterations, corr, corr_offsets
+
+
+def cloud_hausdorff(a_xyz: Tensor, a_offsets, a_id, src_xyz: Tensor, src_offsets, src_id,
+                    translations: Optional[Tensor] = None, trans_offsets=None, transforms: Optional[Tensor] = None):
+    """shapes.hausdorff_distance(A_b, B_b) for B problems in one launch.  A_b: segment a_id[b] of a_xyz.  B_b: source
+    segment src_id[b] placed at translations[trans_offsets[b] : trans_offsets[b+1]] ([n,3] device rows, stacked like
+    np.vstack), or — for a problem without translations — moved by transforms[b] ([B,4,4] device).  Offsets and ids are
+    host sequences.  -> (distances float64 [B,3] = A->B, B->A, their maximum; witnesses int32 [B,2] = the point of A and
+    the point of the placed B that realise the two directed distances), on the device."""
+    a_xyz, src_xyz = _fit_points(a_xyz, "cloud_hausdorff A"), _fit_points(src_xyz, "cloud_hausdorff source")
+    dev = a_xyz.device
+    a_off, a_list = _host_ints(a_offsets, C.c_int64)
+    s_off, s_list = _host_ints(src_offsets, C.c_int64)
+    aid, aid_list = _host_ints(a_id, C.c_int32)
+    sid, sid_list = _host_ints(src_id, C.c_int32)
+    B = len(aid_list)
+    if len(sid_list) != B or not a_list or not s_list:
+        raise ValueError("cloud_hausdorff: a_id and src_id have one entry per problem")
+    t_off, n_trans, queries = None, 0, 0
+    if trans_offsets is not None:
+        t_off, t_list = _host_ints(trans_offsets, C.c_int64)
+        if len(t_list) != B + 1:
+            raise ValueError("cloud_hausdorff: trans_offsets has B + 1 entries")
+        n_trans = t_list[-1]
+    if n_trans:
+        translations = _fit_points(translations, "cloud_hausdorff translations")
+        if translations.shape[0] != n_trans:
+            raise ValueError("cloud_hausdorff: trans_offsets do not end at the number of translations")
+    if transforms is not None:
+        if transforms.dtype != torch.float64 or transforms.numel() != 16 * B or transforms.device != dev:
+            raise ValueError("cloud_hausdorff: transforms is [B,4,4] float64 on the points' device")
+        transforms = transforms.contiguous()
+    for b in range(B):
+        if not (0 <= aid_list[b] < len(a_list) - 1 and 0 <= sid_list[b] < len(s_list) - 1):
+            raise ValueError(f"cloud_hausdorff: problem {b} names a segment that does not exist")
+        k = (t_list[b + 1] - t_list[b]) if trans_offsets is not None else 0
+        queries += max(a_list[aid_list[b] + 1] - a_list[aid_list[b]], 0)
+        queries += max(k, 1) * max(s_list[sid_list[b] + 1] - s_list[sid_list[b]], 0)
+    dist = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    wit = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    lib = L.load()
+    ws = torch.empty(max(lib.fnr_cloud_hausdorff_workspace_bytes(B, queries), 1), dtype=torch.uint8, device=dev)
+    L.check(lib.fnr_cloud_hausdorff(L.ptr(a_xyz), a_xyz.shape[0], a_off, len(a_list) - 1, L.ptr(src_xyz),
+                                    src_xyz.shape[0], s_off, len(s_list) - 1, B, aid, sid,
+                                    L.ptr(translations) if n_trans else None, n_trans, t_off, L.ptr(transforms),
+                                    L.ptr(dist), L.ptr(wit), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
+            "cloud_hausdorff")
+    return dist, wit
+
+
 # ---- eval-image metrics ------------------------------------------------------------------------------
 
 

@@ -275,6 +275,12 @@ SIGNATURES = {
     "fnr_cloud_statistical_outlier": (_i, [_vp, _i64, P(C.c_double), P(C.c_double), C.c_int32, C.c_double, _vp, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
     "fnr_cloud_estimate_normals": (_i, [_vp, _i64, P(C.c_double), P(C.c_double), C.c_int32, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_cloud_icp_workspace_bytes": (C.c_size_t, [_i64]),
+    "fnr_cloud_icp": (_i, [_vp, _i64, P(C.c_int64), _i64, _vp, _i64, P(C.c_int64), _i64, P(C.c_int32), _vp, C.c_double,
+                           C.c_int32, C.c_int32, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_cloud_hausdorff_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "fnr_cloud_hausdorff": (_i, [_vp, _i64, P(C.c_int64), _i64, _vp, _i64, P(C.c_int64), _i64, _i64, P(C.c_int32),
+                                 P(C.c_int32), _vp, _i64, P(C.c_int64), _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 FNR_CLOUD_KNN_MAX = 32

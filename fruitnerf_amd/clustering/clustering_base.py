@@ -12,7 +12,7 @@ on the GPU, with the two Open3D methods the reference calls, same argument names
 from __future__ import annotations
 
 from pathlib import Path
-from typing import List, Optional, Tuple, Union
+from typing import List, Literal, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -101,7 +101,11 @@ def dbscan_labels(points: torch.Tensor, eps: float, min_samples: int) -> torch.T
 
 class FruitClustering:
     def __init__(self, voxel_size_down_sample: float = 0.00005, remove_outliers_nb_points: int = 100,
-                 remove_outliers_radius: float = 0.01, cluster_merge_distance: float = 0.04):
+                 remove_outliers_radius: float = 0.01, cluster_merge_distance: float = 0.04,
+                 second_stage: Literal["host", "device"] = "host"):
+        if second_stage not in ("host", "device"):
+            raise ValueError(f"second_stage is 'host' or 'device', not {second_stage!r}")
+        self.second_stage = second_stage
         self.voxel_size_down_sample = voxel_size_down_sample
         self.remove_outliers_nb_points = remove_outliers_nb_points
         self.remove_outliers_radius = remove_outliers_radius
@@ -172,6 +176,8 @@ class FruitClustering:
     icp_max_iteration: int = 2000
     surface_samples: int = 1000
     max_fruits_per_cluster: int = 6
+    # where the fits run: "host" (shapes.py, the reference's own arrangement) or "device" (fit_fruits_batch)
+    second_stage: str = "host"
 
     def set_template(self, template_points: np.ndarray) -> None:
         """The fruit template (centred at the origin) and its alpha shape, whose volume is the unit of the size test
@@ -198,6 +204,56 @@ class FruitClustering:
         best = int(np.argmin(dists))
         return best + 1, hypotheses[best], dists
 
+    def fit_fruits_batch(self, surfaces: List[np.ndarray], device: Union[str, torch.device] = "cuda"
+                         ) -> List[Tuple[int, List[np.ndarray], List[float]]]:
+        """fit_fruits for every surface of a cloud at once, the fits and their scores on the device: the host builds one
+        Ward tree per surface and the k = 2 .. max part centres from its cuts; ONE cloud_icp call registers the shared
+        template to all surfaces, ONE cloud_hausdorff call scores surfaces x hypotheses (the placed templates are formed
+        in the kernel from the ICP transforms and the centres), one copy brings distances and transforms back; the
+        argmin (first on ties) and the winner's template points are the host's.  No surface: nothing is launched."""
+        if not surfaces:
+            return []
+        dev = torch.device(device)
+        H = self.max_fruits_per_cluster
+        centres: List[List[np.ndarray]] = []                         # per surface: hypotheses 2 .. H
+        for surface in surfaces:
+            tree = shapes.ward_tree(surface)
+            per_k = []
+            for k in range(2, H + 1):
+                parts = shapes.ward_cut(tree, k)
+                per_k.append(np.stack([surface[parts == part].mean(axis=0) for part in np.unique(parts)]))
+            centres.append(per_k)
+        offsets = np.concatenate([[0], np.cumsum([s.shape[0] for s in surfaces])])
+        tgt = torch.as_tensor(np.ascontiguousarray(np.vstack(surfaces), dtype=np.float64), device=dev)
+        template = torch.as_tensor(np.ascontiguousarray(self.fruit_template), device=dev)
+        n = len(surfaces)
+        init = np.tile(np.eye(4), (n, 1, 1))
+        init[:, :3, 3] = np.stack([s.mean(axis=0) for s in surfaces])
+        T, *_ = K.cloud_icp(tgt, offsets, template, [0, template.shape[0]], [0] * n, torch.as_tensor(init, device=dev),
+                            self.icp_max_correspondence_distance, with_scaling=True,
+                            max_iteration=self.icp_max_iteration)
+        trans_offsets = [0]
+        for per_k in centres:
+            trans_offsets.append(trans_offsets[-1])                  # hypothesis 1: the ICP transform
+            for c in per_k:
+                trans_offsets.append(trans_offsets[-1] + c.shape[0])
+        translations = torch.as_tensor(np.vstack([c for per_k in centres for c in per_k]), device=dev)
+        transforms = torch.zeros(n * H, 4, 4, dtype=torch.float64, device=dev)
+        transforms[0::H] = T
+        dist, _ = K.cloud_hausdorff(tgt, offsets, [i for i in range(n) for _ in range(H)], template,
+                                    [0, template.shape[0]], [0] * (n * H), translations, trans_offsets, transforms)
+        back = torch.cat([dist[:, 2].reshape(-1), T.reshape(-1)]).cpu().numpy()
+        dists, T_host = back[:n * H].reshape(n, H), back[n * H:].reshape(n, 4, 4)
+        out = []
+        for i in range(n):
+            best = int(np.argmin(dists[i]))
+            if best == 0:
+                fits = [shapes.transform_points(T_host[i], self.fruit_template)]
+            else:
+                fits = [self.fruit_template + c for c in centres[i][best - 1]]
+            out.append((best + 1, fits, [float(d) for d in dists[i]]))
+        return out
+
     def split_large_cluster(self, X: List[np.ndarray], C, labels, seed: int = 0) -> int:
         """The second counting stage on merge_small_clusters' clusters: a cluster whose alpha-shape volume exceeds the
         template's by more than 1 / 0.9 holds several fruits — fit_fruits says how many; one below 0.3 template volumes is
@@ -205,6 +261,8 @@ class FruitClustering:
         seed: of the surface sampling (Open3D draws from a clock-seeded generator there; cluster i uses seed + i)."""
         if getattr(self, "fruit_template", None) is None:
             raise RuntimeError("split_large_cluster needs a fruit template: set_template(points) / Clustering(...)")
+        if self.second_stage == "device":
+            return self._split_large_cluster_device(X, seed)
         unit = self.fruit_alpha_shape_.volume
         self.additional_count = self.prune_counter = 0
         self.valid_clusters: List[np.ndarray] = []
@@ -225,6 +283,41 @@ class FruitClustering:
             else:
                 self.valid_clusters.append(cluster)
             self.cluster_decisions.append(record)
+        return self._finish_split()
+
+    def _split_large_cluster_device(self, X: List[np.ndarray], seed: int) -> int:
+        """split_large_cluster in two phases: the volumes, the prune / keep / split decisions and the surfaces (same
+        seed + i) on the host as above, then fit_fruits_batch for all split clusters at once, then the same bookkeeping in
+        cluster order."""
+        unit = self.fruit_alpha_shape_.volume
+        self.additional_count = self.prune_counter = 0
+        self.cluster_decisions: List[dict] = []
+        kept: List[Optional[List[np.ndarray]]] = []                  # per cluster: its valid_clusters entries
+        split, surfaces = [], []
+        for i, cluster in enumerate(X):
+            volume = shapes.alpha_shape(cluster, self.alpha_volume).volume
+            record = {"points": int(cluster.shape[0]), "volume": volume, "fruits": 1}
+            if unit < 0.9 * volume:
+                surfaces.append(shapes.alpha_shape(cluster, self.alpha_surface).sample_points_uniformly(
+                    self.surface_samples, seed=seed + i))
+                split.append(i)
+                kept.append(None)
+            elif 0.3 * unit > abs(volume):
+                self.prune_counter += 1
+                record["fruits"] = 0
+                kept.append([])
+            else:
+                kept.append([cluster])
+            self.cluster_decisions.append(record)
+        device = self.pcd.points.device if getattr(self, "pcd", None) is not None else "cuda"
+        for i, (fruits, fits, dists) in zip(split, self.fit_fruits_batch(surfaces, device)):
+            self.additional_count += fruits - 1
+            kept[i] = fits
+            self.cluster_decisions[i].update(fruits=fruits, distances=dists)
+        self.valid_clusters: List[np.ndarray] = [c for entries in kept for c in entries]
+        return self._finish_split()
+
+    def _finish_split(self) -> int:
         self.cluster_centers = [c.mean(axis=0) for c in self.valid_clusters]
         count = self.counter - self.fuse_counter + self.additional_count - self.prune_counter
         gt = getattr(self, "gt_cluster_center", None)
@@ -257,9 +350,15 @@ class FruitClustering:
         self.recall = tp / (tp + fn) if tp + fn else 0.0
         self.F1 = 2 * self.precision * self.recall / (self.precision + self.recall) if self.precision + self.recall else 0.0
 
-    def count(self, pcd: Union[str, PointCloud], eps: float = 0.01, seed: int = 0) -> int:
-        """cluster -> merge_small_clusters -> split_large_cluster (:513-538); 0 for a missing file or an empty cloud."""
+    def count(self, pcd: Union[str, PointCloud], eps: float = 0.01, seed: int = 0,
+              second_stage: Optional[Literal["host", "device"]] = None) -> int:
+        """cluster -> merge_small_clusters -> split_large_cluster (:513-538); 0 for a missing file or an empty cloud.
+        second_stage: where the template fits of split_large_cluster run from now on (None: as constructed)."""
         import os
+        if second_stage is not None:
+            if second_stage not in ("host", "device"):
+                raise ValueError(f"second_stage is 'host' or 'device', not {second_stage!r}")
+            self.second_stage = second_stage
         if isinstance(pcd, str):
             if not os.path.exists(pcd):
                 self.real_count = 0
@@ -295,10 +394,12 @@ class Clustering(FruitClustering):
     def __init__(self, template_path: Union[str, Path, None] = None, voxel_size_down_sample: float = 0.00005,
                  remove_outliers_nb_points: int = 800, remove_outliers_radius: float = 0.02, min_samples: int = 60,
                  apple_template_size: float = 0.8, cluster_merge_distance: float = 0.04, gt_cluster=None,
-                 gt_count: Optional[int] = None, template_radius: float = 0.1):
+                 gt_count: Optional[int] = None, template_radius: float = 0.1,
+                 second_stage: Literal["host", "device"] = "host"):
         super().__init__(voxel_size_down_sample=voxel_size_down_sample,
                          remove_outliers_nb_points=remove_outliers_nb_points,
-                         remove_outliers_radius=remove_outliers_radius, cluster_merge_distance=cluster_merge_distance)
+                         remove_outliers_radius=remove_outliers_radius, cluster_merge_distance=cluster_merge_distance,
+                         second_stage=second_stage)
         self.template_path = template_path
         self.min_samples = min_samples
         # The sphere stands in ONLY for "no template given" and for a Git-LFS pointer file (what the reference's

@@ -192,6 +192,18 @@ def ward_labels(points: np.ndarray, n_clusters: int) -> np.ndarray:
     return hierarchy.fcluster(hierarchy.ward(points), n_clusters, criterion="maxclust") - 1
 
 
+def ward_tree(points: np.ndarray) -> np.ndarray:
+    """The Ward linkage ward_labels cuts, built once: fit_fruits asks for its k = 2 .. 6 cuts of one surface."""
+    from scipy.cluster import hierarchy
+    return hierarchy.ward(points)
+
+
+def ward_cut(tree: np.ndarray, n_clusters: int) -> np.ndarray:
+    """ward_labels(points, n_clusters) from ward_tree(points)."""
+    from scipy.cluster import hierarchy
+    return hierarchy.fcluster(tree, min(n_clusters, tree.shape[0] + 1), criterion="maxclust") - 1
+
+
 def sphere_template(radius: float, n_points: int = 2000) -> np.ndarray:
     """A fruit template when the reference's template meshes are not available (its *_template.ply files are Git-LFS
     pointers): n points on a sphere, Fibonacci lattice (deterministic, near-uniform), centred at the origin."""

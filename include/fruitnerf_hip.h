@@ -966,6 +966,46 @@ int fnr_cloud_statistical_outlier(const double* xyz, int64_t n, const double* lo
 int fnr_cloud_estimate_normals(const double* xyz, int64_t n, const double* lo, const double* hi, int32_t knn,
                                double* normals, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- second counting stage: batched template fits ---------------------------------------------- */
+/* split_large_cluster (clustering/clustering_base.py:260-511) registers the fruit template to every large cluster's
+ * surface with Open3D's ICP and scores six hypotheses by their Hausdorff distance.  These entry points run both for all
+ * clusters of a cloud at once (csrc/cloud_fit.hip); fp64, every reduction in a fixed order, so a problem's result does
+ * not depend on what else is in the batch.  Point sets are [n][3] float64 DEVICE arrays of concatenated segments; the
+ * *_offsets (one more entry than segments, starting at 0, ending at the point count) and the *_id arrays are HOST
+ * arrays, checked before anything is launched.  n_problems == 0 launches nothing. */
+size_t fnr_cloud_icp_workspace_bytes(int64_t n_problems);
+/* registration_icp(source, target, max_correspondence_distance, init, TransformationEstimationPointToPoint(
+ * with_scaling), ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)) (:262-279), Open3D's loop:
+ * evaluate; then per iteration Umeyama on the current pairs, T = update * T, re-evaluate; stop when |d fitness| and
+ * |d inlier_rmse| are both below the criteria, when fewer than 3 pairs remain, or at max_iteration.  The whole loop runs
+ * on the device.  Problem b registers source segment src_id[b] (shared, never replicated) onto target segment b.
+ * A pair needs distance < max_correspondence_distance (STRICT <); the nearest target is exact, ties go to the lowest
+ * target index.  init / transformation: [n_problems][16] row-major 4 x 4; fitness, inlier_rmse: [n_problems];
+ * iterations: [n_problems] = the count Open3D's loop variable ends at (the iteration that found < 3 pairs included);
+ * correspondences: for problem b, one int32 per point of its source segment (target index within segment b, -1 = none),
+ * problems concatenated in order.  An empty target gives fitness 0 and transformation = init. */
+int fnr_cloud_icp(const double* tgt_xyz, int64_t n_tgt_points, const int64_t* tgt_offsets, int64_t n_problems,
+                  const double* src_xyz, int64_t n_src_points, const int64_t* src_offsets, int64_t n_sources,
+                  const int32_t* src_id, const double* init, double max_correspondence_distance, int32_t with_scaling,
+                  int32_t max_iteration, double relative_fitness, double relative_rmse, double* transformation,
+                  double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* correspondences, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* n_queries: sum over the problems of |A_b| + |B_b|. */
+size_t fnr_cloud_hausdorff_workspace_bytes(int64_t n_problems, int64_t n_queries);
+/* hausdorff_distance(A_b, B_b, distance="euclidean") (:277, :315).  A_b = segment a_id[b] of a_xyz.  B_b is never stored:
+ * it is source segment src_id[b] placed k times, point j = p * n_src + i being src[i] + translations[trans_offsets[b] +
+ * p] (k = trans_offsets[b+1] - trans_offsets[b] > 0; translations: device [n_translations][3]), or, for a problem
+ * without translations, src[i] under transforms[b] (device [n_problems][16] row-major 4 x 4; nullable when every problem
+ * has translations; trans_offsets nullable when none has).  distances [n_problems][3] = max_a min_b |a - b|,
+ * max_b min_a |a - b|, the larger of the two; witnesses [n_problems][2] = the a whose nearest b is farthest, the b
+ * (index into the placed set) whose nearest a is farthest, the lowest index on ties.  The search is exact.  A problem
+ * with an empty set gives NaN / -1. */
+int fnr_cloud_hausdorff(const double* a_xyz, int64_t n_a_points, const int64_t* a_offsets, int64_t n_a_sets,
+                        const double* src_xyz, int64_t n_src_points, const int64_t* src_offsets, int64_t n_sources,
+                        int64_t n_problems, const int32_t* a_id, const int32_t* src_id, const double* translations,
+                        int64_t n_translations, const int64_t* trans_offsets, const double* transforms,
+                        double* distances, int32_t* witnesses, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- eval-image metrics ------------------------------------------------------------------------ */
 /* FruitModel.get_image_metrics_and_images (fruit_nerf/fruit_nerf.py:403-458) on the device: everything the reference
  * computes with torchmetrics on a rendered [H, W, 3] image, as raw sums (the host forms the four ratios):
