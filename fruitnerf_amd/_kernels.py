@@ -552,6 +552,70 @@ def depth_points(origins: Tensor, directions: Tensor, depth: Tensor, rgb: Tensor
                                          L.stream_ptr(dev)), "depth_points_normals")
 
 
+class TsdfVolumeArg:
+    """fnr_tsdf_volume view of a TSDF volume's tensors: values / weights [nx,ny,nz], colors [nx,ny,nz,3], float32 and
+    contiguous on the HIP device (kept alive here); lo / hi: 3 floats each."""
+
+    def __init__(self, values: Tensor, weights: Tensor, colors: Tensor, lo, hi, truncation_margin: float,
+                 max_weight: float):
+        L.require_gpu_tensor(values, "TSDF values")
+        if values.dim() != 3 or weights.shape != values.shape or colors.shape != values.shape + (3,):
+            raise ValueError(f"TSDF arrays: values {tuple(values.shape)}, weights {tuple(weights.shape)}, colors "
+                             f"{tuple(colors.shape)}; expected [nx,ny,nz], [nx,ny,nz], [nx,ny,nz,3]")
+        for t in (values, weights, colors):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != values.device:
+                raise ValueError("TSDF arrays must be contiguous float32 tensors on one device")
+        self.tensors = (values, weights, colors)
+        self.device = values.device
+        self.n_nodes = values.numel()
+        c = L.fnr_tsdf_volume()
+        c.dims[:] = list(values.shape)
+        c.lo[:] = [float(v) for v in lo]
+        c.hi[:] = [float(v) for v in hi]
+        c.truncation_margin, c.max_weight = float(truncation_margin), float(max_weight)
+        c.values, c.weights, c.colors = values.data_ptr(), weights.data_ptr(), colors.data_ptr()
+        self.c = c
+        self.ref = C.byref(c)
+
+
+def tsdf_integrate(vol: TsdfVolumeArg, c2w: Tensor, intrinsics: Tensor, depth: Tensor, rgb: Tensor,
+                   mask: Optional[Tensor] = None, depth_kind: int = L.FNR_TSDF_DEPTH_RAY) -> None:
+    """Fuses cameras c2w [n,3,4] / intrinsics [n,4] (fx, fy, cx, cy) with depth [n,H,W], rgb [n,H,W,3] and the optional
+    mask [n,H,W] (bool / uint8, 0 = ignore the pixel) into the volume, in the order given (fnr_tsdf_integrate)."""
+    n = c2w.shape[0]
+    if c2w.shape != (n, 3, 4) or intrinsics.shape != (n, 4) or depth.dim() != 3 or depth.shape[0] != n \
+            or rgb.shape != depth.shape + (3,) or (mask is not None and mask.shape != depth.shape):
+        raise ValueError(f"tsdf_integrate: c2w {tuple(c2w.shape)}, intrinsics {tuple(intrinsics.shape)}, depth "
+                         f"{tuple(depth.shape)}, rgb {tuple(rgb.shape)}"
+                         + ("" if mask is None else f", mask {tuple(mask.shape)}"))
+    if n == 0:
+        return
+    dev = vol.device
+    c2w, intrinsics, depth, rgb = [_f32c(t).to(dev) for t in (c2w, intrinsics, depth, rgb)]
+    m = None if mask is None else (mask != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    L.check(L.load().fnr_tsdf_integrate(vol.ref, n, L.ptr(c2w), L.ptr(intrinsics), depth.shape[1], depth.shape[2],
+                                        L.ptr(depth), L.ptr(rgb), L.ptr(m), int(depth_kind), L.stream_ptr(dev)),
+            "tsdf_integrate")
+
+
+def tsdf_mesh(vol: TsdfVolumeArg):
+    """Marching tetrahedra over the volume (fnr_tsdf_mesh_count, one host read of the two counts, fnr_tsdf_mesh_emit).
+    -> vertices [V,3], faces [F,3] int32, normals [V,3], colors [V,3] on the device; their order is fixed by the volume."""
+    lib = L.load()
+    dev = vol.device
+    nbytes = L.tsdf_mesh_workspace_bytes(vol.n_nodes)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    L.check(lib.fnr_tsdf_mesh_count(vol.ref, L.ptr(counts), L.ptr(ws), ws.numel() * 8, L.stream_ptr(dev)),
+            "tsdf_mesh_count")
+    n_vertices, n_faces = counts.tolist()
+    vertices, normals, colors = (torch.empty(n_vertices, 3, device=dev) for _ in range(3))
+    faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
+    L.check(lib.fnr_tsdf_mesh_emit(vol.ref, L.ptr(ws), ws.numel() * 8, n_vertices, n_faces, L.ptr(vertices),
+                                   L.ptr(normals), L.ptr(colors), L.ptr(faces), L.stream_ptr(dev)), "tsdf_mesh_emit")
+    return vertices, faces, normals, colors
+
+
 # ---- training ---------------------------------------------------------------------------------------
 
 

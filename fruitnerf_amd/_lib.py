@@ -111,6 +111,19 @@ class fnr_lattice(C.Structure):
                 ("xs", C.c_void_p), ("ys", C.c_void_p), ("zs", C.c_void_p)]
 
 
+class fnr_tsdf_volume(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("truncation_margin", C.c_float),
+                ("max_weight", C.c_float), ("values", C.c_void_p), ("weights", C.c_void_p), ("colors", C.c_void_p)]
+
+
+FNR_TSDF_DEPTH_Z, FNR_TSDF_DEPTH_RAY = 0, 1
+
+
+def tsdf_mesh_workspace_bytes(n_nodes: int) -> int:
+    """FNR_TSDF_MESH_WORKSPACE_BYTES of include/fruitnerf_hip.h."""
+    return 4 * n_nodes + 16 * ((n_nodes + 255) // 256) + 16
+
+
 class fnr_image_set(C.Structure):
     _fields_ = [("n_images", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("images", C.c_void_p),
                 ("masks", C.c_void_p), ("c2w", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float),
@@ -268,6 +281,10 @@ SIGNATURES = {
     "fnr_depth_points": (_i, [_vp, _vp, _vp, _vp, _i64, P(C.c_float), P(C.c_float), _vp, _vp, _i64, _vp, _vp, _vp]),
     "fnr_depth_points_normals": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, P(C.c_float), P(C.c_float), _vp, _vp, _vp, _i64, _vp,
                                       _vp, _vp]),
+    "fnr_tsdf_integrate": (_i, [P(fnr_tsdf_volume), C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32,
+                                _vp]),
+    "fnr_tsdf_mesh_count": (_i, [P(fnr_tsdf_volume), _vp, _vp, C.c_size_t, _vp]),
+    "fnr_tsdf_mesh_emit": (_i, [P(fnr_tsdf_volume), _vp, C.c_size_t, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "fnr_field_normals": (_i, [P(fnr_field_net), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fnr_render_normals": (_i, [_i64, _i, _vp, _vp, _i, _vp, _vp]),
     "fnr_cloud_knn_workspace_bytes": (C.c_size_t, [_i64, C.c_int32]),

@@ -12,6 +12,7 @@ equirectangular ones raise.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple, Union
 
 import torch
@@ -75,6 +76,18 @@ class Cameras:
 
     def __len__(self) -> int:
         return self.camera_to_worlds.shape[0]
+
+    def rescale_output_resolution(self, scale: float) -> None:
+        """Nerfstudio's Cameras.rescale_output_resolution, in place: fx, fy, cx, cy are multiplied by `scale` and the
+        image becomes floor(height * scale) x floor(width * scale)."""
+        scale = float(scale)
+        if not scale > 0.0:
+            raise ValueError(f"rescale_output_resolution: scale {scale} must be positive")
+        height, width = math.floor(self.height * scale), math.floor(self.width * scale)
+        if height < 1 or width < 1:
+            raise ValueError(f"rescale_output_resolution: scale {scale} leaves a {height} x {width} image")
+        self.fx, self.fy, self.cx, self.cy = self.fx * scale, self.fy * scale, self.cx * scale, self.cy * scale
+        self.height, self.width = height, width
 
     def camera_table(self, device):
         return camera_table_of(self, device)

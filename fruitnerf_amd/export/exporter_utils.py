@@ -226,6 +226,59 @@ def generate_point_cloud(pipeline, num_points: int = 1_000_000, remove_outliers:
     return pcd
 
 
+def export_tsdf_mesh(pipeline, output_dir, downscale_factor: int = 2, depth_output_name: str = "depth",
+                     rgb_output_name: str = "rgb", resolution=128, batch_size: int = 10, use_bounding_box: bool = True,
+                     bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
+                     semantic_threshold: Optional[float] = None):
+    """Nerfstudio's ExportTSDFMesh.main / export_tsdf_mesh (`ns-export tsdf`; its fields as recalled): every camera of
+    `pipeline.datamanager.train_dataset.cameras` is rendered at 1 / downscale_factor of its resolution (pinhole: the
+    fusion does not model distortion, so the rays are generated without it), its `depth_output_name` / `rgb_output_name`
+    images are fused into a TSDF volume of `resolution` (an int or three) nodes over the bounding box — without
+    `use_bounding_box`, over `train_dataset.scene_box.aabb` — `batch_size` cameras per launch, and the marching-
+    tetrahedra mesh is written to <output_dir>/tsdf_mesh.ply (ply.write_triangle_mesh).  -> the TSDF.
+
+    semantic_threshold (this project's addition): pixels whose sigmoid(outputs["semantics"]) is below it are left out
+    of the fusion, so the mesh is the fruit alone — what the counting stage looks at.  A missing output is a KeyError."""
+    from ..cameras.cameras import Cameras, _column, _image_size, generate_rays_of
+    from .tsdf import TSDF
+    if int(downscale_factor) < 1 or int(batch_size) < 1:
+        raise ValueError("export_tsdf_mesh: downscale_factor and batch_size must be at least 1")
+    model = pipeline.model
+    dev = model.device
+    dataset = pipeline.datamanager.train_dataset
+    src = dataset.cameras
+    n = src.camera_to_worlds.shape[0]
+    height, width = _image_size(src)
+    cameras = Cameras(src.camera_to_worlds.to(dev), *[_column(getattr(src, k), n, k).to(dev) for k in ("fx", "fy", "cx", "cy")],
+                      width=width, height=height, camera_type=getattr(src, "camera_type", None))
+    cameras.rescale_output_resolution(1.0 / int(downscale_factor))
+    if use_bounding_box:
+        aabb = torch.tensor([list(bounding_box_min), list(bounding_box_max)], dtype=torch.float32)
+    else:
+        aabb = torch.as_tensor(dataset.scene_box.aabb, dtype=torch.float32).cpu()
+    tsdf = TSDF.from_aabb(aabb, resolution, dev)
+    intrinsics = torch.cat([cameras.fx, cameras.fy, cameras.cx, cameras.cy], dim=1)
+    names = [depth_output_name, rgb_output_name] + ([] if semantic_threshold is None else ["semantics"])
+    for begin in range(0, n, int(batch_size)):
+        batch = range(begin, min(begin + int(batch_size), n))
+        images = {name: [] for name in names}
+        for i in batch:
+            outputs = model.get_outputs_for_camera_ray_bundle(generate_rays_of(cameras, i))
+            for name in names:
+                if name not in outputs:
+                    raise KeyError(f"Could not find {name} in the model outputs; choose from {list(outputs.keys())}")
+                images[name].append(outputs[name].to(dev))
+        mask = None
+        if semantic_threshold is not None:
+            mask = torch.sigmoid(torch.stack(images["semantics"])[..., 0]) >= float(semantic_threshold)
+        tsdf.integrate(cameras.camera_to_worlds[batch.start:batch.stop], intrinsics[batch.start:batch.stop],
+                       torch.stack(images[depth_output_name])[..., 0], torch.stack(images[rgb_output_name]), mask)
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    tsdf.export(str(out / "tsdf_mesh.ply"))
+    return tsdf
+
+
 def export_point_cloud(pipeline, output_dir, **kwargs):
     """ExportPointCloud.main: generate_point_cloud(pipeline, **kwargs) written to <output_dir>/point_cloud.ply (binary
     PLY in Open3D's layout, colours quantised to uchar, normals when they were estimated).  -> the PointCloud."""

@@ -28,7 +28,8 @@ extern "C" {
 #endif
 
 /* 13 also covers the per-image camera table (fnr_camera_table, the fnr_*_cams entry points and fnr_camera_rays): pure
- * additions — no existing symbol or struct changed, so a caller built against the earlier 13 runs unchanged. */
+ * additions — no existing symbol or struct changed, so a caller built against the earlier 13 runs unchanged.  The TSDF
+ * mesh export (fnr_tsdf_volume, the three fnr_tsdf_* entry points) is an addition of the same kind. */
 #define FNR_ABI_VERSION 13
 #define FNR_MAX_LEVELS 16
 #define FNR_MAX_SEM_LAYERS 4
@@ -914,6 +915,71 @@ int fnr_depth_points_normals(const float* origins, const float* directions, cons
                              const float* normals, int64_t n_rays, const float* box_min, const float* box_max,
                              float* points, float* colors, float* normals_out, int64_t capacity, uint64_t* count,
                              void* workspace, void* stream);
+
+/* ---- TSDF mesh export: depth fusion + marching tetrahedra (csrc/tsdf.hip) ----------------------- */
+/* What Nerfstudio's `ns-export tsdf` computes (exporter/tsdf_utils.py, as recalled — Nerfstudio is not available to this
+ * project, so THIS text is the contract; tests/tsdf_reference.py restates it in float64).  Pure additions to ABI 13.
+ *
+ * Volume.  dims = (nx, ny, nz) NODES over the axis-aligned box [lo, hi]; voxel_size = (hi - lo) / dims per axis (fp32);
+ * node (i, j, k) sits at lo + (i, j, k) * voxel_size and has the linear index (i * ny + j) * nz + k (z fastest).
+ * values / weights: [nx][ny][nz], colors: [nx][ny][nz][3], fp32; the caller initialises values = -1, weights = 0,
+ * colors = 0.  truncation = truncation_margin * voxel_size.x (Nerfstudio's margin: 5).  2 <= every dim <= 2048. */
+typedef struct fnr_tsdf_volume {
+  int32_t dims[3];
+  float lo[3];
+  float hi[3];
+  float truncation_margin;
+  float max_weight; /* >= 1.  1: Nerfstudio's clamp (the last valid camera wins); large: the plain running average */
+  float* values;
+  float* weights;
+  float* colors;
+} fnr_tsdf_volume;
+#define FNR_TSDF_DEPTH_Z 0   /* depth images hold z, the distance along the optical axis (what Nerfstudio compares) */
+#define FNR_TSDF_DEPTH_RAY 1 /* depth images hold the distance along the pixel's ray (this model's "depth" output) */
+/* Fuses n_cameras pinhole cameras, in the order given, into the volume.  c2w: [n][3][4] camera-to-world rows (R | t),
+ * intrinsics: [n][4] = fx, fy, cx, cy, depth: [n][H][W], rgb: [n][H][W][3], mask: [n][H][W] bytes or NULL (all valid);
+ * all DEVICE arrays.  For node p and camera c, every operation in fp32:
+ *   q = R^T (p - t)  (Nerfstudio's camera frame: x right, y up, -z forward),  z = -q.z;
+ *   u = fx * q.x / z + cx,  v = fy * (-q.y) / z + cy   (pinhole; distortion is not modelled);
+ *   col = rint(u - 0.5), row = rint(v - 0.5), ties to even (grid_sample(mode="nearest", align_corners=False));
+ *   a pixel outside the image or with mask byte 0 reads depth 0;
+ *   voxel_depth = z (FNR_TSDF_DEPTH_Z) or |q| (FNR_TSDF_DEPTH_RAY);  dist = sampled depth - voxel_depth;
+ *   the sample is valid iff z > 0 && sampled depth > 0 && dist > -truncation; for a valid sample
+ *     s = clamp(dist / truncation, -1, 1),  value = (value * w + s) / (w + 1), each colour channel likewise with the
+ *     sampled rgb,  w = min(w + 1, max_weight).
+ * One thread per node; the camera loop runs inside the kernel, so a node's five floats are read and written once per call
+ * and the result is bit-identical however the cameras are split into calls.  n_cameras == 0 launches nothing. */
+int fnr_tsdf_integrate(const fnr_tsdf_volume* volume, int32_t n_cameras, const float* c2w, const float* intrinsics,
+                       int32_t H, int32_t W, const float* depth, const float* rgb, const uint8_t* mask,
+                       int32_t depth_kind, void* stream);
+/* Surface extraction: marching tetrahedra on the cells of the node grid.  A node is inside iff value < 0 (unobserved
+ * nodes, -1, are inside).  Cell (i, j, k) has the corners (i + dx, j + dy, k + dz), corner id = dx + 2 dy + 4 dz, and is
+ * split into six tetrahedra around its main diagonal: tetrahedron t walks from corner 0 to corner 7 along the axes in the
+ * order t = 0: x y z, 1: x z y, 2: y x z, 3: y z x, 4: z x y, 5: z y x, its corners c0..c3 being the four corners on that
+ * walk.  The same split in every cell, so faces match across cells.
+ *   Edges.  Every tetrahedron edge runs from a node a to the node b = a + (dx, dy, dz) with direction code
+ * m = dx + 2 dy + 4 dz in 1..7 (three axes, three face diagonals, the body diagonal); its key is 8 * index(a) + m.  It is
+ * active iff its endpoints differ in side, and carries one vertex, shared by every cell around it:
+ *   t = (0 - v_a) / (v_b - v_a);  position = p_a + t * (p_b - p_a), from a, the endpoint with the smaller index;
+ *   colour = colour of the nearer endpoint: of a iff |v_a| <= |v_b| (a tie goes to the smaller index);
+ *   normal = normalise(g_a + t * (g_b - g_a)), g = the central-difference gradient of values in world units (one-sided
+ *   at the border); a zero vector stays zero.
+ *   Faces.  With the inside corners i0 < i1 .. and the outside corners o0 < o1 .. of a tetrahedron (positions on its walk):
+ *   one inside: (i0 o0, i0 o1, i0 o2); three inside: (o0 i0, o0 i1, o0 i2); two inside: the quad (i0 o0, i0 o1, i1 o1,
+ *   i1 o0) as the triangles (A, B, C), (A, C, D); each triangle then wound so that its normal points towards the outside
+ *   (positive values).  The 16-case table is derived at compile time from these rules (csrc/tsdf.hip).
+ *   Order.  Vertices ascend by edge key; faces ascend by (cell index = index of its corner 0, t, triangle).  Both come
+ * from exclusive scans: the arrays are a function of the volume alone, whatever the launch geometry.
+ * fnr_tsdf_mesh_count writes counts[2] (DEVICE uint64) = number of vertices, number of faces, and leaves the scan
+ * results in `workspace` (>= FNR_TSDF_MESH_WORKSPACE_BYTES(nx * ny * nz) bytes, 8-byte aligned).  The caller reads the
+ * counts (a synchronisation), allocates, and calls fnr_tsdf_mesh_emit with the SAME workspace and the unchanged volume:
+ * vertices / normals / colors [n_vertices][3] fp32 (world units), faces [n_faces][3] int32; entries beyond n_vertices /
+ * n_faces are not written.  More than 2^31 - 1 vertices cannot be indexed and are refused. */
+#define FNR_TSDF_MESH_WORKSPACE_BYTES(n_nodes) (4 * (size_t)(n_nodes) + 16 * (((size_t)(n_nodes) + 255) / 256) + 16)
+int fnr_tsdf_mesh_count(const fnr_tsdf_volume* volume, uint64_t* counts, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int fnr_tsdf_mesh_emit(const fnr_tsdf_volume* volume, const void* workspace, size_t workspace_bytes, int64_t n_vertices,
+                       int64_t n_faces, float* vertices, float* normals, float* colors, int32_t* faces, void* stream);
 
 /* ---- point-cloud front-end of the counting stage ---------------------------------------------- */
 /* FruitClustering.cluster (clustering/clustering_base.py:183-207) runs, on the exported cloud, Open3D's
