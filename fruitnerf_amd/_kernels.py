@@ -806,34 +806,24 @@ def field_mlp_bwd(net: L.fnr_field_net, grads: L.fnr_field_net, rays: RaysArg, S
     d_feats = _empty(*feats.shape, device=dev)
     nbytes = lib.fnr_field_mlp_bwd_workspace_bytes(rays.n, S)
     ws = _empty(nbytes, dtype=torch.uint8, device=dev)
+    d_pos = _empty(N, 4, device=dev) if jacobian is not None else None
+    adam, grad_arena = weight_adam if weight_adam is not None else (None, None)
+    # every export takes the same arguments, in this order; `position` and `optimiser` only where its form has them
+    common = (C.byref(net), C.byref(grads), rays.ref, S, L.ptr(feats), L.ptr(h_saved), L.ptr(ray_bias), L.ptr(packed),
+              L.ptr(selector), L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.ptr(d_feats))
+    position = (L.ptr(jacobian), L.ptr(d_pos))
+    optimiser = (None if adam is None else C.byref(adam), L.ptr(grad_arena))
+    workspace = (L.ptr(ws), nbytes, L.stream_ptr(dev))
     if semgrad:
-        adam, grad_arena = weight_adam if weight_adam is not None else (None, None)
-        d_pos = _empty(N, 4, device=dev) if jacobian is not None else None
-        L.check(lib.fnr_field_mlp_bwd_semgrad(C.byref(net), C.byref(grads), rays.ref, S, L.ptr(feats), L.ptr(h_saved),
-                                              L.ptr(ray_bias), L.ptr(packed), L.ptr(selector), L.ptr(d_density),
-                                              L.ptr(d_rgb), L.ptr(d_logit), L.ptr(d_feats), L.ptr(jacobian), L.ptr(d_pos),
-                                              None if adam is None else C.byref(adam), L.ptr(grad_arena), L.ptr(ws), nbytes,
-                                              L.stream_ptr(dev)), "field_mlp_bwd_semgrad")
-        return (d_feats, d_pos) if jacobian is not None else d_feats
-    if weight_adam is not None:
-        adam, grad_arena = weight_adam
-        d_pos = _empty(N, 4, device=dev) if jacobian is not None else None
-        L.check(lib.fnr_field_mlp_bwd_adam(C.byref(net), C.byref(grads), rays.ref, S, L.ptr(feats), L.ptr(h_saved),
-                                           L.ptr(ray_bias), L.ptr(packed), L.ptr(selector), L.ptr(d_density), L.ptr(d_rgb),
-                                           L.ptr(d_logit), L.ptr(d_feats), L.ptr(jacobian), L.ptr(d_pos), C.byref(adam),
-                                           L.ptr(grad_arena), L.ptr(ws), nbytes, L.stream_ptr(dev)), "field_mlp_bwd_adam")
-        return (d_feats, d_pos) if jacobian is not None else d_feats
-    if jacobian is not None:
-        d_pos = _empty(N, 4, device=dev)
-        L.check(lib.fnr_field_mlp_bwd_rays(C.byref(net), C.byref(grads), rays.ref, S, L.ptr(feats), L.ptr(h_saved),
-                                           L.ptr(ray_bias), L.ptr(packed), L.ptr(selector), L.ptr(d_density), L.ptr(d_rgb),
-                                           L.ptr(d_logit), L.ptr(d_feats), L.ptr(jacobian), L.ptr(d_pos), L.ptr(ws), nbytes,
-                                           L.stream_ptr(dev)), "field_mlp_bwd_rays")
-        return d_feats, d_pos
-    L.check(lib.fnr_field_mlp_bwd(C.byref(net), C.byref(grads), rays.ref, S, L.ptr(feats), L.ptr(h_saved),
-                                  L.ptr(ray_bias), L.ptr(packed), L.ptr(selector), L.ptr(d_density), L.ptr(d_rgb), L.ptr(d_logit), L.ptr(d_feats), L.ptr(ws), nbytes,
-                                  L.stream_ptr(dev)), "field_mlp_bwd")
-    return d_feats
+        name, args = "field_mlp_bwd_semgrad", common + position + optimiser + workspace
+    elif weight_adam is not None:
+        name, args = "field_mlp_bwd_adam", common + position + optimiser + workspace
+    elif jacobian is not None:
+        name, args = "field_mlp_bwd_rays", common + position + workspace
+    else:
+        name, args = "field_mlp_bwd", common + workspace
+    L.check(getattr(lib, "fnr_" + name)(*args), name)
+    return (d_feats, d_pos) if jacobian is not None else d_feats
 
 
 class _WorkspaceCache:

@@ -60,8 +60,8 @@ __device__ __forceinline__ void table_adam_update(const TableAdam& a, float g, f
     }
   }
 }
-// The optimiser step of a parameter taken by the thread that finishes its gradient entry (k_reduce_dw,
-// k_embedding_grad, k_prop_reduce in prop_bwd.hip: single writers): the parameter / moment arrays parallel the gradient arena.
+// The optimiser step of a parameter taken by the thread that finishes its gradient entry (both roles of k_finish_weights in
+// field_mlp_bwd.hip, k_prop_reduce in prop_bwd.hip: single writers): the parameter / moment arrays parallel the gradient arena.
 struct WeightAdam {
   TableAdam t;               // hyper-parameters and step-dependent scalars (its p / m / v pointers are unused here)
   long long p_off, m_off, v_off;   // element offsets from a GRADIENT address to the parameter / exp_avg / exp_avg_sq entry

@@ -121,52 +121,11 @@ __device__ __forceinline__ void pack_field_weights_bf16_block(const FieldPtrs& p
 }
 
 template <class Cfg>
-__global__ __launch_bounds__(256) void k_pack_field_weights_bf16(FieldPtrs p, int ns, __bf16* __restrict__ image) {
-  pack_field_weights_bf16_block<Cfg>(p, ns, image, blockIdx.x);
-}
-template <class Cfg>
 constexpr int pack_field_weights_bf16_blocks() { return (BfImage<Cfg>::BLOCKS * 64 + 255) / 256; }
 
+// the launch of k_pack_field_weights_bf16 (the bf16 pieces of the fragment image): field_mlp.hip, like launch_pack_field_weights
 template <class Cfg>
-static inline void launch_pack_field_weights_bf16(const FieldPtrs& p, int ns, __bf16* image, hipStream_t st) {
-  hipLaunchKernelGGL((k_pack_field_weights_bf16<Cfg>), dim3(pack_field_weights_bf16_blocks<Cfg>()), dim3(256), 0, st, p, ns,
-                     image);
-}
-
-// Everything a forward call prepares from the weights, ONE launch (three dependent ~5 us launches before): workgroups
-// [0, nb_pack) write the fp32 fragment image, [nb_pack, nb_pack + nb_pack16) the bf16 pieces (none in fp32 mode), the
-// rest the per-ray colour bias — read from the raw weights, so no role waits for another.
-template <class Cfg>
-__global__ __launch_bounds__(256) void k_prepare_field(FieldPtrs p, float* __restrict__ packed, int ns,
-                                                       __bf16* __restrict__ image, RaysDev rays,
-                                                       const float* __restrict__ embedding,
-                                                       const float* __restrict__ mean_embedding,
-                                                       float* __restrict__ ray_bias, int nb_pack, int nb_pack16) {
-  int b = blockIdx.x;
-  if (b < nb_pack) {
-    pack_field_weights_block<Cfg>(p, packed, b);
-    return;
-  }
-  b -= nb_pack;
-  if (b < nb_pack16) {
-    pack_field_weights_bf16_block<Cfg>(p, ns, image, b);
-    return;
-  }
-  b -= nb_pack16;
-  color_ray_bias_block<Cfg, true>(p, nullptr, rays, embedding, mean_embedding, ray_bias, b,
-                                  (int)gridDim.x - nb_pack - nb_pack16);
-}
-// ns = 0: fp32 mode (no bf16 pieces)
-template <class Cfg>
-static inline void launch_prepare_field(const FieldPtrs& p, float* packed, int ns, __bf16* image, const RaysDev& rays,
-                                        const float* embedding, const float* mean_embedding, float* ray_bias,
-                                        hipStream_t st) {
-  const int nb_pack = pack_field_weights_blocks<Cfg>();
-  const int nb_pack16 = ns > 0 ? pack_field_weights_bf16_blocks<Cfg>() : 0;
-  const long long nb_bias = color_ray_bias_blocks(rays);
-  hipLaunchKernelGGL((k_prepare_field<Cfg>), dim3((unsigned)(nb_pack + nb_pack16 + nb_bias)), dim3(256), 0, st, p, packed, ns,
-                     image, rays, embedding, mean_embedding, ray_bias, nb_pack, nb_pack16);
-}
+void launch_pack_field_weights_bf16(const FieldPtrs& p, int ns, __bf16* image, hipStream_t st);
 
 // ---- what a kernel keeps in LDS: an ordered list of (layer, forward | transposed) segments, NS pieces each -------
 // Segs: struct with  static constexpr int N;  static constexpr int layer(int i);  static constexpr bool isT(int i);
@@ -428,24 +387,30 @@ __device__ __forceinline__ void bf_layer_T1(const bf16x8* __restrict__ segT, con
   bf_layer_acc1<NS, NIBO, (NOB + 1) / 2>(segT, x, o, lane);
 }
 
-// ---- host entry points of the bf16-pipe modes (fnr_field_net.mlp_mode != 0), called from field_mlp.hip / field_mlp_bwd.hip ----
+// ---- host entry points of the bf16-pipe modes (fnr_field_net.mlp_mode != 0), forward: called from field_mlp.hip ----------
 // cfg: 0 `fruit_nerf`, 1 `fruit_nerf_big`; mode: MLP_BF16 | MLP_BF16X3; image_ws: the fragment image the caller has packed
 // (k_prepare_field / launch_pack_field_weights_bf16), field_bf16_image_bytes() covers both shapes at BF_MAX_PIECES.
-size_t field_bf16_image_bytes();  // field_mlp_bf16.hip, like the next three
+size_t field_bf16_image_bytes();  // field_mlp_bf16.hip, like the next two
 int field_mlp_fwd_bf16(int cfg, int mode, const FieldPtrs& p, const float* packed, void* image_ws, const float* ray_bias,
                        const RaysDev& rd, int S, long long N, const float2* feats, const uint8_t* selector, float* density,
                        float* rgb, float* logit, float* geo_out, float* h_buf, hipStream_t st);
 int field_mlp_fwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
                                const float* h_buf, float* logit, hipStream_t st);
-int field_mlp_bwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
-                               const float* h_saved, const float* d_logit, float* partials, long long blocks,
-                               hipStream_t st, float* d_h_semgrad = nullptr);  // pass_semantic_gradients: d_h [N,32] += dX of sem0
-namespace pw {
-// what the branches of one per-wave backward share (field_mlp_bwd_launch builds it once)
-struct BwdArgs {
-  const float* packed;
-  const __bf16* image;
-  const float* ray_bias;
+
+// ---- the backward: one argument block for the whole family, host side only (the kernels keep their loose pointer parameters).
+// field_mlp_bwd_entry (field_mlp_bwd.hip) validates the call and fills it once; the launch path and the launchers below take it.
+struct WeightAdam;  // adam.hpp
+struct FieldBwdArgs {
+  int cfg, mode;             // 0 `fruit_nerf` | 1 `fruit_nerf_big`; FNR_MLP_FP32 | FNR_MLP_BF16 | FNR_MLP_BF16X3
+  FieldPtrs p, gp;           // the nn.Linear tensors and their gradients
+  const float* embedding;    // appearance embedding [n_images, 32] and its gradient
+  float* g_embedding;
+  int n_images, n_levels;
+  const WeightAdam* wadam;   // NULL: gradients are added into gp / g_embedding; else the weight finish takes the optimiser step
+  const float* packed;       // fp32 fragment image: the forward pass's (saved) or the workspace's (pack_images)
+  const __bf16* image;       // ... and its bf16 pieces
+  const float* ray_bias;     // saved by the forward pass, or the workspace's (make_ray_bias)
+  bool pack_images, make_ray_bias, semgrad;  // semgrad (pass_semantic_gradients): the semantic branch adds its dX into d_h
   RaysDev rd;
   int S;
   long long N;
@@ -454,13 +419,18 @@ struct BwdArgs {
   const uint8_t* selector;
   const float *d_density, *d_rgb, *d_logit;
   float2* d_feats;
-  float *d_h, *gsum_tile, *gsum_extra, *partials;
-  long long blocks;  // workgroups = partial images, the same for every branch
+  float *d_h, *gsum_tile, *gsum_extra, *g_ray, *partials;  // gsum_extra: NULL unless tiles straddle rays (S % 16 != 0)
+  long long blocks;          // workgroups = partial images, the same for every branch
+  const float2* jac;         // the encode's input Jacobian and the position gradient: both or neither
+  float4* d_pos;
   hipStream_t st;
 };
-}  // namespace pw
-// branch: 0 colour, 1 semantic (`fruit_nerf` only), 2 base — with jac and d_pos, the base branch also writes the position
-// gradient; 3 (`fruit_nerf` only, pass_semantic_gradients): a.d_h += the input gradient of mlp_semantics.  field_mlp_bwd_pw.hip
-int field_mlp_bwd_pw(int cfg, int mode, int branch, const pw::BwdArgs& a, const float2* jac, float4* d_pos);
+// One launcher per arithmetic, one branch per call.  BR_SEM_DX (`fruit_nerf`, bf16 modes, semgrad): d_h += the input gradient
+// of mlp_semantics, a kernel of its own ahead of BR_SEM; everywhere else the semantic kernel forms it itself.
+enum { BR_COLOR = 0, BR_SEM = 1, BR_BASE = 2, BR_SEM_DX = 3 };
+int field_mlp_bwd_fp32(int branch, const FieldBwdArgs& a);  // field_mlp_bwd_fp32.hip; `fruit_nerf_big`'s BR_SEM is two launches
+// bf16 modes, every branch but `fruit_nerf_big`'s BR_SEM; with a.jac, BR_BASE also writes the position gradient
+int field_mlp_bwd_pw(int branch, const FieldBwdArgs& a);    // field_mlp_bwd_pw.hip
+int field_mlp_bwd_sem_big_bf16(const FieldBwdArgs& a);      // bf16 modes, `fruit_nerf_big`'s BR_SEM: field_mlp_bf16.hip
 
 }  // namespace fnr

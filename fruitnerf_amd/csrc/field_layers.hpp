@@ -236,16 +236,10 @@ __device__ __forceinline__ void pack_field_weights_block(const FieldPtrs& p, flo
   }
 }
 template <class Cfg>
-__global__ __launch_bounds__(256) void k_pack_field_weights(FieldPtrs p, float* __restrict__ packed) {
-  pack_field_weights_block<Cfg>(p, packed, blockIdx.x);
-}
-template <class Cfg>
 constexpr int pack_field_weights_blocks() { return (Cfg::PACKED_FLOATS + 255) / 256; }
-
+// the launch of k_pack_field_weights: defined, and instantiated for the two built shapes, in field_mlp.hip alone
 template <class Cfg>
-static inline void launch_pack_field_weights(const FieldPtrs& p, float* packed, hipStream_t st) {
-  hipLaunchKernelGGL((k_pack_field_weights<Cfg>), dim3((Cfg::PACKED_FLOATS + 255) / 256), dim3(256), 0, st, p, packed);
-}
+void launch_pack_field_weights(const FieldPtrs& p, float* packed, hipStream_t st);
 
 // out^T[16 NOB][16] += W[:, input blocks 0..NIB-1] * in^T ; `in`/`out` are C-layout accumulators.
 // NIB_STRIDE = number of input blocks of the layer in the image (> NIB when only the leading blocks are used).
@@ -370,25 +364,14 @@ __device__ __forceinline__ void color_ray_bias_block(const FieldPtrs& p, const f
     ray_bias[(size_t)ray * 64 + lane] = acc;
   }
 }
-template <class Cfg>
-__global__ __launch_bounds__(256) void k_color_ray_bias(const float* __restrict__ packed, RaysDev rays,
-                                                        const float* __restrict__ embedding,
-                                                        const float* __restrict__ mean_embedding,
-                                                        float* __restrict__ ray_bias) {
-  FieldPtrs none{};
-  color_ray_bias_block<Cfg, false>(none, packed, rays, embedding, mean_embedding, ray_bias, blockIdx.x, gridDim.x);
-}
 static inline long long color_ray_bias_blocks(const RaysDev& rays) {
   long long blocks = (rays.n_rays + 7) / 8;
   if (blocks > 8ll * device_cu_count()) blocks = 8ll * device_cu_count();
   return blocks < 1 ? 1 : blocks;
 }
-
+// the launch of k_color_ray_bias (the packed-image form of the block above): field_mlp.hip, like launch_pack_field_weights
 template <class Cfg>
-static inline void launch_color_ray_bias(const float* packed, const RaysDev& rays, const float* embedding,
-                                         const float* mean_embedding, float* ray_bias, hipStream_t st) {
-  hipLaunchKernelGGL((k_color_ray_bias<Cfg>), dim3((unsigned)color_ray_bias_blocks(rays)), dim3(256), 0, st, packed, rays,
-                     embedding, mean_embedding, ray_bias);
-}
+void launch_color_ray_bias(const float* packed, const RaysDev& rays, const float* embedding, const float* mean_embedding,
+                           float* ray_bias, hipStream_t st);
 
 }  // namespace fnr

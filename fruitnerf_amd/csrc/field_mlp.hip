@@ -48,6 +48,83 @@ static inline size_t fwd_ws_packed_bytes() { return ((size_t)(FIELD_MAX_PACKED_F
 size_t field_fwd_ws_image_offset() { return fwd_ws_packed_bytes(); }
 static inline size_t fwd_ws_fixed_bytes() { return fwd_ws_packed_bytes() + (field_bf16_image_bytes() + 255) / 256 * 256; }
 
+// ---- the launches that prepare a call's images from the weights: defined here alone, the backward's three instantiated below
+template <class Cfg>
+__global__ __launch_bounds__(256) void k_pack_field_weights(FieldPtrs p, float* __restrict__ packed) {
+  pack_field_weights_block<Cfg>(p, packed, blockIdx.x);
+}
+template <class Cfg>
+void launch_pack_field_weights(const FieldPtrs& p, float* packed, hipStream_t st) {
+  hipLaunchKernelGGL((k_pack_field_weights<Cfg>), dim3((Cfg::PACKED_FLOATS + 255) / 256), dim3(256), 0, st, p, packed);
+}
+
+template <class Cfg>
+__global__ __launch_bounds__(256) void k_color_ray_bias(const float* __restrict__ packed, RaysDev rays,
+                                                        const float* __restrict__ embedding,
+                                                        const float* __restrict__ mean_embedding,
+                                                        float* __restrict__ ray_bias) {
+  FieldPtrs none{};
+  color_ray_bias_block<Cfg, false>(none, packed, rays, embedding, mean_embedding, ray_bias, blockIdx.x, gridDim.x);
+}
+template <class Cfg>
+void launch_color_ray_bias(const float* packed, const RaysDev& rays, const float* embedding, const float* mean_embedding,
+                           float* ray_bias, hipStream_t st) {
+  hipLaunchKernelGGL((k_color_ray_bias<Cfg>), dim3((unsigned)color_ray_bias_blocks(rays)), dim3(256), 0, st, packed, rays,
+                     embedding, mean_embedding, ray_bias);
+}
+
+template <class Cfg>
+__global__ __launch_bounds__(256) void k_pack_field_weights_bf16(FieldPtrs p, int ns, __bf16* __restrict__ image) {
+  pack_field_weights_bf16_block<Cfg>(p, ns, image, blockIdx.x);
+}
+template <class Cfg>
+void launch_pack_field_weights_bf16(const FieldPtrs& p, int ns, __bf16* image, hipStream_t st) {
+  hipLaunchKernelGGL((k_pack_field_weights_bf16<Cfg>), dim3(pack_field_weights_bf16_blocks<Cfg>()), dim3(256), 0, st, p, ns,
+                     image);
+}
+
+// Everything a forward call prepares from the weights, ONE launch (three dependent ~5 us launches before): workgroups
+// [0, nb_pack) write the fp32 fragment image, [nb_pack, nb_pack + nb_pack16) the bf16 pieces (none in fp32 mode), the
+// rest the per-ray colour bias — read from the raw weights, so no role waits for another.
+template <class Cfg>
+__global__ __launch_bounds__(256) void k_prepare_field(FieldPtrs p, float* __restrict__ packed, int ns,
+                                                       __bf16* __restrict__ image, RaysDev rays,
+                                                       const float* __restrict__ embedding,
+                                                       const float* __restrict__ mean_embedding,
+                                                       float* __restrict__ ray_bias, int nb_pack, int nb_pack16) {
+  int b = blockIdx.x;
+  if (b < nb_pack) {
+    pack_field_weights_block<Cfg>(p, packed, b);
+    return;
+  }
+  b -= nb_pack;
+  if (b < nb_pack16) {
+    pack_field_weights_bf16_block<Cfg>(p, ns, image, b);
+    return;
+  }
+  b -= nb_pack16;
+  color_ray_bias_block<Cfg, true>(p, nullptr, rays, embedding, mean_embedding, ray_bias, b,
+                                  (int)gridDim.x - nb_pack - nb_pack16);
+}
+// ns = 0: fp32 mode (no bf16 pieces)
+template <class Cfg>
+static void launch_prepare_field(const FieldPtrs& p, float* packed, int ns, __bf16* image, const RaysDev& rays,
+                                 const float* embedding, const float* mean_embedding, float* ray_bias, hipStream_t st) {
+  const int nb_pack = pack_field_weights_blocks<Cfg>();
+  const int nb_pack16 = ns > 0 ? pack_field_weights_bf16_blocks<Cfg>() : 0;
+  const long long nb_bias = color_ray_bias_blocks(rays);
+  hipLaunchKernelGGL((k_prepare_field<Cfg>), dim3((unsigned)(nb_pack + nb_pack16 + nb_bias)), dim3(256), 0, st, p, packed, ns,
+                     image, rays, embedding, mean_embedding, ray_bias, nb_pack, nb_pack16);
+}
+
+#define FNR_INSTANTIATE(C)                                                                                                \
+  template void launch_pack_field_weights<C>(const FieldPtrs&, float*, hipStream_t);                                      \
+  template void launch_color_ray_bias<C>(const float*, const RaysDev&, const float*, const float*, float*, hipStream_t); \
+  template void launch_pack_field_weights_bf16<C>(const FieldPtrs&, int, __bf16*, hipStream_t);
+FNR_INSTANTIATE(FieldCfgBase)
+FNR_INSTANTIATE(FieldCfgBig)
+#undef FNR_INSTANTIATE
+
 // ---- per-tile pieces shared by the forward and backward kernels ("R" = the LdsRange the kernel staged) ----------
 
 // B operand of base layer 0 from the level-major features: lane group g covers levels {g, 4+g, 8+g, 12+g}

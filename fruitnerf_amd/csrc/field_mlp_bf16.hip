@@ -4,13 +4,18 @@
 //                       product in the forward pass and in the backward's forward recompute, 3 in dX / dW — fp32-grade
 //                       results at 16/6 resp. 16/3 of the fp32-MFMA issue rate;
 //   FNR_MLP_BF16   (1)  plain bf16 operands, fp32 accumulate — throughput mode, not parity grade.
-// Same entry points, buffers and partial-gradient image as the fp32 kernels (field_mlp.hip, field_mlp_bwd.hip):
-// the per-ray colour bias, the per-ray / per-camera finish of mlp_head layer 0 and k_reduce_dw are shared.
+// Same entry points, buffers and partial-gradient image as the fp32 kernels (field_mlp.hip, field_mlp_bwd_fp32.hip):
+// the per-ray colour bias and the backward's per-ray and weight finish (k_color_ray_grads, k_finish_weights:
+// field_mlp_bwd.hip, which also runs the backward's branches in order) are shared.
 // Replaces the same reference code: fruit_field.py:132-166,187-281 and its autograd.
 // This file: the forward pass of both shapes (one wave = one PAIR of 16-sample tiles sharing every LDS fragment) and the
 // 128-wide semantic branch of `fruit_nerf_big`, forward and backward: one tile per wave, 8 waves = a 128-sample batch,
 // weight streaming because its fragments exceed the LDS, COOPERATIVE dW (every 16 x 16 block of a layer's weight gradient
 // owned by one wave over the batch).  Every other branch's backward is per-wave: field_mlp_bwd_pw.hip.
+// That one backward kernel stays next to the forward kernels ON PURPOSE: what hipcc emits for a kernel of this file depends
+// on which others the module holds (shared helper instantiations and dynamic-LDS symbol; the IR first differs after the
+// inliner).  Without the backward kernel k_field_mlp_fwd_sem_big_bf16 becomes other code (170 instead of 208 registers at
+// three pieces), without both k_field_mlp_fwd_bf16 of `fruit_nerf_big` does: splitting the file is a kernel change.
 #include <type_traits>
 
 #include "field_bf16.hpp"
@@ -157,7 +162,7 @@ __device__ __forceinline__ void zero_vec_bf(f32x4 (&a)[N]) {
 // `fruit_nerf_big` semantic branch, backward: mlp_semantics 30 -> 128 -> 128 -> 64 + SemanticFieldHead
 // (fruit_field.py:144-156,263-268 with fruit_nerf_config.py:82-95).  Its 119 KB of fp32 weights, 464 accumulator
 // registers of dW and 128-wide activations made the fp32 path two launches of 4 waves x 512 registers that each repeat
-// the forward and most of the dX chain (field_mlp_bwd.hip: 2.26 ms of a 7.06 ms step at 8192 rays).  Here:
+// the forward and most of the dX chain (field_mlp_bwd_fp32.hip: 2.26 ms of a 7.06 ms step at 8192 rays).  Here:
 //   * WEIGHT STREAMING: a workgroup of 8 waves takes a batch of 8 tiles (128 samples) through the branch layer by layer;
 //     the bf16 fragment pieces of the layer(s) in use are re-staged from L2 into the SAME LDS region per phase
 //     (forward sem0+sem1 at three pieces, 120 KB | transposed head+sem2 | transposed sem1 at two: ~1.8 KB of L2 reads per sample);
@@ -527,45 +532,24 @@ int field_mlp_fwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, con
   return launch(ensure_dyn_lds<kern>(bytes), kern, bytes);
 }
 
-int field_mlp_bwd_sem_big_bf16(int mode, const FieldPtrs& p, void* image_ws, const float* packed, long long N,
-                               const float* h_saved, const float* d_logit, float* partials, long long blocks,
-                               hipStream_t st, float* d_h_semgrad) {
+template <int NSF, int NS>  // pass_semantic_gradients: the SEMGRAD instantiation, which takes d_h as one more argument
+static int bwd_launch(const FieldBwdArgs& a) {
   using Cfg = FieldCfgBig;
-  __bf16* image = reinterpret_cast<__bf16*>(image_ws);  // packed by field_mlp_bwd_launch (or the forward pass)
-  auto launch = [&](int once, auto kern, int bytes) -> int {
+  constexpr int bytes = cs_words<NS>() * 4 + (256 + 144) * 4;
+  static_assert(bytes <= 160 * 1024, "fruit_nerf_big semantic branch exceeds the LDS");
+  auto go = [&](int once, auto kern, auto... d_h) -> int {
     if (once) return once;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), bytes, st, packed, image, p.w[Cfg::L_SEM2], p.b[Cfg::L_SEM2],
-                       N, h_saved, d_logit, partials);
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.blocks), dim3(512), bytes, a.st, a.packed, a.image, a.p.w[Cfg::L_SEM2],
+                       a.p.b[Cfg::L_SEM2], a.N, a.h_saved, a.d_logit, a.partials, d_h...);
     FNR_LAUNCH_CHECK();
     return FNR_OK;
   };
-  if (d_h_semgrad) {  // pass_semantic_gradients: the same launches of the SEMGRAD instantiations
-    auto launch_sg = [&](int once, auto kern, int bytes) -> int {
-      if (once) return once;
-      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), bytes, st, packed, image, p.w[Cfg::L_SEM2],
-                         p.b[Cfg::L_SEM2], N, h_saved, d_logit, partials, d_h_semgrad);
-      FNR_LAUNCH_CHECK();
-      return FNR_OK;
-    };
-    if (mode == MLP_BF16) {
-      constexpr int bytes = cs_words<1>() * 4 + (256 + 144) * 4;
-      constexpr auto kern = k_field_mlp_bwd_sem_big_bf16<Cfg, 1, 1, true, float*>;
-      return launch_sg(ensure_dyn_lds<kern>(bytes), kern, bytes);
-    }
-    constexpr int bytes = cs_words<2>() * 4 + (256 + 144) * 4;
-    constexpr auto kern = k_field_mlp_bwd_sem_big_bf16<Cfg, 3, 2, true, float*>;
-    return launch_sg(ensure_dyn_lds<kern>(bytes), kern, bytes);
-  }
-  if (mode == MLP_BF16) {
-    constexpr int bytes = cs_words<1>() * 4 + (256 + 144) * 4;
-    constexpr auto kern = k_field_mlp_bwd_sem_big_bf16<Cfg, 1, 1>;
-    return launch(ensure_dyn_lds<kern>(bytes), kern, bytes);
-  }
-  constexpr int bytes = cs_words<2>() * 4 + (256 + 144) * 4;
-  static_assert(bytes <= 160 * 1024, "fruit_nerf_big semantic branch exceeds the LDS");
-  constexpr auto kern = k_field_mlp_bwd_sem_big_bf16<Cfg, 3, 2>;
-  return launch(ensure_dyn_lds<kern>(bytes), kern, bytes);
+  constexpr auto kern = k_field_mlp_bwd_sem_big_bf16<Cfg, NSF, NS>;
+  constexpr auto kern_sg = k_field_mlp_bwd_sem_big_bf16<Cfg, NSF, NS, true, float*>;
+  return a.semgrad ? go(ensure_dyn_lds<kern_sg>(bytes), kern_sg, a.d_h) : go(ensure_dyn_lds<kern>(bytes), kern);
 }
+
+int field_mlp_bwd_sem_big_bf16(const FieldBwdArgs& a) { return a.mode == MLP_BF16 ? bwd_launch<1, 1>(a) : bwd_launch<3, 2>(a); }
 
 // ---- forward launch (called from field_mlp.hip when fnr_field_net.mlp_mode != 0) -----------------------------------
 template <class Cfg, int NS>

@@ -1027,7 +1027,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void k_field_mlp_sem_dx_pw(
 #define FNR_PW_WAVES 8
 #endif
 template <class Cfg, int NSF, int NS>
-static int launch(const BwdArgs& a) {
+static int launch(const FieldBwdArgs& a) {
   if constexpr (Cfg::NSEM == 2) {
     constexpr int WAVES = FNR_PW_WAVES, THREADS = 64 * WAVES, NT = FNR_PW_NT_SEM_DX;
     FNR_CHECK_ARG(a.N < (1ll << 31) - 64, "field_mlp_bwd: %lld samples exceed the 32-bit sample index of the backward kernels", a.N);
@@ -1066,15 +1066,15 @@ namespace pw {
 #endif
 
 template <class Cfg, int NSF, int NS>
-static int launch(int branch, const BwdArgs& a, const float2* jac, float4* d_pos) {
-  if (branch == 3) return pw_dx::launch<Cfg, NSF, NS>(a);
+static int launch(int branch, const FieldBwdArgs& a) {
+  if (branch == BR_SEM_DX) return pw_dx::launch<Cfg, NSF, NS>(a);
   constexpr int WAVES = FNR_PW_WAVES, THREADS = 64 * WAVES;
   FNR_CHECK_ARG(a.N < (1ll << 31) - 64, "field_mlp_bwd: %lld samples exceed the 32-bit sample index of the backward kernels", a.N);
   const int n = (int)a.N;
   // exactly `blocks` workgroups: every one of the caller's partial images receives this branch's blocks (a workgroup
   // without samples stores zeros)
   const dim3 grid((unsigned)a.blocks);
-  if (branch == 0) {
+  if (branch == BR_COLOR) {
     constexpr int NT = FNR_PW_NT_COLOR;
     using L = Lds<Cfg, SegsColF<Cfg>, SegsColT<Cfg>, NSF, NS, NT, WAVES, 80>;
     static_assert(L::BYTES <= 160 * 1024, "colour branch exceeds the LDS");
@@ -1083,7 +1083,7 @@ static int launch(int branch, const BwdArgs& a, const float2* jac, float4* d_pos
     if (once) return once;
     hipLaunchKernelGGL(kern, grid, dim3(THREADS), L::BYTES, a.st, a.packed, a.image, a.ray_bias, a.rd, a.S, n, a.h_saved, a.d_rgb,
                        a.d_h, a.gsum_tile, a.gsum_extra, a.partials);
-  } else if (branch == 1) {
+  } else if (branch == BR_SEM) {
     if constexpr (Cfg::NSEM == 2) {
       constexpr int NT = NSF == 1 ? 1 : FNR_PW_NT_SEM;  // (plain bf16: hipcc's schedule of the two-tile form spills 8 registers)
       using L = Lds<Cfg, SegsSemF<Cfg>, SegsSemT<Cfg>, NSF, NS, NT, WAVES, 128>;
@@ -1099,19 +1099,13 @@ static int launch(int branch, const BwdArgs& a, const float2* jac, float4* d_pos
     constexpr int NT = Cfg::HB == 1 ? FNR_PW_NT_BASE : FNR_PW_NT_BASE_BIG;
     using L = Lds<Cfg, SegsBaseF<Cfg>, SegsBaseT<Cfg>, NSF, NS, NT, WAVES, 64>;
     static_assert(L::BYTES <= 160 * 1024, "base branch exceeds the LDS");
-    if (jac && d_pos) {
-      constexpr auto kern = k_field_mlp_bwd_base_pw<Cfg, NSF, NS, NT, WAVES, true>;
-      const int once = ensure_dyn_lds<kern>(L::BYTES);
-      if (once) return once;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), L::BYTES, a.st, a.packed, a.image, n, a.feats, a.h_saved, a.selector,
-                         a.d_density, a.d_h, a.d_feats, a.partials, jac, d_pos);
-    } else {
-      constexpr auto kern = k_field_mlp_bwd_base_pw<Cfg, NSF, NS, NT, WAVES, false>;
-      const int once = ensure_dyn_lds<kern>(L::BYTES);
-      if (once) return once;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), L::BYTES, a.st, a.packed, a.image, n, a.feats, a.h_saved, a.selector,
-                         a.d_density, a.d_h, a.d_feats, a.partials, jac, d_pos);
-    }
+    constexpr auto with_pos = k_field_mlp_bwd_base_pw<Cfg, NSF, NS, NT, WAVES, true>;
+    constexpr auto without = k_field_mlp_bwd_base_pw<Cfg, NSF, NS, NT, WAVES, false>;
+    const bool pos = a.jac && a.d_pos;
+    const int once = pos ? ensure_dyn_lds<with_pos>(L::BYTES) : ensure_dyn_lds<without>(L::BYTES);
+    if (once) return once;
+    hipLaunchKernelGGL(pos ? with_pos : without, grid, dim3(THREADS), L::BYTES, a.st, a.packed, a.image, n, a.feats, a.h_saved,
+                       a.selector, a.d_density, a.d_h, a.d_feats, a.partials, a.jac, a.d_pos);
   }
   FNR_LAUNCH_CHECK();
   return FNR_OK;
@@ -1122,10 +1116,10 @@ static int launch(int branch, const BwdArgs& a, const float2* jac, float4* d_pos
 // The backward of every branch but `fruit_nerf_big`'s semantic one (field_mlp_bwd_sem_big_bf16) in the bf16-pipe modes; the
 // arguments are described at the declaration (field_bf16.hpp).  The bf16x3 mode runs dX / dW with two pieces (three products),
 // the forward recompute with three.
-int field_mlp_bwd_pw(int cfg, int mode, int branch, const pw::BwdArgs& a, const float2* jac, float4* d_pos) {
-#define FNR_PW_LAUNCH(C, A, B) pw::launch<C, A, B>(branch, a, jac, d_pos)
-  if (cfg == 0) return mode == MLP_BF16 ? FNR_PW_LAUNCH(FieldCfgBase, 1, 1) : FNR_PW_LAUNCH(FieldCfgBase, 3, 2);
-  return mode == MLP_BF16 ? FNR_PW_LAUNCH(FieldCfgBig, 1, 1) : FNR_PW_LAUNCH(FieldCfgBig, 3, 2);
+int field_mlp_bwd_pw(int branch, const FieldBwdArgs& a) {
+#define FNR_PW_LAUNCH(C, A, B) pw::launch<C, A, B>(branch, a)
+  if (a.cfg == 0) return a.mode == MLP_BF16 ? FNR_PW_LAUNCH(FieldCfgBase, 1, 1) : FNR_PW_LAUNCH(FieldCfgBase, 3, 2);
+  return a.mode == MLP_BF16 ? FNR_PW_LAUNCH(FieldCfgBig, 1, 1) : FNR_PW_LAUNCH(FieldCfgBig, 3, 2);
 #undef FNR_PW_LAUNCH
 }
 

@@ -1273,7 +1273,7 @@ LOSSES_ON_SIDE = os.environ.get("FNR_LOSSES_ON_SIDE", "1") != "0"
 # the second stream.  FNR_FUSE_COMPOSITE_BACKWARD=0: two launches (A/B); same bits either way.
 FUSE_COMPOSITE_BACKWARD = os.environ.get("FNR_FUSE_COMPOSITE_BACKWARD", "1") != "0"
 FUSE_CAMERA_OPTIMIZER = True  # single process: the pose table's optimiser step runs inside the pose-gradient kernel
-FUSE_WEIGHT_OPTIMIZER = True  # ... and the field's MLP weights + embedding step inside k_reduce_dw / k_embedding_grad
+FUSE_WEIGHT_OPTIMIZER = True  # ... and the field's MLP weights + embedding step inside k_finish_weights
 FUSE_TABLE_OPTIMIZER = True   # single process: the main hash table's Adam / RAdam step runs inside the scatter
 
 

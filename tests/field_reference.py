@@ -6,7 +6,7 @@ The operation (float32 inputs upcast; `x` [N,32] = the hash features, column 2 l
   logit = head(mlp_semantics(h[1:1 + geo]))      (geo detached unless semgrad)
   c_ray = [SH16((d + 1) / 2) | embedding[camera] or the mean embedding]; ray_bias = b_c0 + W_c0[:, const columns] c_ray  [R,64]
   c1 = ray_bias[ray] + W_c0[:, geo columns] geo, c2 = W_c1 relu(c1) + b_c1, c3 = W_c2 relu(c2) + b_c2, rgb = sigmoid(c3)
-What the kernels save and recompute (csrc/field_mlp_bwd.hip, field_mlp_bwd_pw.hip): h [N, 16 | 32] and ray_bias are SAVED by
+What the kernels save and recompute (csrc/field_mlp_bwd_fp32.hip, field_mlp_bwd_pw.hip, field_mlp_bf16.hip): h [N, 16 | 32] and ray_bias are SAVED by
 the forward; the backward recomputes a1 and h from the features (base branch, for the gates and trunc_exp), the colour and
 semantic activations from the saved h, and the sigmoid s from the recomputed c3, forming d_c3 = d_rgb * s * (1 - s) in float32.
 ray_bias, the per-ray sums of the colour branch's first-layer gradient, the ray-constant columns of W_c0, its bias and the
