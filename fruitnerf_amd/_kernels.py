@@ -1377,24 +1377,39 @@ class CameraTableArg:
         return C.byref(self.c)
 
 
-def _table_ref(cams: Optional["CameraTableArg"], image_set: "ImageSetArg"):
-    """The nullable camera-table argument of the fnr_*_mode entry points."""
-    return None if cams is None else cams.ref(image_set)
+def _camera_entry(op: str, image_set: ImageSetArg, cams: Optional[CameraTableArg], pose_mode: int, per_edge: bool = False):
+    """The entry point of `op` for a configuration -> (call, options): `call(*args)` runs it and raises on failure,
+    `options` are the arguments the chosen form takes for the table and the mode (after the image set, where there is one).
+    fnr_<op>_edges iff per_edge; else fnr_<op>_mode iff the mode is not SO3xR3; else fnr_<op>_cams iff a table is given; else
+    fnr_<op>.  The _mode and _edges forms take a nullable table."""
+    table = None if cams is None else cams.ref(image_set)
+    if per_edge:
+        name, options = op + "_edges", (table, pose_mode)
+    elif pose_mode != L.FNR_POSE_SO3XR3:
+        name, options = op + "_mode", (table, pose_mode)
+    elif cams is None:
+        name, options = op, ()
+    else:
+        name, options = op + "_cams", (table,)
+    fn = getattr(L.load(), "fnr_" + name)
+    return (lambda *args: L.check(fn(*args), name)), options
+
+
+def _ray_outputs(R: int, dev) -> dict:
+    """The per-ray outputs of pixel sampling: origins, directions, camera index, target colour, fruit mask."""
+    return {"origins": _empty(R, 3, device=dev), "directions": _empty(R, 3, device=dev),
+            "cam": _empty(R, dtype=torch.int32, device=dev), "image": _empty(R, 3, device=dev), "mask": _empty(R, device=dev)}
 
 
 def camera_adjust(image_set: ImageSetArg, train_ids: Tensor, pose_adjustment: Tensor,
                   pose_mode: int = L.FNR_POSE_SO3XR3) -> Tensor:
     """c2w' [n_train,3,4] = multiply(c2w[train_ids], exp_map(pose_adjustment)), the exponential map of pose_mode
     (L.FNR_POSE_SO3XR3 | L.FNR_POSE_SE3; anything but SO3xR3 goes through the fnr_*_mode entry points)."""
-    lib = L.load()
+    call, options = _camera_entry("camera_adjust", image_set, None, pose_mode)
     ids = train_ids.to(torch.int64).contiguous()
     out = torch.empty(ids.numel(), 3, 4, device=pose_adjustment.device)
-    if pose_mode == L.FNR_POSE_SO3XR3:
-        L.check(lib.fnr_camera_adjust(L.ptr(image_set.c2w), L.ptr(ids), ids.numel(), L.ptr(_f32c(pose_adjustment)),
-                                      L.ptr(out), L.stream_ptr(out.device)), "camera_adjust")
-    else:
-        L.check(lib.fnr_camera_adjust_mode(L.ptr(image_set.c2w), L.ptr(ids), ids.numel(), L.ptr(_f32c(pose_adjustment)),
-                                           pose_mode, L.ptr(out), L.stream_ptr(out.device)), "camera_adjust_mode")
+    call(L.ptr(image_set.c2w), L.ptr(ids), ids.numel(), L.ptr(_f32c(pose_adjustment)), *options[1:], L.ptr(out),
+         L.stream_ptr(out.device))       # (no table here: of the options only the mode)
     return out
 
 
@@ -1404,17 +1419,11 @@ def camera_pose_grad(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, cam: 
     """pose_grad [n_train,6] += d(loss)/d(pose_adjustment) from the ray gradients of the rays drawn with `u`
     (cams: through that camera table, fnr_camera_pose_grad_cams; pose_mode: the exponential map the cameras were
     adjusted with)."""
-    lib = L.load()
+    call, options = _camera_entry("camera_pose_grad", image_set, cams, pose_mode)
     ids = train_ids.to(torch.int64).contiguous()
-    rest = (L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)), L.ptr(cam), L.ptr(_f32c(pose_adjustment)),
-            L.ptr(c2w_adjusted), L.ptr(d_origins), L.ptr(d_directions), L.ptr(pose_grad), L.stream_ptr(u.device))
-    if pose_mode != L.FNR_POSE_SO3XR3:
-        L.check(lib.fnr_camera_pose_grad_mode(C.byref(image_set.c), _table_ref(cams, image_set), pose_mode, *rest),
-                "camera_pose_grad_mode")
-    elif cams is None:
-        L.check(lib.fnr_camera_pose_grad(C.byref(image_set.c), *rest), "camera_pose_grad")
-    else:
-        L.check(lib.fnr_camera_pose_grad_cams(C.byref(image_set.c), cams.ref(image_set), *rest), "camera_pose_grad_cams")
+    call(C.byref(image_set.c), *options, L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)), L.ptr(cam),
+         L.ptr(_f32c(pose_adjustment)), L.ptr(c2w_adjusted), L.ptr(d_origins), L.ptr(d_directions), L.ptr(pose_grad),
+         L.stream_ptr(u.device))
 
 
 def camera_pose_grad_adam(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, cam: Tensor, c2w_adjusted: Tensor,
@@ -1422,18 +1431,10 @@ def camera_pose_grad_adam(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, 
                           cams: Optional[CameraTableArg] = None, pose_mode: int = L.FNR_POSE_SO3XR3) -> None:
     """camera_pose_grad + the pose table's Adam / RAdam step (adam.params = pose_adjustment) in one launch; pose_grad
     is consumed and left zero."""
-    lib = L.load()
+    call, options = _camera_entry("camera_pose_grad_adam", image_set, cams, pose_mode)
     ids = train_ids.to(torch.int64).contiguous()
-    rest = (L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)), L.ptr(cam), L.ptr(c2w_adjusted), L.ptr(d_origins),
-            L.ptr(d_directions), L.ptr(pose_grad), C.byref(adam), L.stream_ptr(u.device))
-    if pose_mode != L.FNR_POSE_SO3XR3:
-        L.check(lib.fnr_camera_pose_grad_adam_mode(C.byref(image_set.c), _table_ref(cams, image_set), pose_mode, *rest),
-                "camera_pose_grad_adam_mode")
-    elif cams is None:
-        L.check(lib.fnr_camera_pose_grad_adam(C.byref(image_set.c), *rest), "camera_pose_grad_adam")
-    else:
-        L.check(lib.fnr_camera_pose_grad_adam_cams(C.byref(image_set.c), cams.ref(image_set), *rest),
-                "camera_pose_grad_adam_cams")
+    call(C.byref(image_set.c), *options, L.ptr(ids), ids.numel(), u.shape[0], L.ptr(_f32c(u)), L.ptr(cam), L.ptr(c2w_adjusted),
+         L.ptr(d_origins), L.ptr(d_directions), L.ptr(pose_grad), C.byref(adam), L.stream_ptr(u.device))
 
 
 def train_prologue(image_set: ImageSetArg, train_ids: Tensor, n_rays: int, seed: int, offset: int,
@@ -1443,63 +1444,36 @@ def train_prologue(image_set: ImageSetArg, train_ids: Tensor, n_rays: int, seed:
     """fnr_train_prologue: random numbers + camera adjust + pixel sampling + level-0 spaced sampling in one launch
     (cams: rays through that camera table, fnr_train_prologue_cams; pose_mode: the exponential map of pose_adjustment;
     per_edge: one jitter per level-0 bin edge drawn in the kernel, fnr_train_prologue_edges — no "jitter" rows)."""
-    lib = L.load()
+    call, options = _camera_entry("train_prologue", image_set, cams, pose_mode, per_edge)
     dev = image_set.images.device
     R = int(n_rays)
     ids = train_ids.to(torch.int64).contiguous()
     n_train = ids.numel()
     out = {
         "u": _empty(R, 3, device=dev), "jitter": None if per_edge else _empty(n_jitter, R, device=dev),
-        "origins": _empty(R, 3, device=dev), "directions": _empty(R, 3, device=dev),
-        "cam": _empty(R, dtype=torch.int32, device=dev), "image": _empty(R, 3, device=dev),
-        "mask": _empty(R, device=dev), "spacing": _empty(R, S0 + 1, device=dev),
-        "euclid": _empty(R, S0 + 1, device=dev),
+        **_ray_outputs(R, dev), "spacing": _empty(R, S0 + 1, device=dev), "euclid": _empty(R, S0 + 1, device=dev),
         "c2w_adjusted": _empty(n_train, 3, 4, device=dev) if pose_adjustment is not None else None,
         "S0": S0, "near": float(near), "far": float(far), "spacing_kind": spacing_kind,
     }
     base = host_linspace(0.0, 1.0, S0 + 1, dev)
-    if per_edge:
-        L.check(lib.fnr_train_prologue_edges(
-            C.byref(image_set.c), _table_ref(cams, image_set), pose_mode, L.ptr(ids), n_train, R, int(seed) & (2 ** 64 - 1),
-            int(offset) & (2 ** 64 - 1), L.ptr(_f32c(pose_adjustment)) if pose_adjustment is not None else None,
-            L.ptr(out["c2w_adjusted"]), L.ptr(out["u"]), L.ptr(out["origins"]), L.ptr(out["directions"]), L.ptr(out["cam"]),
-            L.ptr(out["image"]), L.ptr(out["mask"]), float(near), float(far), spacing_kind, S0, L.ptr(base),
-            L.ptr(out["spacing"]), L.ptr(out["euclid"]), L.stream_ptr(dev)), "train_prologue_edges")
-        return out
-    rest = (L.ptr(ids), n_train, R, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
-            L.ptr(_f32c(pose_adjustment)) if pose_adjustment is not None else None,
-            L.ptr(out["c2w_adjusted"]), L.ptr(out["u"]), L.ptr(out["jitter"]), n_jitter,
-            L.ptr(out["origins"]), L.ptr(out["directions"]), L.ptr(out["cam"]), L.ptr(out["image"]),
-            L.ptr(out["mask"]), float(near), float(far), spacing_kind, S0, L.ptr(base),
-            L.ptr(out["spacing"]), L.ptr(out["euclid"]), L.stream_ptr(dev))
-    if pose_mode != L.FNR_POSE_SO3XR3:
-        L.check(lib.fnr_train_prologue_mode(C.byref(image_set.c), _table_ref(cams, image_set), pose_mode, *rest),
-                "train_prologue_mode")
-    elif cams is None:
-        L.check(lib.fnr_train_prologue(C.byref(image_set.c), *rest), "train_prologue")
-    else:
-        L.check(lib.fnr_train_prologue_cams(C.byref(image_set.c), cams.ref(image_set), *rest), "train_prologue_cams")
+    jitter = () if per_edge else (L.ptr(out["jitter"]), n_jitter)      # the per-edge form has neither argument
+    call(C.byref(image_set.c), *options, L.ptr(ids), n_train, R, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+         L.ptr(_f32c(pose_adjustment)) if pose_adjustment is not None else None, L.ptr(out["c2w_adjusted"]), L.ptr(out["u"]),
+         *jitter, L.ptr(out["origins"]), L.ptr(out["directions"]), L.ptr(out["cam"]), L.ptr(out["image"]), L.ptr(out["mask"]),
+         float(near), float(far), spacing_kind, S0, L.ptr(base), L.ptr(out["spacing"]), L.ptr(out["euclid"]), L.stream_ptr(dev))
     return out
 
 
 def sample_pixels(image_set: ImageSetArg, train_ids: Tensor, u: Tensor, c2w_adjusted: Optional[Tensor] = None,
                   cams: Optional[CameraTableArg] = None):
-    lib = L.load()
+    call, options = _camera_entry("sample_pixels", image_set, cams, L.FNR_POSE_SO3XR3)
     dev = u.device
     R = u.shape[0]
     ids = train_ids.to(torch.int64).contiguous()
-    origins = _empty(R, 3, device=dev)
-    directions = _empty(R, 3, device=dev)
-    cam = _empty(R, dtype=torch.int32, device=dev)
-    image = _empty(R, 3, device=dev)
-    mask = _empty(R, device=dev)
-    rest = (L.ptr(ids), ids.numel(), R, L.ptr(_f32c(u)), L.ptr(c2w_adjusted), L.ptr(origins), L.ptr(directions),
-            L.ptr(cam), L.ptr(image), L.ptr(mask), L.stream_ptr(dev))
-    if cams is None:
-        L.check(lib.fnr_sample_pixels(C.byref(image_set.c), *rest), "sample_pixels")
-    else:
-        L.check(lib.fnr_sample_pixels_cams(C.byref(image_set.c), cams.ref(image_set), *rest), "sample_pixels_cams")
-    return origins, directions, cam, image, mask
+    out = _ray_outputs(R, dev)
+    call(C.byref(image_set.c), *options, L.ptr(ids), ids.numel(), R, L.ptr(_f32c(u)), L.ptr(c2w_adjusted), *map(L.ptr, out.values()),
+         L.stream_ptr(dev))
+    return tuple(out.values())
 
 
 def camera_rays(c2w: Tensor, intrinsics_row: Tensor, distortion_row: Optional[Tensor], H: int, W: int, y0: int = 0,

@@ -1,9 +1,14 @@
 // camera_math.hpp — SO3xR3 and SE3 exponential maps and pose composition shared by camera_opt.hip (k_camera_adjust,
 // k_camera_pose_grad) and pixel_sampler.hip (fnr_train_prologue computes a ray's corrected camera in place).
 // nerfstudio 0.3.2 CameraOptimizer(mode="SO3xR3" | "SE3") semantics, see camera_opt.hip.
-// pixel_direction: a pixel's camera-frame direction through a per-image camera table (fnr_camera_table: intrinsics +
-// OpenCV distortion), shared by every kernel of the _cams entry points.
+// pixel -> ray, one function per step, for k_sample_pixels, k_train_prologue, k_camera_rays and the recompute in
+// k_camera_pose_grad: pick_pixel (u -> clamped slot, row, column), pixel_direction / camera_direction (camera-frame direction
+// through a camera-table row — intrinsics + OpenCV distortion — or the set-wide pinhole, a table row without distortion),
+// world_ray (origin + unit direction), gather_target (rgb / 255 and mask).  A change to ray generation is made here, once.
+// Host side, at the end: CameraCall, the one argument block of the family's entry points, its validator and kernel selection.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace fnr {
@@ -193,6 +198,114 @@ __device__ __forceinline__ void pixel_direction(const float* __restrict__ K, con
   float yu = fdiv(fsub(fadd((float)y, 0.5f), K[3]), K[1]);
   if (D) undistort_opencv(D, xu, yu, xu, yu);
   dc[0] = xu, dc[1] = -yu, dc[2] = -1.0f;
+}
+
+// ---- pixel -> ray: the ONE copy of each step, for every kernel that makes a ray or makes it again -----------------------------
+struct PixelGrid {
+  int H, W;
+  float fx, fy, cx, cy;  // the set-wide pinhole (kernels without a camera table)
+};
+
+struct ImageSetDev {
+  int n_images;
+  PixelGrid grid;         // (all that k_camera_pose_grad takes of the set, next to its cameras)
+  const uint8_t* images;  // [M,H,W,3]
+  const uint8_t* masks;   // [M,H,W]
+  const float* c2w;       // [M,3,4]
+};
+
+struct Pixel {
+  int k, y, x;  // training slot (camera index = appearance-embedding row), pixel row, pixel column
+};
+
+// indices = floor(rand * [n_train, H, W]) (PixelSampler.sample_method), clamped like the torch mirror
+__device__ __forceinline__ Pixel pick_pixel(const float* __restrict__ u, int n_train, int H, int W) {
+  Pixel p{(int)(u[0] * (float)n_train), (int)(u[1] * (float)H), (int)(u[2] * (float)W)};
+  p.k = min(p.k, n_train - 1);
+  p.y = min(p.y, H - 1);
+  p.x = min(p.x, W - 1);
+  return p;
+}
+
+// pixel_direction of dataset image `img`: through its camera-table row (CAMS) or the set-wide pinhole
+template <bool CAMS>
+__device__ __forceinline__ void camera_direction(const PixelGrid& g, const CameraTableDev& cams, long long img, int x, int y,
+                                                 float (&dc)[3]) {
+  if constexpr (CAMS) {
+    pixel_direction(cams.intrinsics + 4 * img, cams.distortion ? cams.distortion + 6 * img : nullptr, x, y, dc);
+  } else {
+    const float K[4] = {g.fx, g.fy, g.cx, g.cy};
+    pixel_direction(K, nullptr, x, y, dc);
+  }
+}
+
+// camera M [3,4] and camera-frame direction dc -> origin = the translation column, direction = normalize(R dc)
+__device__ __forceinline__ void world_ray(const float* __restrict__ M, const float (&dc)[3], float* __restrict__ origin,
+                                          float* __restrict__ direction) {
+  float d[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    d[a] = fadd(fadd(fmul(M[4 * a], dc[0]), fmul(M[4 * a + 1], dc[1])), fmul(M[4 * a + 2], dc[2]));
+  const float nrm = fmaxf(sqrtf(fadd(fadd(fmul(d[0], d[0]), fmul(d[1], d[1])), fmul(d[2], d[2]))), 1e-12f);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    direction[a] = fdiv(d[a], nrm);
+    origin[a] = M[4 * a + 3];
+  }
+}
+
+// the training targets of pixel (y, x) of dataset image `img`: rgb / 255 and the fruit mask
+__device__ __forceinline__ void gather_target(const ImageSetDev& s, long long img, int y, int x, float* __restrict__ rgb,
+                                              float* __restrict__ mask) {
+  const size_t pix = ((size_t)img * s.grid.H + y) * s.grid.W + x;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) rgb[c] = fdiv((float)s.images[3 * pix + c], 255.0f);
+  *mask = (float)s.masks[pix];
+}
+
+// ---- host side: one argument block for the family (fnr_sample_pixels*, fnr_train_prologue*, fnr_camera_adjust*,
+// fnr_camera_pose_grad*, fnr_camera_pose_grad_adam*).  An entry point fills it with what every call shares, puts the
+// operation's own pointers in the operation's struct next to it, and calls the operation; the kernels keep their parameters.
+struct CameraCall {
+  const char* name;        // the entry point that was called: what a step program lists for the recorded call
+  ImageSetDev set;         // by value, as the kernels take them: a recorded call outlives the caller's structs
+  CameraTableDev cams;     // (NULL rows unless use_cams)
+  bool has_set, has_cams;  // the caller's pointers were not NULL
+  bool use_cams;           // rays go through the table (a _cams entry point, or a _mode / _edges one given a table)
+  int pose_mode;
+  const long long* train_ids;
+  int n_train;
+  long long n_rays;
+  void* stream;
+};
+
+static inline CameraCall camera_call(const char* name, const fnr_image_set* s, const fnr_camera_table* cams, bool use_cams,
+                                     int pose_mode, const int64_t* train_ids, int n_train, int64_t n_rays, void* stream) {
+  return {name, s ? ImageSetDev{s->n_images, {s->H, s->W, s->fx, s->fy, s->cx, s->cy}, s->images, s->masks, s->c2w} : ImageSetDev{},
+          use_cams && cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{}, s != nullptr, cams != nullptr,
+          use_cams, pose_mode, reinterpret_cast<const long long*>(train_ids), n_train, n_rays, stream};
+}
+
+// The checks every operation starts with, in this order.  op: the operation, as its messages name it;  own: its own pointers
+// are all there;  images: it reads the set's images and masks, not only its cameras.
+static inline int check_camera_call(const CameraCall& c, const char* op, bool own, bool images) {
+  const ImageSetDev& s = c.set;
+  FNR_CHECK_ARG(c.pose_mode == FNR_POSE_SO3XR3 || c.pose_mode == FNR_POSE_SE3, "%s: pose_mode %d (0 = SO3xR3, 1 = SE3)", op,
+                c.pose_mode);
+  FNR_CHECK_ARG(!c.use_cams || (c.has_cams && c.cams.intrinsics), "%s_cams: null camera table", op);
+  FNR_CHECK_ARG(c.has_set && c.train_ids && own && (images || (s.c2w && c.n_train > 0)), "%s: null argument", op);
+  FNR_CHECK_ARG(!images || (s.images && s.masks && s.c2w && s.n_images > 0 && s.grid.H > 0 && s.grid.W > 0 && c.n_train > 0),
+                "%s: bad image set", op);
+  return FNR_OK;
+}
+
+// The call's kernel: pick(cams, mode) names it, with decltype(cams)::value = CAMS and decltype(mode)::value = MODE.
+template <class Pick>
+static inline auto camera_kernel(const CameraCall& c, Pick pick) {
+  using SO3xR3 = std::integral_constant<int, FNR_POSE_SO3XR3>;
+  using SE3 = std::integral_constant<int, FNR_POSE_SE3>;
+  if (c.pose_mode == FNR_POSE_SE3) return c.use_cams ? pick(std::true_type{}, SE3{}) : pick(std::false_type{}, SE3{});
+  return c.use_cams ? pick(std::true_type{}, SO3xR3{}) : pick(std::false_type{}, SO3xR3{});
 }
 
 }  // namespace fnr

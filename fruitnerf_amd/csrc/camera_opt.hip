@@ -32,20 +32,15 @@ __global__ __launch_bounds__(64) void k_camera_adjust(const float* __restrict__ 
 
 constexpr int CPG_ROUND = 4096;   // rays a pose-gradient workgroup compacts at a time (16 per thread: one round per batch)
 
-struct PinholeDev {
-  int H, W;
-  float fx, fy, cx, cy;
-};
-
 // pose_grad[k] += d(loss)/d(tangent[k]) from the ray gradients of camera k's rays.  ADAM (single process): the
 // camera's workgroup then takes the optimiser step of its 6 pose parameters itself (the gradient it has just finished
 // + whatever pose_grad held) and leaves pose_grad zero — fnr_camera_pose_grad + fnr_adam_step / fnr_radam_step with
 // zero_grad, one launch less per step.
-// CAMS: the rays' camera-frame directions are recomputed through the camera table (pixel_direction) instead of the pinhole;
-// they do not depend on the pose, so the gradient formulas are the same.
+// CAMS: the rays' camera-frame directions are recomputed through the camera's table row instead of the set's pinhole (one
+// pixel_direction call either way); they do not depend on the pose, so the gradient formulas are the same.
 // MODE: the single-thread tail maps dL/dR', dL/dt' to the six tangent components of that exponential map.
 template <bool ADAM, bool CAMS, int MODE>
-__global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, CameraTableDev cams, const float* __restrict__ c2w,
+__global__ __launch_bounds__(256) void k_camera_pose_grad(PixelGrid grid, CameraTableDev cams, const float* __restrict__ c2w,
                                                           const long long* __restrict__ train_ids, long long n_rays,
                                                           const float* __restrict__ u, const int* __restrict__ cam_idx,
                                                           const float* __restrict__ pose,
@@ -65,7 +60,7 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, Camera
   // memory round trips (~1.5 us each), and these were four more of them at its end
   float Mk[12], wk[3], g_old[6], Pk[6], Mm[6], Vk[6];
   float tvk[6];         // SE3: the whole tangent row (the translation's gradient needs v and w)
-  float Kk[4], Dk[6];   // CAMS: the camera's intrinsics and distortion rows
+  float Kk[4], Dk[6];   // the camera's intrinsics row (CAMS: of the table, else the set's pinhole) and distortion row
   const bool distorted = CAMS && cams.distortion != nullptr;
   {
     const float* Msrc = c2w + train_ids[k] * 12;
@@ -74,6 +69,8 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, Camera
       for (int i = 0; i < 4; ++i) Kk[i] = cams.intrinsics[train_ids[k] * 4 + i];
 #pragma unroll
       for (int i = 0; i < 6; ++i) Dk[i] = distorted ? cams.distortion[train_ids[k] * 6 + i] : 0.0f;
+    } else {
+      Kk[0] = grid.fx, Kk[1] = grid.fy, Kk[2] = grid.cx, Kk[3] = grid.cy;
     }
 #pragma unroll
     for (int i = 0; i < 12; ++i) Mk[i] = Msrc[i];
@@ -128,16 +125,9 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, Camera
     __syncthreads();
     for (int i = threadIdx.x; i < total; i += 256) {
       const long long r = base0 + s_list[i];
-      int y = (int)(u[3 * r + 1] * (float)cam.H);
-      int x = (int)(u[3 * r + 2] * (float)cam.W);
-      y = min(y, cam.H - 1);
-      x = min(x, cam.W - 1);
+      const Pixel p = pick_pixel(u + 3 * r, (int)gridDim.x, grid.H, grid.W);  // (its slot is known: cam_idx[r] = k)
       float dc[3];
-      if constexpr (CAMS) {
-        pixel_direction(Kk, distorted ? Dk : nullptr, x, y, dc);
-      } else {
-        dc[0] = ((float)x + 0.5f - cam.cx) / cam.fx, dc[1] = -(((float)y + 0.5f - cam.cy) / cam.fy), dc[2] = -1.0f;
-      }
+      pixel_direction(Kk, distorted ? Dk : nullptr, p.x, p.y, dc);
       float v[3];
 #pragma unroll
       for (int a = 0; a < 3; ++a) v[a] = Ma[4 * a] * dc[0] + Ma[4 * a + 1] * dc[1] + Ma[4 * a + 2] * dc[2];
@@ -235,16 +225,18 @@ __global__ __launch_bounds__(256) void k_camera_pose_grad(PinholeDev cam, Camera
 
 using namespace fnr;
 
-static bool pose_mode_ok(int pose_mode) { return pose_mode == FNR_POSE_SO3XR3 || pose_mode == FNR_POSE_SE3; }
-
+// fnr_camera_adjust*: the block's set carries the cameras alone
 static int camera_adjust(const char* name, const float* c2w, const int64_t* train_ids, int n_train,
                          const float* pose_adjustment, int pose_mode, float* c2w_adjusted, void* stream) {
-  FNR_SEQ_UNRECORDABLE(name);
-  FNR_CHECK_ARG(pose_mode_ok(pose_mode), "camera_adjust: pose_mode %d (0 = SO3xR3, 1 = SE3)", pose_mode);
-  FNR_CHECK_ARG(c2w && train_ids && pose_adjustment && c2w_adjusted && n_train > 0, "camera_adjust: null argument");
-  const auto kernel = pose_mode == FNR_POSE_SE3 ? k_camera_adjust<FNR_POSE_SE3> : k_camera_adjust<FNR_POSE_SO3XR3>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_train + 63) / 64)), dim3(64), 0, as_stream(stream), c2w,
-                     reinterpret_cast<const long long*>(train_ids), n_train, pose_adjustment, c2w_adjusted);
+  fnr_image_set set{};
+  set.c2w = c2w;
+  const CameraCall c = camera_call(name, &set, nullptr, false, pose_mode, train_ids, n_train, 0, stream);
+  FNR_SEQ_UNRECORDABLE(c.name);
+  const int rc = check_camera_call(c, "camera_adjust", pose_adjustment && c2w_adjusted, false);
+  if (rc) return rc;
+  const auto kernel = camera_kernel(c, [](auto, auto mode) { return k_camera_adjust<decltype(mode)::value>; });
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_train + 63) / 64)), dim3(64), 0, as_stream(stream), c2w, c.train_ids, n_train,
+                     pose_adjustment, c2w_adjusted);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -259,28 +251,47 @@ extern "C" int fnr_camera_adjust_mode(const float* c2w, const int64_t* train_ids
   return camera_adjust("fnr_camera_adjust_mode", c2w, train_ids, n_train, pose_adjustment, pose_mode, c2w_adjusted, stream);
 }
 
-template <bool ADAM>
-static auto pose_grad_kernel(bool use_cams, int pose_mode) {
-  if (pose_mode == FNR_POSE_SE3) return use_cams ? k_camera_pose_grad<ADAM, true, FNR_POSE_SE3> : k_camera_pose_grad<ADAM, false, FNR_POSE_SE3>;
-  return use_cams ? k_camera_pose_grad<ADAM, true, FNR_POSE_SO3XR3> : k_camera_pose_grad<ADAM, false, FNR_POSE_SO3XR3>;
-}
+// The pose gradient's own pointers.  pose_adjustment: the plain form's; the fused form (ADAM) reads the table it steps,
+// adam->params.
+struct PoseGradArgs {
+  const float* u;
+  const int32_t* camera_indices;
+  const float *pose_adjustment, *c2w_adjusted, *d_origins, *d_directions;
+  float* pose_grad;
+};
 
-static int camera_pose_grad(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
-                            int pose_mode, const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
-                            const int32_t* camera_indices, const float* pose_adjustment, const float* c2w_adjusted,
-                            const float* d_origins, const float* d_directions, float* pose_grad, void* stream) {
-  FNR_SEQ_UNRECORDABLE(name);
-  FNR_CHECK_ARG(pose_mode_ok(pose_mode), "camera_pose_grad: pose_mode %d (0 = SO3xR3, 1 = SE3)", pose_mode);
-  FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "camera_pose_grad_cams: null camera table");
-  FNR_CHECK_ARG(set && set->c2w && train_ids && u && camera_indices && pose_adjustment && c2w_adjusted && d_origins &&
-                    d_directions && pose_grad && n_train > 0,
-                "camera_pose_grad: null argument");
-  if (n_rays == 0) return FNR_OK;
-  PinholeDev cam{set->H, set->W, set->fx, set->fy, set->cx, set->cy};
-  const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
-  hipLaunchKernelGGL(pose_grad_kernel<false>(use_cams, pose_mode), dim3((unsigned)n_train), dim3(256), 0, as_stream(stream),
-                     cam, t, set->c2w, reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices,
-                     pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, TableAdam{});
+// ADAM: fnr_camera_pose_grad_adam*, the one form of the family a step program records besides the prologue — replayed from
+// the block, `a` and a copy of the optimiser struct with the step's lr / step patched in.
+template <bool ADAM>
+static int camera_pose_grad(const CameraCall& c, PoseGradArgs a, const fnr_table_adam* adam = nullptr) {
+  if constexpr (ADAM) {
+    if (seq::recording() && c.has_set && adam && (!c.use_cams || c.has_cams)) {
+      const fnr_table_adam adam_ = *adam;
+      seq::push(c.name, [=](const fnr_step_scalars* sc) {
+        const fnr_table_adam patched = seq::patched(adam_, sc);
+        return camera_pose_grad<true>(c, a, &patched);
+      });
+    }
+  } else {
+    FNR_SEQ_UNRECORDABLE(c.name);
+  }
+  const bool own = a.u && a.camera_indices && (ADAM ? adam != nullptr : a.pose_adjustment != nullptr) && a.c2w_adjusted &&
+                   a.d_origins && a.d_directions && a.pose_grad;
+  int rc = check_camera_call(c, ADAM ? "camera_pose_grad_adam" : "camera_pose_grad", own, false);
+  if (rc) return rc;
+  TableAdam t{};
+  if constexpr (ADAM) {
+    if ((rc = make_table_adam(adam, t))) return rc;
+    a.pose_adjustment = adam->params;
+  } else if (c.n_rays == 0) {
+    return FNR_OK;  // (the fused form still takes the step: every pose parameter decays its moments)
+  }
+  const auto kernel = camera_kernel(c, [](auto cams, auto mode) {
+    return k_camera_pose_grad<ADAM, decltype(cams)::value, decltype(mode)::value>;
+  });
+  hipLaunchKernelGGL(kernel, dim3((unsigned)c.n_train), dim3(256), 0, as_stream(c.stream), c.set.grid, c.cams, c.set.c2w,
+                     c.train_ids, c.n_rays, a.u, a.camera_indices, a.pose_adjustment, a.c2w_adjusted, a.d_origins, a.d_directions,
+                     a.pose_grad, t);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -289,82 +300,53 @@ extern "C" int fnr_camera_pose_grad(const fnr_image_set* set, const int64_t* tra
                                     const float* u, const int32_t* camera_indices, const float* pose_adjustment,
                                     const float* c2w_adjusted, const float* d_origins, const float* d_directions,
                                     float* pose_grad, void* stream) {
-  return camera_pose_grad("fnr_camera_pose_grad", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, u,
-                          camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
+  return camera_pose_grad<false>(camera_call("fnr_camera_pose_grad", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train,
+                                             n_rays, stream),
+                                 {u, camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad});
 }
 
 extern "C" int fnr_camera_pose_grad_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
                                          int n_train, int64_t n_rays, const float* u, const int32_t* camera_indices,
                                          const float* pose_adjustment, const float* c2w_adjusted, const float* d_origins,
                                          const float* d_directions, float* pose_grad, void* stream) {
-  return camera_pose_grad("fnr_camera_pose_grad_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, u,
-                          camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
+  return camera_pose_grad<false>(camera_call("fnr_camera_pose_grad_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train,
+                                             n_rays, stream),
+                                 {u, camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad});
 }
 
 extern "C" int fnr_camera_pose_grad_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
                                          const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
-                                         const int32_t* camera_indices, const float* pose_adjustment,
-                                         const float* c2w_adjusted, const float* d_origins, const float* d_directions,
-                                         float* pose_grad, void* stream) {
-  return camera_pose_grad("fnr_camera_pose_grad_mode", set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, u,
-                          camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad, stream);
-}
-
-// name: the entry point that was called, which is what a step program lists for the recorded call
-static int camera_pose_grad_adam(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
-                                 int pose_mode, const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
-                                 const int32_t* camera_indices, const float* c2w_adjusted, const float* d_origins,
-                                 const float* d_directions, float* pose_grad, const fnr_table_adam* adam, void* stream) {
-  if (seq::recording() && set && adam && (!use_cams || cams)) {
-    const fnr_image_set set_ = *set;
-    const fnr_camera_table cams_ = use_cams ? *cams : fnr_camera_table{nullptr, nullptr};
-    const fnr_table_adam adam_ = *adam;
-    seq::push(name, [=](const fnr_step_scalars* sc) {
-      const fnr_table_adam a = seq::patched(adam_, sc);
-      return camera_pose_grad_adam(name, &set_, &cams_, use_cams, pose_mode, train_ids, n_train, n_rays, u, camera_indices,
-                                   c2w_adjusted, d_origins, d_directions, pose_grad, &a, stream);
-    });
-  }
-  FNR_CHECK_ARG(pose_mode_ok(pose_mode), "camera_pose_grad_adam: pose_mode %d (0 = SO3xR3, 1 = SE3)", pose_mode);
-  FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "camera_pose_grad_adam_cams: null camera table");
-  FNR_CHECK_ARG(set && set->c2w && train_ids && u && camera_indices && c2w_adjusted && d_origins && d_directions &&
-                    pose_grad && adam && n_train > 0,
-                "camera_pose_grad_adam: null argument");
-  TableAdam t;
-  const int rc = make_table_adam(adam, t);
-  if (rc) return rc;
-  PinholeDev cam{set->H, set->W, set->fx, set->fy, set->cx, set->cy};
-  const CameraTableDev ct = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
-  // n_rays == 0 still takes the step (every pose parameter decays its moments)
-  hipLaunchKernelGGL(pose_grad_kernel<true>(use_cams, pose_mode), dim3((unsigned)n_train), dim3(256), 0, as_stream(stream),
-                     cam, ct, set->c2w, reinterpret_cast<const long long*>(train_ids), (long long)n_rays, u, camera_indices,
-                     adam->params, c2w_adjusted, d_origins, d_directions, pose_grad, t);
-  FNR_LAUNCH_CHECK();
-  return FNR_OK;
+                                         const int32_t* camera_indices, const float* pose_adjustment, const float* c2w_adjusted,
+                                         const float* d_origins, const float* d_directions, float* pose_grad, void* stream) {
+  return camera_pose_grad<false>(camera_call("fnr_camera_pose_grad_mode", set, cams, cams != nullptr, pose_mode, train_ids,
+                                             n_train, n_rays, stream),
+                                 {u, camera_indices, pose_adjustment, c2w_adjusted, d_origins, d_directions, pose_grad});
 }
 
 extern "C" int fnr_camera_pose_grad_adam(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
                                          const float* u, const int32_t* camera_indices, const float* c2w_adjusted,
                                          const float* d_origins, const float* d_directions, float* pose_grad,
                                          const fnr_table_adam* adam, void* stream) {
-  return camera_pose_grad_adam("fnr_camera_pose_grad_adam", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays,
-                               u, camera_indices, c2w_adjusted, d_origins, d_directions, pose_grad, adam, stream);
+  return camera_pose_grad<true>(camera_call("fnr_camera_pose_grad_adam", set, nullptr, false, FNR_POSE_SO3XR3, train_ids,
+                                            n_train, n_rays, stream),
+                                {u, camera_indices, nullptr, c2w_adjusted, d_origins, d_directions, pose_grad}, adam);
 }
 
-extern "C" int fnr_camera_pose_grad_adam_cams(const fnr_image_set* set, const fnr_camera_table* cams,
-                                              const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
-                                              const int32_t* camera_indices, const float* c2w_adjusted,
-                                              const float* d_origins, const float* d_directions, float* pose_grad,
-                                              const fnr_table_adam* adam, void* stream) {
-  return camera_pose_grad_adam("fnr_camera_pose_grad_adam_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train,
-                               n_rays, u, camera_indices, c2w_adjusted, d_origins, d_directions, pose_grad, adam, stream);
+extern "C" int fnr_camera_pose_grad_adam_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
+                                              int n_train, int64_t n_rays, const float* u, const int32_t* camera_indices,
+                                              const float* c2w_adjusted, const float* d_origins, const float* d_directions,
+                                              float* pose_grad, const fnr_table_adam* adam, void* stream) {
+  return camera_pose_grad<true>(camera_call("fnr_camera_pose_grad_adam_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids,
+                                            n_train, n_rays, stream),
+                                {u, camera_indices, nullptr, c2w_adjusted, d_origins, d_directions, pose_grad}, adam);
 }
 
 extern "C" int fnr_camera_pose_grad_adam_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
                                               const int64_t* train_ids, int n_train, int64_t n_rays, const float* u,
-                                              const int32_t* camera_indices, const float* c2w_adjusted,
-                                              const float* d_origins, const float* d_directions, float* pose_grad,
-                                              const fnr_table_adam* adam, void* stream) {
-  return camera_pose_grad_adam("fnr_camera_pose_grad_adam_mode", set, cams, cams != nullptr, pose_mode, train_ids, n_train,
-                               n_rays, u, camera_indices, c2w_adjusted, d_origins, d_directions, pose_grad, adam, stream);
+                                              const int32_t* camera_indices, const float* c2w_adjusted, const float* d_origins,
+                                              const float* d_directions, float* pose_grad, const fnr_table_adam* adam,
+                                              void* stream) {
+  return camera_pose_grad<true>(camera_call("fnr_camera_pose_grad_adam_mode", set, cams, cams != nullptr, pose_mode, train_ids,
+                                            n_train, n_rays, stream),
+                                {u, camera_indices, nullptr, c2w_adjusted, d_origins, d_directions, pose_grad}, adam);
 }

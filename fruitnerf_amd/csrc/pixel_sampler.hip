@@ -10,16 +10,8 @@
 
 namespace fnr {
 
-struct ImageSetDev {
-  int n_images, H, W;
-  const uint8_t* images;  // [M,H,W,3]
-  const uint8_t* masks;   // [M,H,W]
-  const float* c2w;       // [M,3,4]
-  float fx, fy, cx, cy;
-};
-
-// CAMS: the camera-frame direction comes from the per-image camera table (camera_math.hpp::pixel_direction) instead of
-// the set-wide pinhole; everything after it is the same code.
+// CAMS: the camera-frame direction comes from the per-image camera table instead of the set-wide pinhole
+// (camera_math.hpp::camera_direction); everything else is the same code.
 template <bool CAMS>
 __global__ __launch_bounds__(256) void k_sample_pixels(ImageSetDev s, CameraTableDev cams,
                                                        const long long* __restrict__ train_ids,
@@ -30,40 +22,15 @@ __global__ __launch_bounds__(256) void k_sample_pixels(ImageSetDev s, CameraTabl
                                                        float* __restrict__ mask) {
   const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
   if (r >= n_rays) return;
-  // indices = floor(rand * [n_train, H, W]) (PixelSampler.sample_method), clamped like the torch mirror
-  int k = (int)(u[3 * r] * (float)n_train);
-  int y = (int)(u[3 * r + 1] * (float)s.H);
-  int x = (int)(u[3 * r + 2] * (float)s.W);
-  k = min(k, n_train - 1);
-  y = min(y, s.H - 1);
-  x = min(x, s.W - 1);
-  const long long img = train_ids[k];
-  float dx, dy, dz;
-  if constexpr (CAMS) {
-    float dc[3];
-    pixel_direction(cams.intrinsics + 4 * img, cams.distortion ? cams.distortion + 6 * img : nullptr, x, y, dc);
-    dx = dc[0], dy = dc[1], dz = dc[2];
-  } else {
-    dx = fdiv(fsub(fadd((float)x, 0.5f), s.cx), s.fx);
-    dy = -fdiv(fsub(fadd((float)y, 0.5f), s.cy), s.fy);
-    dz = -1.0f;
-  }
+  const Pixel p = pick_pixel(u + 3 * r, n_train, s.grid.H, s.grid.W);
+  const long long img = train_ids[p.k];
+  float dc[3];
+  camera_direction<CAMS>(s.grid, cams, img, p.x, p.y, dc);
   // camera-pose optimisation: the slot's corrected camera (fnr_camera_adjust) replaces the dataset's
-  const float* M = c2w_adjusted ? c2w_adjusted + (size_t)k * 12 : s.c2w + img * 12;
-  float d[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) d[a] = fadd(fadd(fmul(M[4 * a], dx), fmul(M[4 * a + 1], dy)), fmul(M[4 * a + 2], dz));
-  const float nrm = fmaxf(sqrtf(fadd(fadd(fmul(d[0], d[0]), fmul(d[1], d[1])), fmul(d[2], d[2]))), 1e-12f);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    directions[3 * r + a] = fdiv(d[a], nrm);
-    origins[3 * r + a] = M[4 * a + 3];
-  }
-  cam_idx[r] = k;  // camera index = position in the training set (appearance-embedding row)
-  const size_t pix = ((size_t)img * s.H + y) * s.W + x;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) image[3 * r + c] = fdiv((float)s.images[3 * pix + c], 255.0f);
-  mask[r] = (float)s.masks[pix];
+  const float* M = c2w_adjusted ? c2w_adjusted + (size_t)p.k * 12 : s.c2w + img * 12;
+  world_ray(M, dc, origins + 3 * r, directions + 3 * r);
+  cam_idx[r] = p.k;  // camera index = position in the training set (appearance-embedding row)
+  gather_target(s, img, p.y, p.x, image + 3 * r, mask + r);
 }
 
 // ---- the start of a training step in ONE launch (fnr_train_prologue) ---------------------------------------------------
@@ -85,11 +52,8 @@ __global__ __launch_bounds__(256) void k_random_background(unsigned long long se
   for (int c = 0; c < 3; ++c) out[3 * r + c] = w[c];
 }
 
+// The prologue's own arguments, as an entry point fills them, then what train_prologue() adds from the call's CameraCall.
 struct PrologueArgs {
-  ImageSetDev set;
-  const long long* train_ids;
-  int n_train;
-  long long n_rays;
   unsigned long long seed, offset;
   const float* pose;        // [n_train, 6] tangents of the kernel's MODE, or NULL (cameras as they are)
   float* c2w_adjusted;      // [n_train, 3, 4] out (with pose)
@@ -102,6 +66,10 @@ struct PrologueArgs {
   int kind, S0;
   const float* base_bins;   // [S0 + 1]
   float *spacing0, *euclid0;   // [R, S0 + 1] out
+  ImageSetDev set;
+  const long long* train_ids;
+  int n_train;
+  long long n_rays;
   int nb_rays;              // workgroups of the per-ray role
 };
 
@@ -127,45 +95,21 @@ __global__ __launch_bounds__(256) void k_train_prologue(PrologueArgs a, CameraTa
     for (int i = 0; i < 3; ++i) a.u[3 * r + i] = rnd[i];
     if constexpr (!EDGES)
       for (int i = 0; i < a.n_jitter; ++i) a.jitter[(size_t)i * a.n_rays + r] = rnd[3 + i];
-    // pixel sampling + ray generation: k_sample_pixels, with the ray's corrected camera formed in place
-    int k = (int)(rnd[0] * (float)a.n_train);
-    int y = (int)(rnd[1] * (float)a.set.H);
-    int x = (int)(rnd[2] * (float)a.set.W);
-    k = min(k, a.n_train - 1);
-    y = min(y, a.set.H - 1);
-    x = min(x, a.set.W - 1);
-    const long long img = a.train_ids[k];
-    float dx, dy, dz;
-    if constexpr (CAMS) {
-      float dc[3];
-      pixel_direction(cams.intrinsics + 4 * img, cams.distortion ? cams.distortion + 6 * img : nullptr, x, y, dc);
-      dx = dc[0], dy = dc[1], dz = dc[2];
-    } else {
-      dx = fdiv(fsub(fadd((float)x, 0.5f), a.set.cx), a.set.fx);
-      dy = -fdiv(fsub(fadd((float)y, 0.5f), a.set.cy), a.set.fy);
-      dz = -1.0f;
-    }
+    // pixel sampling + ray generation: what k_sample_pixels does, with the ray's corrected camera formed in place
+    const Pixel p = pick_pixel(rnd, a.n_train, a.set.grid.H, a.set.grid.W);
+    const long long img = a.train_ids[p.k];
+    float dc[3];
+    camera_direction<CAMS>(a.set.grid, cams, img, p.x, p.y, dc);
     float M[12];
     if (a.pose) {
-      adjusted_camera<MODE>(a.set.c2w + img * 12, a.pose + 6 * k, M);
+      adjusted_camera<MODE>(a.set.c2w + img * 12, a.pose + 6 * p.k, M);
     } else {
 #pragma unroll
       for (int i = 0; i < 12; ++i) M[i] = a.set.c2w[img * 12 + i];
     }
-    float d[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) d[q] = fadd(fadd(fmul(M[4 * q], dx), fmul(M[4 * q + 1], dy)), fmul(M[4 * q + 2], dz));
-    const float nrm = fmaxf(sqrtf(fadd(fadd(fmul(d[0], d[0]), fmul(d[1], d[1])), fmul(d[2], d[2]))), 1e-12f);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      a.directions[3 * r + q] = fdiv(d[q], nrm);
-      a.origins[3 * r + q] = M[4 * q + 3];
-    }
-    a.cam_idx[r] = k;
-    const size_t pix = ((size_t)img * a.set.H + y) * a.set.W + x;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a.image[3 * r + c] = fdiv((float)a.set.images[3 * pix + c], 255.0f);
-    a.mask[r] = (float)a.set.masks[pix];
+    world_ray(M, dc, a.origins + 3 * r, a.directions + 3 * r);
+    a.cam_idx[r] = p.k;
+    gather_target(a.set, img, p.y, p.x, a.image + 3 * r, a.mask + r);
     return;
   }
   if constexpr (EDGES) {
@@ -219,7 +163,7 @@ __global__ __launch_bounds__(256) void k_edge_jitter(unsigned long long seed, un
 }
 
 // ---- full-image rays of ONE camera (fnr_camera_rays): rows [y0, y1) of its H x W pixels, one thread per pixel ----------
-// Same arithmetic as k_sample_pixels<true> on the `u` that selects the pixel (tests/test_gpu_camera_models.py).
+// The functions of k_sample_pixels<true> on the pixel itself instead of the `u` that selects it.
 __global__ __launch_bounds__(256) void k_camera_rays(const float* __restrict__ c2w, const float* __restrict__ K,
                                                      const float* __restrict__ D, int W, int y0, long long n_pix,
                                                      float* __restrict__ origins, float* __restrict__ directions) {
@@ -229,41 +173,31 @@ __global__ __launch_bounds__(256) void k_camera_rays(const float* __restrict__ c
   const int x = (int)(r - (long long)row * W), y = y0 + row;
   float dc[3];
   pixel_direction(K, D, x, y, dc);
-  const float* M = c2w;
-  float d[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-    d[a] = fadd(fadd(fmul(M[4 * a], dc[0]), fmul(M[4 * a + 1], dc[1])), fmul(M[4 * a + 2], dc[2]));
-  const float nrm = fmaxf(sqrtf(fadd(fadd(fmul(d[0], d[0]), fmul(d[1], d[1])), fmul(d[2], d[2]))), 1e-12f);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    directions[3 * r + a] = fdiv(d[a], nrm);
-    origins[3 * r + a] = M[4 * a + 3];
-  }
+  world_ray(c2w, dc, origins + 3 * r, directions + 3 * r);
 }
 
 }  // namespace fnr
 
 using namespace fnr;
 
-// cams: NULL for the set-wide pinhole (fnr_sample_pixels), the camera table of the _cams variant otherwise
-static int sample_pixels(const char* name, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
-                         const int64_t* train_ids, int n_train, int64_t n_rays, const float* u, const float* c2w_adjusted,
-                         float* origins, float* directions, int32_t* camera_indices, float* image, float* fruit_mask,
-                         void* stream) {
-  FNR_SEQ_UNRECORDABLE(name);
-  FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "sample_pixels_cams: null camera table");
-  FNR_CHECK_ARG(set && train_ids && u && origins && directions && camera_indices && image && fruit_mask,
-                "sample_pixels: null argument");
-  FNR_CHECK_ARG(set->images && set->masks && set->c2w && set->n_images > 0 && set->H > 0 && set->W > 0 && n_train > 0,
-                "sample_pixels: bad image set");
-  if (n_rays == 0) return FNR_OK;
-  ImageSetDev s{set->n_images, set->H, set->W, set->images, set->masks, set->c2w, set->fx, set->fy, set->cx, set->cy};
-  const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
-  const auto kernel = use_cams ? k_sample_pixels<true> : k_sample_pixels<false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream), s, t,
-                     reinterpret_cast<const long long*>(train_ids), n_train, (long long)n_rays, u, c2w_adjusted, origins,
-                     directions, camera_indices, image, fruit_mask);
+// fnr_sample_pixels*'s own pointers
+struct SamplePixelsArgs {
+  const float *u, *c2w_adjusted;
+  float *origins, *directions;
+  int32_t* camera_indices;
+  float *image, *fruit_mask;
+};
+
+static int sample_pixels(const CameraCall& c, const SamplePixelsArgs& a) {
+  FNR_SEQ_UNRECORDABLE(c.name);
+  const bool own = a.u && a.origins && a.directions && a.camera_indices && a.image && a.fruit_mask;
+  const int rc = check_camera_call(c, "sample_pixels", own, true);
+  if (rc) return rc;
+  if (c.n_rays == 0) return FNR_OK;
+  const auto kernel = camera_kernel(c, [](auto cams, auto) { return k_sample_pixels<decltype(cams)::value>; });
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((c.n_rays + 255) / 256)), dim3(256), 0, as_stream(c.stream), c.set, c.cams,
+                     c.train_ids, c.n_train, c.n_rays, a.u, a.c2w_adjusted, a.origins, a.directions, a.camera_indices, a.image,
+                     a.fruit_mask);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
@@ -271,16 +205,16 @@ static int sample_pixels(const char* name, const fnr_image_set* set, const fnr_c
 extern "C" int fnr_sample_pixels(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
                                  const float* u, const float* c2w_adjusted, float* origins, float* directions,
                                  int32_t* camera_indices, float* image, float* fruit_mask, void* stream) {
-  return sample_pixels("fnr_sample_pixels", set, nullptr, false, train_ids, n_train, n_rays, u, c2w_adjusted, origins,
-                       directions, camera_indices, image, fruit_mask, stream);
+  return sample_pixels(camera_call("fnr_sample_pixels", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays,
+                                   stream), {u, c2w_adjusted, origins, directions, camera_indices, image, fruit_mask});
 }
 
 extern "C" int fnr_sample_pixels_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
-                                      int n_train, int64_t n_rays, const float* u, const float* c2w_adjusted,
-                                      float* origins, float* directions, int32_t* camera_indices, float* image,
-                                      float* fruit_mask, void* stream) {
-  return sample_pixels("fnr_sample_pixels_cams", set, cams, true, train_ids, n_train, n_rays, u, c2w_adjusted, origins,
-                       directions, camera_indices, image, fruit_mask, stream);
+                                      int n_train, int64_t n_rays, const float* u, const float* c2w_adjusted, float* origins,
+                                      float* directions, int32_t* camera_indices, float* image, float* fruit_mask,
+                                      void* stream) {
+  return sample_pixels(camera_call("fnr_sample_pixels_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train, n_rays,
+                                   stream), {u, c2w_adjusted, origins, directions, camera_indices, image, fruit_mask});
 }
 
 extern "C" int fnr_camera_rays(const float* c2w, const float* intrinsics, const float* distortion, int H, int W, int y0,
@@ -297,98 +231,78 @@ extern "C" int fnr_camera_rays(const float* c2w, const float* intrinsics, const 
   return FNR_OK;
 }
 
-// name: the entry point that was called, which is what a step program lists for the recorded call
-// edges: the per-edge form (fnr_train_prologue_edges; jitter == NULL, n_jitter == 0)
-static int train_prologue(const char* name, bool edges, const fnr_image_set* set, const fnr_camera_table* cams, bool use_cams,
-                          int pose_mode, const int64_t* train_ids,
-                          int n_train, int64_t n_rays, uint64_t seed, uint64_t offset, const float* pose_adjustment,
-                          float* c2w_adjusted, float* u, float* jitter, int n_jitter, float* origins, float* directions,
-                          int32_t* camera_indices, float* image, float* fruit_mask, float near_plane, float far_plane,
-                          int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
-                          void* stream) {
-  if (seq::recording() && set && (!use_cams || cams)) {
-    const fnr_image_set set_ = *set;
-    const fnr_camera_table cams_ = use_cams ? *cams : fnr_camera_table{nullptr, nullptr};
-    seq::push(name, [=](const fnr_step_scalars* sc) {
-      return train_prologue(name, edges, &set_, &cams_, use_cams, pose_mode, train_ids, n_train, n_rays, seed,
-                            sc ? sc->prologue_offset : offset,
-                            pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
-                            fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+// a: the entry point's part of the kernel's arguments;  edges: the per-edge form (fnr_train_prologue_edges; jitter == NULL,
+// n_jitter == 0).  A recorded call is replayed from the block and `a` with the step's offset.
+static int train_prologue(const CameraCall& c, PrologueArgs a, bool edges) {
+  if (seq::recording() && c.has_set && (!c.use_cams || c.has_cams)) {
+    seq::push(c.name, [=](const fnr_step_scalars* sc) {
+      PrologueArgs b = a;
+      if (sc) b.offset = sc->prologue_offset;
+      return train_prologue(c, b, edges);
     });
   }
-  FNR_CHECK_ARG(pose_mode == FNR_POSE_SO3XR3 || pose_mode == FNR_POSE_SE3, "train_prologue: pose_mode %d (0 = SO3xR3, 1 = SE3)",
-                pose_mode);
-  FNR_CHECK_ARG(!use_cams || (cams && cams->intrinsics), "train_prologue_cams: null camera table");
-  FNR_CHECK_ARG(set && train_ids && u && (jitter || edges) && origins && directions && camera_indices && image && fruit_mask &&
-                    base_bins && spacing0 && euclid0,
-                "train_prologue: null argument");
-  FNR_CHECK_ARG(set->images && set->masks && set->c2w && set->n_images > 0 && set->H > 0 && set->W > 0 && n_train > 0,
-                "train_prologue: bad image set");
-  FNR_CHECK_ARG(edges || (n_jitter >= 1 && n_jitter <= FNR_TRAIN_PROLOGUE_MAX_JITTER && S0 >= 1),
-                "train_prologue: n_jitter %d (1..%d), S0 %d", n_jitter, FNR_TRAIN_PROLOGUE_MAX_JITTER, S0);
+  const bool own = a.u && (a.jitter || edges) && a.origins && a.directions && a.cam_idx && a.image && a.mask && a.base_bins &&
+                   a.spacing0 && a.euclid0;
+  const int rc = check_camera_call(c, "train_prologue", own, true);
+  if (rc) return rc;
+  const int S0 = a.S0;
+  FNR_CHECK_ARG(edges || (a.n_jitter >= 1 && a.n_jitter <= FNR_TRAIN_PROLOGUE_MAX_JITTER && S0 >= 1),
+                "train_prologue: n_jitter %d (1..%d), S0 %d", a.n_jitter, FNR_TRAIN_PROLOGUE_MAX_JITTER, S0);
   FNR_CHECK_ARG(!edges || (S0 >= 1 && S0 < FNR_EDGE_JITTER_MAX_EDGES), "train_prologue_edges: S0 %d (1..%d)", S0,
                 FNR_EDGE_JITTER_MAX_EDGES - 1);
-  FNR_CHECK_ARG((pose_adjustment == nullptr) == (c2w_adjusted == nullptr), "train_prologue: pose and c2w_adjusted go together");
-  FNR_CHECK_ARG(n_rays >= n_train || !pose_adjustment, "train_prologue: fewer rays than cameras");
-  if (n_rays == 0) return FNR_OK;
-  PrologueArgs a;
-  a.set = ImageSetDev{set->n_images, set->H, set->W, set->images, set->masks, set->c2w, set->fx, set->fy, set->cx, set->cy};
-  a.train_ids = reinterpret_cast<const long long*>(train_ids);
-  a.n_train = n_train, a.n_rays = n_rays, a.seed = seed, a.offset = offset;
-  a.pose = pose_adjustment, a.c2w_adjusted = c2w_adjusted, a.u = u, a.jitter = jitter, a.n_jitter = n_jitter;
-  a.origins = origins, a.directions = directions, a.cam_idx = camera_indices, a.image = image, a.mask = fruit_mask;
-  a.near = near_plane, a.far = far_plane, a.kind = spacing_kind, a.S0 = S0, a.base_bins = base_bins;
-  a.spacing0 = spacing0, a.euclid0 = euclid0;
+  FNR_CHECK_ARG((a.pose == nullptr) == (a.c2w_adjusted == nullptr), "train_prologue: pose and c2w_adjusted go together");
+  FNR_CHECK_ARG(c.n_rays >= c.n_train || !a.pose, "train_prologue: fewer rays than cameras");
+  if (c.n_rays == 0) return FNR_OK;
+  void* const stream = c.stream;  // (FNR_PROF)
+  const long long n_rays = c.n_rays;
+  a.set = c.set, a.train_ids = c.train_ids, a.n_train = c.n_train, a.n_rays = n_rays;
   a.nb_rays = (int)((n_rays + 255) / 256);
   // (per edge: one thread per quad of edges)
   const long long nb_bins = ((edges ? n_rays * (long long)((S0 + 4) >> 2) : n_rays * (long long)(S0 + 1)) + 255) / 256;
   FNR_PROF(OP_SAMPLE_SPACED, n_rays * (long long)(S0 + 1));
-  const CameraTableDev t = use_cams ? CameraTableDev{cams->intrinsics, cams->distortion} : CameraTableDev{nullptr, nullptr};
-  const auto kernel =
-      edges ? (pose_mode == FNR_POSE_SE3
-                   ? (use_cams ? k_train_prologue<true, FNR_POSE_SE3, true> : k_train_prologue<false, FNR_POSE_SE3, true>)
-                   : (use_cams ? k_train_prologue<true, FNR_POSE_SO3XR3, true> : k_train_prologue<false, FNR_POSE_SO3XR3, true>))
-            : (pose_mode == FNR_POSE_SE3
-                   ? (use_cams ? k_train_prologue<true, FNR_POSE_SE3> : k_train_prologue<false, FNR_POSE_SE3>)
-                   : (use_cams ? k_train_prologue<true, FNR_POSE_SO3XR3> : k_train_prologue<false, FNR_POSE_SO3XR3>));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(a.nb_rays + nb_bins)), dim3(256), 0, as_stream(stream), a, t);
+  const auto kernel = camera_kernel(c, [edges](auto cams, auto mode) {
+    constexpr bool CAMS = decltype(cams)::value;
+    constexpr int MODE = decltype(mode)::value;
+    return edges ? k_train_prologue<CAMS, MODE, true> : k_train_prologue<CAMS, MODE, false>;
+  });
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(a.nb_rays + nb_bins)), dim3(256), 0, as_stream(stream), a, c.cams);
   FNR_LAUNCH_CHECK();
   return FNR_OK;
 }
 
 extern "C" int fnr_train_prologue(const fnr_image_set* set, const int64_t* train_ids, int n_train, int64_t n_rays,
-                                  uint64_t seed, uint64_t offset, const float* pose_adjustment, float* c2w_adjusted,
-                                  float* u, float* jitter, int n_jitter, float* origins, float* directions,
-                                  int32_t* camera_indices, float* image, float* fruit_mask, float near_plane,
-                                  float far_plane, int spacing_kind, int S0, const float* base_bins, float* spacing0,
-                                  float* euclid0, void* stream) {
-  return train_prologue("fnr_train_prologue", false, set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, seed, offset,
-                        pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
-                        fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+                                  uint64_t seed, uint64_t offset, const float* pose_adjustment, float* c2w_adjusted, float* u,
+                                  float* jitter, int n_jitter, float* origins, float* directions, int32_t* camera_indices,
+                                  float* image, float* fruit_mask, float near_plane, float far_plane, int spacing_kind, int S0,
+                                  const float* base_bins, float* spacing0, float* euclid0, void* stream) {
+  return train_prologue(camera_call("fnr_train_prologue", set, nullptr, false, FNR_POSE_SO3XR3, train_ids, n_train, n_rays,
+                                    stream),
+                        {seed, offset, pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices,
+                         image, fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0}, false);
 }
 
 extern "C" int fnr_train_prologue_cams(const fnr_image_set* set, const fnr_camera_table* cams, const int64_t* train_ids,
                                        int n_train, int64_t n_rays, uint64_t seed, uint64_t offset,
-                                       const float* pose_adjustment, float* c2w_adjusted, float* u, float* jitter,
-                                       int n_jitter, float* origins, float* directions, int32_t* camera_indices,
-                                       float* image, float* fruit_mask, float near_plane, float far_plane,
-                                       int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
-                                       void* stream) {
-  return train_prologue("fnr_train_prologue_cams", false, set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train, n_rays, seed, offset,
-                        pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices, image,
-                        fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+                                       const float* pose_adjustment, float* c2w_adjusted, float* u, float* jitter, int n_jitter,
+                                       float* origins, float* directions, int32_t* camera_indices, float* image,
+                                       float* fruit_mask, float near_plane, float far_plane, int spacing_kind, int S0,
+                                       const float* base_bins, float* spacing0, float* euclid0, void* stream) {
+  return train_prologue(camera_call("fnr_train_prologue_cams", set, cams, true, FNR_POSE_SO3XR3, train_ids, n_train, n_rays,
+                                    stream),
+                        {seed, offset, pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices,
+                         image, fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0}, false);
 }
 
 extern "C" int fnr_train_prologue_mode(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
                                        const int64_t* train_ids, int n_train, int64_t n_rays, uint64_t seed, uint64_t offset,
-                                       const float* pose_adjustment, float* c2w_adjusted, float* u, float* jitter,
-                                       int n_jitter, float* origins, float* directions, int32_t* camera_indices,
-                                       float* image, float* fruit_mask, float near_plane, float far_plane,
-                                       int spacing_kind, int S0, const float* base_bins, float* spacing0, float* euclid0,
-                                       void* stream) {
-  return train_prologue("fnr_train_prologue_mode", false, set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, seed,
-                        offset, pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices,
-                        image, fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+                                       const float* pose_adjustment, float* c2w_adjusted, float* u, float* jitter, int n_jitter,
+                                       float* origins, float* directions, int32_t* camera_indices, float* image,
+                                       float* fruit_mask, float near_plane, float far_plane, int spacing_kind, int S0,
+                                       const float* base_bins, float* spacing0, float* euclid0, void* stream) {
+  return train_prologue(camera_call("fnr_train_prologue_mode", set, cams, cams != nullptr, pose_mode, train_ids, n_train,
+                                    n_rays, stream),
+                        {seed, offset, pose_adjustment, c2w_adjusted, u, jitter, n_jitter, origins, directions, camera_indices,
+                         image, fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0}, false);
 }
 
 extern "C" int fnr_train_prologue_edges(const fnr_image_set* set, const fnr_camera_table* cams, int pose_mode,
@@ -397,9 +311,10 @@ extern "C" int fnr_train_prologue_edges(const fnr_image_set* set, const fnr_came
                                         float* directions, int32_t* camera_indices, float* image, float* fruit_mask,
                                         float near_plane, float far_plane, int spacing_kind, int S0, const float* base_bins,
                                         float* spacing0, float* euclid0, void* stream) {
-  return train_prologue("fnr_train_prologue_edges", true, set, cams, cams != nullptr, pose_mode, train_ids, n_train, n_rays, seed,
-                        offset, pose_adjustment, c2w_adjusted, u, nullptr, 0, origins, directions, camera_indices, image,
-                        fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0, stream);
+  return train_prologue(camera_call("fnr_train_prologue_edges", set, cams, cams != nullptr, pose_mode, train_ids, n_train,
+                                    n_rays, stream),
+                        {seed, offset, pose_adjustment, c2w_adjusted, u, nullptr, 0, origins, directions, camera_indices, image,
+                         fruit_mask, near_plane, far_plane, spacing_kind, S0, base_bins, spacing0, euclid0}, true);
 }
 
 extern "C" int fnr_edge_jitter(uint64_t seed, uint64_t offset, int level, int64_t n_rays, int n_edges, float* out,

@@ -216,6 +216,14 @@ class PixelBatcher:
             self._cams = camera_table_of(self.cameras, self.data["images"].device)
         return self._cams
 
+    def image_set(self):
+        """K.ImageSetArg over the image batch (on a HIP device), built on first use and kept as `_set`."""
+        if self._set is None:
+            from .. import _kernels as K
+            d = self.data
+            self._set = K.ImageSetArg(d["images"], d["masks"], d["c2w"], d["fx"], d["fy"], d["cx"], d["cy"])
+        return self._set
+
     def sample(self, n_rays: int, camera_optimizer=None, level0: Optional[dict] = None):
         """One fused kernel on the HIP device (fnr_sample_pixels / fnr_train_prologue); a batch on the CPU raises.
         camera_optimizer (cameras.camera_optimizers.CameraOptimizer, mode SO3xR3 or SE3): rays come from the pose-corrected
@@ -231,12 +239,10 @@ class PixelBatcher:
         dev = d["images"].device
         if level0 is not None and dev.type == "cuda":
             from .. import _kernels as K
-            if self._set is None:
-                self._set = K.ImageSetArg(d["images"], d["masks"], d["c2w"], d["fx"], d["fy"], d["cx"], d["cy"])
             pose = camera_optimizer.pose_adjustment.data if (camera_optimizer is not None and camera_optimizer.enabled) else None
             pose_mode = camera_optimizer.pose_mode if pose is not None else 0     # (without poses the mode reads nothing)
             self._offset = getattr(self, "_offset", 0) + 1
-            out = K.train_prologue(self._set, self.image_ids, n_rays, self.gen.initial_seed(), self._offset, pose,
+            out = K.train_prologue(self.image_set(), self.image_ids, n_rays, self.gen.initial_seed(), self._offset, pose,
                                    level0["near"], level0["far"], level0["S"], n_jitter=level0.get("n_jitter", 3),
                                    cams=self.camera_table(), pose_mode=pose_mode, per_edge=bool(level0.get("per_edge")))
             self.last_draw = {"u": out["u"], "cam": out["cam"], "c2w_adjusted": out["c2w_adjusted"]}
@@ -254,10 +260,9 @@ class PixelBatcher:
         u = torch.rand(n_rays, 3, device=dev, generator=self.gen)
         if dev.type == "cuda":
             from .. import _kernels as K
-            if self._set is None:
-                self._set = K.ImageSetArg(d["images"], d["masks"], d["c2w"], d["fx"], d["fy"], d["cx"], d["cy"])
-            c2w_adj = camera_optimizer.adjusted_cameras(self._set, self.image_ids) if camera_optimizer is not None else None
-            o, dirs, cam, image, mask = K.sample_pixels(self._set, self.image_ids, u, c2w_adj, cams=self.camera_table())
+            iset = self.image_set()
+            c2w_adj = camera_optimizer.adjusted_cameras(iset, self.image_ids) if camera_optimizer is not None else None
+            o, dirs, cam, image, mask = K.sample_pixels(iset, self.image_ids, u, c2w_adj, cams=self.camera_table())
             self.last_draw = {"u": u, "cam": cam, "c2w_adjusted": c2w_adj}
             self.last_presample = None
             return o, dirs, cam[:, None], {"image": image, "fruit_mask": mask[:, None]}
