@@ -286,6 +286,33 @@ static inline CameraCall camera_call(const char* name, const fnr_image_set* s, c
           use_cams, pose_mode, reinterpret_cast<const long long*>(train_ids), n_train, n_rays, stream};
 }
 
+// fnr_train_prologue*'s own arguments (pixel_sampler.hip), as an entry point fills them, then what train_prologue() adds from
+// the call's CameraCall.
+struct PrologueArgs {
+  unsigned long long seed, offset;
+  const float* pose;        // [n_train, 6] tangents of the kernel's MODE, or NULL (cameras as they are)
+  float* c2w_adjusted;      // [n_train, 3, 4] out (with pose)
+  float *u, *jitter;        // [R, 3], [n_jitter, R] out (the per-edge form writes no jitter)
+  int n_jitter;             // <= 5
+  float *origins, *directions;
+  int* cam_idx;
+  float *image, *mask;
+  float near, far;
+  int kind, S0;
+  const float* base_bins;   // [S0 + 1]
+  float *spacing0, *euclid0;   // [R, S0 + 1] out
+  ImageSetDev set;
+  const long long* train_ids;
+  int n_train;
+  long long n_rays;
+  int nb_rays;              // workgroups of the per-ray role
+};
+// replayed from a step program (sequencer.hpp): the step's random-number counter
+static inline PrologueArgs patched(PrologueArgs a, const fnr_step_scalars* s) {
+  if (s) a.offset = s->prologue_offset;
+  return a;
+}
+
 // The checks every operation starts with, in this order.  op: the operation, as its messages name it;  own: its own pointers
 // are all there;  images: it reads the set's images and masks, not only its cameras.
 static inline int check_camera_call(const CameraCall& c, const char* op, bool own, bool images) {

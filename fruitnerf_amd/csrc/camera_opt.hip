@@ -265,13 +265,7 @@ struct PoseGradArgs {
 template <bool ADAM>
 static int camera_pose_grad(const CameraCall& c, PoseGradArgs a, const fnr_table_adam* adam = nullptr) {
   if constexpr (ADAM) {
-    if (seq::recording() && c.has_set && adam && (!c.use_cams || c.has_cams)) {
-      const fnr_table_adam adam_ = *adam;
-      seq::push(c.name, [=](const fnr_step_scalars* sc) {
-        const fnr_table_adam patched = seq::patched(adam_, sc);
-        return camera_pose_grad<true>(c, a, &patched);
-      });
-    }
+    if (c.has_set && (!c.use_cams || c.has_cams)) seq::record(c.name, &camera_pose_grad<true>, c, a, adam);
   } else {
     FNR_SEQ_UNRECORDABLE(c.name);
   }

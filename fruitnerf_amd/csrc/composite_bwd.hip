@@ -279,13 +279,8 @@ extern "C" int fnr_composite_bwd_targets(const fnr_rays* rays, int S, const floa
                                          const float* rgb, const float* weights, const float* out_rgb, const float* image,
                                          const float* out_semantics, const float* mask, float semantic_loss_weight,
                                          float* d_density, float* d_rgb, float* d_logit, void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_bwd_targets", [=](const fnr_step_scalars*) {
-      return fnr_composite_bwd_targets(&rays_, S, euclid_bins, density, rgb, weights, out_rgb, image, out_semantics, mask,
-                                       semantic_loss_weight, d_density, d_rgb, d_logit, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_composite_bwd_targets, rays, S, euclid_bins, density, rgb, weights, out_rgb, image, out_semantics, mask,
+                 semantic_loss_weight, d_density, d_rgb, d_logit, stream);
   const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
   return launch_composite_bwd("composite_bwd_targets", rays, S, euclid_bins, density, rgb, nullptr, weights, nullptr, nullptr,
                               &tg, false, nullptr, d_density, d_rgb, d_logit, stream);
@@ -301,14 +296,8 @@ extern "C" int fnr_composite_fwd_bwd_targets(const fnr_rays* rays, int S, const 
                                              float* out_accumulation, float* out_depth, float* out_semantics,
                                              int64_t* out_label, float* d_density, float* d_rgb, float* d_logit,
                                              void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_fwd_bwd_targets", [=](const fnr_step_scalars*) {
-      return fnr_composite_fwd_bwd_targets(&rays_, S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights,
-                                           out_rgb, out_accumulation, out_depth, out_semantics, out_label, d_density, d_rgb,
-                                           d_logit, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_composite_fwd_bwd_targets, rays, S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight,
+                 weights, out_rgb, out_accumulation, out_depth, out_semantics, out_label, d_density, d_rgb, d_logit, stream);
   return launch_composite_fwd_bwd("composite_fwd_bwd_targets", rays, S, euclid_bins, density, rgb, logit, image, mask,
                                   semantic_loss_weight, false, nullptr, weights, out_rgb, out_accumulation, out_depth,
                                   out_semantics, out_label, d_density, d_rgb, d_logit, stream);
@@ -330,13 +319,8 @@ extern "C" int fnr_composite_bwd_targets_semgrad(const fnr_rays* rays, int S, co
                                                  const float* out_rgb, const float* image, const float* out_semantics,
                                                  const float* mask, float semantic_loss_weight, float* d_density,
                                                  float* d_rgb, float* d_logit, void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_bwd_targets_semgrad", [=](const fnr_step_scalars*) {
-      return fnr_composite_bwd_targets_semgrad(&rays_, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
-                                               out_semantics, mask, semantic_loss_weight, d_density, d_rgb, d_logit, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_composite_bwd_targets_semgrad, rays, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
+                 out_semantics, mask, semantic_loss_weight, d_density, d_rgb, d_logit, stream);
   const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
   return launch_composite_bwd("composite_bwd_targets_semgrad", rays, S, euclid_bins, density, rgb, logit, weights, nullptr,
                               nullptr, &tg, true, nullptr, d_density, d_rgb, d_logit, stream);
@@ -348,14 +332,9 @@ extern "C" int fnr_composite_fwd_bwd_targets_semgrad(const fnr_rays* rays, int S
                                                      float* weights, float* out_rgb, float* out_accumulation,
                                                      float* out_depth, float* out_semantics, int64_t* out_label,
                                                      float* d_density, float* d_rgb, float* d_logit, void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_fwd_bwd_targets_semgrad", [=](const fnr_step_scalars*) {
-      return fnr_composite_fwd_bwd_targets_semgrad(&rays_, S, euclid_bins, density, rgb, logit, image, mask,
-                                                   semantic_loss_weight, weights, out_rgb, out_accumulation, out_depth,
-                                                   out_semantics, out_label, d_density, d_rgb, d_logit, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_composite_fwd_bwd_targets_semgrad, rays, S, euclid_bins, density, rgb, logit, image, mask,
+                 semantic_loss_weight, weights, out_rgb, out_accumulation, out_depth, out_semantics, out_label, d_density, d_rgb,
+                 d_logit, stream);
   return launch_composite_fwd_bwd("composite_fwd_bwd_targets_semgrad", rays, S, euclid_bins, density, rgb, logit, image, mask,
                                   semantic_loss_weight, true, nullptr, weights, out_rgb, out_accumulation, out_depth,
                                   out_semantics, out_label, d_density, d_rgb, d_logit, stream);
@@ -392,15 +371,8 @@ extern "C" int fnr_composite_bwd_targets_opt(const fnr_rays* rays, int S, const 
                                                    out_semantics, mask, semantic_loss_weight, d_density, d_rgb, d_logit, stream)
                : fnr_composite_bwd_targets(rays, S, euclid_bins, density, rgb, weights, out_rgb, image, out_semantics, mask,
                                            semantic_loss_weight, d_density, d_rgb, d_logit, stream);
-  if (seq::recording() && rays && opt) {
-    const fnr_rays rays_ = *rays;
-    const fnr_composite_options opt_ = *opt;
-    seq::push("fnr_composite_bwd_targets_opt", [=](const fnr_step_scalars*) {
-      return fnr_composite_bwd_targets_opt(&rays_, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
-                                           out_semantics, mask, semantic_loss_weight, &opt_, d_density, d_rgb, d_logit,
-                                           stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_composite_bwd_targets_opt, rays, S, euclid_bins, density, rgb, logit, weights, out_rgb, image,
+                 out_semantics, mask, semantic_loss_weight, opt, d_density, d_rgb, d_logit, stream);
   FNR_CHECK_COMPOSITE_OPTIONS("composite_bwd_targets_opt", opt);
   const LossTargets tg{out_rgb, image, out_semantics, mask, semantic_loss_weight};
   return launch_composite_bwd("composite_bwd_targets_opt", rays, S, euclid_bins, density, rgb, logit, weights, nullptr, nullptr,
@@ -417,15 +389,9 @@ extern "C" int fnr_composite_fwd_bwd_targets_opt(const fnr_rays* rays, int S, co
     return (opt->semantic_gradients ? fnr_composite_fwd_bwd_targets_semgrad : fnr_composite_fwd_bwd_targets)(
         rays, S, euclid_bins, density, rgb, logit, image, mask, semantic_loss_weight, weights, out_rgb, out_accumulation,
         out_depth, out_semantics, out_label, d_density, d_rgb, d_logit, stream);
-  if (seq::recording() && rays && opt) {
-    const fnr_rays rays_ = *rays;
-    const fnr_composite_options opt_ = *opt;
-    seq::push("fnr_composite_fwd_bwd_targets_opt", [=](const fnr_step_scalars*) {
-      return fnr_composite_fwd_bwd_targets_opt(&rays_, S, euclid_bins, density, rgb, logit, image, mask,
-                                               semantic_loss_weight, &opt_, weights, out_rgb, out_accumulation, out_depth,
-                                               out_semantics, out_label, d_density, d_rgb, d_logit, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_composite_fwd_bwd_targets_opt, rays, S, euclid_bins, density, rgb, logit, image, mask,
+                 semantic_loss_weight, opt, weights, out_rgb, out_accumulation, out_depth, out_semantics, out_label, d_density,
+                 d_rgb, d_logit, stream);
   FNR_CHECK_COMPOSITE_OPTIONS("composite_fwd_bwd_targets_opt", opt);
   return launch_composite_fwd_bwd("composite_fwd_bwd_targets_opt", rays, S, euclid_bins, density, rgb, logit, image, mask,
                                   semantic_loss_weight, opt->semantic_gradients, opt, weights, out_rgb, out_accumulation,

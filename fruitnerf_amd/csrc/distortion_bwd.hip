@@ -110,12 +110,8 @@ using namespace fnr;
 extern "C" int fnr_distortion_bwd(int64_t n_rays, int S, const float* spacing, const float* euclid_bins,
                                   const float* density, const float* weights, float mult, const float* upstream,
                                   int gradient_scaling, float* d_weights, float* d_density, void* stream) {
-  if (seq::recording()) {
-    seq::push("fnr_distortion_bwd", [=](const fnr_step_scalars*) {
-      return fnr_distortion_bwd(n_rays, S, spacing, euclid_bins, density, weights, mult, upstream, gradient_scaling,
-                                d_weights, d_density, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_distortion_bwd, n_rays, S, spacing, euclid_bins, density, weights, mult, upstream, gradient_scaling,
+                 d_weights, d_density, stream);
   FNR_CHECK_ARG(n_rays >= 0 && spacing && euclid_bins && density && weights && d_density, "distortion_bwd: null argument");
   FNR_CHECK_ARG(S > 0 && S <= 64 * WB_MAXE, "distortion_bwd: S %d out of range", S);
   if (n_rays == 0) return FNR_OK;

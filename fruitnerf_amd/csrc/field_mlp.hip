@@ -326,14 +326,8 @@ extern "C" int fnr_field_mlp_fwd(const fnr_field_net* net, const fnr_rays* rays,
                                  const uint8_t* selector, const float* mean_embedding, float* density, float* rgb,
                                  float* logit, float* geo_out, float* h_save, float* ray_bias_save,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-  if (seq::recording() && net && rays) {
-    const fnr_field_net net_ = *net;
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_field_mlp_fwd", [=](const fnr_step_scalars*) {
-      return fnr_field_mlp_fwd(&net_, &rays_, S, feats, selector, mean_embedding, density, rgb, logit, geo_out, h_save,
-                               ray_bias_save, workspace, workspace_bytes, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_field_mlp_fwd, net, rays, S, feats, selector, mean_embedding, density, rgb, logit, geo_out, h_save,
+                 ray_bias_save, workspace, workspace_bytes, stream);
   FNR_CHECK_ARG(net && rays && feats && density && rgb && logit && S > 0, "field_mlp_fwd: null argument");
   FNR_CHECK_ARG(rays->directions, "field_mlp_fwd: rays.directions is null");
   FNR_CHECK_ARG(mean_embedding || (rays->camera_indices && net->embedding),

@@ -377,20 +377,12 @@ int field_mlp_bwd_entry(const BwdCall& c, bool semgrad) {
   return a.cfg == 0 ? field_mlp_bwd_launch<FieldCfgBase>(a, ws) : field_mlp_bwd_launch<FieldCfgBig>(a, ws);
 }
 
-// _adam / _semgrad while a step program is recorded: the replay calls the same entry point on copies of the host structs,
-// with the optimiser's lr / step patched in.  False: nothing was recorded.
-bool record_bwd(const char* name, decltype(&fnr_field_mlp_bwd_adam) again, const BwdCall& c) {
-  if (!(seq::recording() && c.net && c.grads && c.rays && c.weight_adam)) return false;
-  const fnr_field_net net_ = *c.net, grads_ = *c.grads;
-  const fnr_rays rays_ = *c.rays;
-  const fnr_table_adam adam_ = *c.weight_adam;
-  seq::push(name, [=](const fnr_step_scalars* sc) {
-    const fnr_table_adam adam = seq::patched(adam_, sc);
-    return again(&net_, &grads_, &rays_, c.S, c.feats, c.h_saved, c.ray_bias_saved, c.packed_saved, c.selector, c.d_density,
-                 c.d_rgb, c.d_logit, c.d_feats, c.jacobian, c.d_position, &adam, c.grad_arena, c.workspace, c.workspace_bytes,
-                 c.stream);
-  });
-  return true;
+// _adam / _semgrad while a step program is recorded: `entry`, the export that was called, is what replays, as `name`, on the
+// block's members (a call without its host structs, weight_adam among them, is not recorded).  False: nothing was recorded.
+bool record_bwd(const char* name, decltype(&fnr_field_mlp_bwd_adam) entry, const BwdCall& c) {
+  return seq::record(name, entry, c.net, c.grads, c.rays, c.S, c.feats, c.h_saved, c.ray_bias_saved, c.packed_saved, c.selector,
+                     c.d_density, c.d_rgb, c.d_logit, c.d_feats, c.jacobian, c.d_position, c.weight_adam, c.grad_arena,
+                     c.workspace, c.workspace_bytes, c.stream);
 }
 }  // namespace
 

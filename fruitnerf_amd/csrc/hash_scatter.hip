@@ -787,17 +787,8 @@ extern "C" int fnr_hash_encode_bwd_adam(const fnr_grid* grid_grad, const fnr_war
                                         const float* euclid_bins, int S, const float* d_feats, void* workspace,
                                         size_t workspace_bytes, int workspace_clean, const fnr_table_adam* adam,
                                         void* stream) {
-  if (seq::recording() && grid_grad && warp && rays && adam) {
-    const fnr_grid grid_ = *grid_grad;
-    const fnr_warp warp_ = *warp;
-    const fnr_rays rays_ = *rays;
-    const fnr_table_adam adam_ = *adam;
-    seq::push("fnr_hash_encode_bwd_adam", [=](const fnr_step_scalars* sc) {
-      const fnr_table_adam a = seq::patched(adam_, sc);
-      return fnr_hash_encode_bwd_adam(&grid_, &warp_, &rays_, euclid_bins, S, d_feats, workspace, workspace_bytes,
-                                      workspace_clean, &a, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_hash_encode_bwd_adam, grid_grad, warp, rays, euclid_bins, S, d_feats, workspace, workspace_bytes,
+                 workspace_clean, adam, stream);
   FNR_CHECK_ARG(grid_grad && warp && rays && euclid_bins && d_feats && S > 0, "hash_encode_bwd_adam: null argument");
   FNR_CHECK_ARG(grid_grad->n_levels >= 1 && grid_grad->n_levels <= FNR_MAX_LEVELS, "hash_encode_bwd_adam: n_levels");
   TableAdam t;

@@ -52,27 +52,6 @@ __global__ __launch_bounds__(256) void k_random_background(unsigned long long se
   for (int c = 0; c < 3; ++c) out[3 * r + c] = w[c];
 }
 
-// The prologue's own arguments, as an entry point fills them, then what train_prologue() adds from the call's CameraCall.
-struct PrologueArgs {
-  unsigned long long seed, offset;
-  const float* pose;        // [n_train, 6] tangents of the kernel's MODE, or NULL (cameras as they are)
-  float* c2w_adjusted;      // [n_train, 3, 4] out (with pose)
-  float *u, *jitter;        // [R, 3], [n_jitter, R] out (the per-edge form writes no jitter)
-  int n_jitter;             // <= 5
-  float *origins, *directions;
-  int* cam_idx;
-  float *image, *mask;
-  float near, far;
-  int kind, S0;
-  const float* base_bins;   // [S0 + 1]
-  float *spacing0, *euclid0;   // [R, S0 + 1] out
-  ImageSetDev set;
-  const long long* train_ids;
-  int n_train;
-  long long n_rays;
-  int nb_rays;              // workgroups of the per-ray role
-};
-
 // EDGES (use_single_jitter = False, fnr_train_prologue_edges): the per-ray role writes no jitter rows, and the level-0 role is
 // one thread per QUAD of bin edges — one Philox call gives the jitters of edges 4q .. 4q + 3 (step_randoms.hpp).
 template <bool CAMS, int MODE, bool EDGES = false>
@@ -234,13 +213,7 @@ extern "C" int fnr_camera_rays(const float* c2w, const float* intrinsics, const 
 // a: the entry point's part of the kernel's arguments;  edges: the per-edge form (fnr_train_prologue_edges; jitter == NULL,
 // n_jitter == 0).  A recorded call is replayed from the block and `a` with the step's offset.
 static int train_prologue(const CameraCall& c, PrologueArgs a, bool edges) {
-  if (seq::recording() && c.has_set && (!c.use_cams || c.has_cams)) {
-    seq::push(c.name, [=](const fnr_step_scalars* sc) {
-      PrologueArgs b = a;
-      if (sc) b.offset = sc->prologue_offset;
-      return train_prologue(c, b, edges);
-    });
-  }
+  if (c.has_set && (!c.use_cams || c.has_cams)) seq::record(c.name, &train_prologue, c, a, edges);
   const bool own = a.u && (a.jitter || edges) && a.origins && a.directions && a.cam_idx && a.image && a.mask && a.base_bins &&
                    a.spacing0 && a.euclid0;
   const int rc = check_camera_call(c, "train_prologue", own, true);
@@ -319,11 +292,7 @@ extern "C" int fnr_train_prologue_edges(const fnr_image_set* set, const fnr_came
 
 extern "C" int fnr_edge_jitter(uint64_t seed, uint64_t offset, int level, int64_t n_rays, int n_edges, float* out,
                                void* stream) {
-  if (seq::recording()) {
-    seq::push("fnr_edge_jitter", [=](const fnr_step_scalars* sc) {
-      return fnr_edge_jitter(seed, sc ? sc->prologue_offset : offset, level, n_rays, n_edges, out, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_edge_jitter, seed, seq::Offset{offset}, level, n_rays, n_edges, out, stream);
   FNR_CHECK_ARG(out && n_rays >= 0, "edge_jitter: null argument or negative ray count");
   FNR_CHECK_ARG(level >= 0 && level < FNR_EDGE_JITTER_MAX_LEVELS, "edge_jitter: level %d (0..%d)", level,
                 FNR_EDGE_JITTER_MAX_LEVELS - 1);
@@ -338,11 +307,7 @@ extern "C" int fnr_edge_jitter(uint64_t seed, uint64_t offset, int level, int64_
 }
 
 extern "C" int fnr_random_background(uint64_t seed, uint64_t offset, int64_t n_rays, float* out, void* stream) {
-  if (seq::recording()) {
-    seq::push("fnr_random_background", [=](const fnr_step_scalars* sc) {
-      return fnr_random_background(seed, sc ? sc->prologue_offset : offset, n_rays, out, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_random_background, seed, seq::Offset{offset}, n_rays, out, stream);
   FNR_CHECK_ARG(out && n_rays >= 0, "random_background: null argument or negative ray count");
   if (n_rays == 0) return FNR_OK;
   hipLaunchKernelGGL(k_random_background, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, as_stream(stream),

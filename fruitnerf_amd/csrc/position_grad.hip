@@ -340,24 +340,11 @@ extern "C" int fnr_position_grad_reduce_multi(int n_sources, const fnr_warp* con
                                               const float* const* euclid_bins, const int* S, const int* n_levels,
                                               const float* const* partials, int accumulate, float* d_origins,
                                               float* d_directions, void* stream) {
-  if (seq::recording() && n_sources >= 1 && n_sources <= FNR_MAX_POSITION_SOURCES && warps && rays && euclid_bins && S &&
-      n_levels && partials) {
-    constexpr int M = FNR_MAX_POSITION_SOURCES;
-    std::array<fnr_warp, M> warps_{};
-    for (int q = 0; q < n_sources; ++q)
-      if (warps[q]) warps_[q] = *warps[q];
-    const fnr_rays rays_ = *rays;
-    const auto eu_ = seq::copy_n<const float*, M>(euclid_bins, n_sources);
-    const auto S_ = seq::copy_n<int, M>(S, n_sources);
-    const auto lv_ = seq::copy_n<int, M>(n_levels, n_sources);
-    const auto pa_ = seq::copy_n<const float*, M>(partials, n_sources);
-    seq::push("fnr_position_grad_reduce_multi", [=](const fnr_step_scalars*) {
-      const fnr_warp* w_[M];
-      for (int q = 0; q < M; ++q) w_[q] = &warps_[q];
-      return fnr_position_grad_reduce_multi(n_sources, w_, &rays_, eu_.data(), S_.data(), lv_.data(), pa_.data(), accumulate,
-                                            d_origins, d_directions, stream);
-    });
-  }
+  constexpr int M = FNR_MAX_POSITION_SOURCES;
+  FNR_SEQ_RECORD(fnr_position_grad_reduce_multi, n_sources, seq::host_array<M>(warps, n_sources), rays,
+                 seq::host_array<M>(euclid_bins, n_sources), seq::host_array<M>(S, n_sources),
+                 seq::host_array<M>(n_levels, n_sources), seq::host_array<M>(partials, n_sources), accumulate, d_origins,
+                 d_directions, stream);
   FNR_CHECK_ARG(n_sources >= 1 && n_sources <= FNR_MAX_POSITION_SOURCES && warps && rays && euclid_bins && S && n_levels &&
                     partials && d_origins && d_directions,
                 "position_grad_reduce_multi: bad argument (1..%d sources)", FNR_MAX_POSITION_SOURCES);

@@ -423,48 +423,19 @@ static int prop_single(const char* who, PropLevel lv, const fnr_rays* rays, cons
   return scatter_accumulate(acc, adam, st);
 }
 
-// What the paired exports share ahead of their launches.  While a step program is being recorded the call is pushed as `name`
-// (the export) with its arguments by value: the replay rebuilds the pointer arrays, patches the optimiser descriptors from its
-// scalars and calls again(event, <the common arguments>).  Then the checks of the pair and, if there are rays, of its levels -> lv.
-template <class Again>
-static int pair_begin(const char* name, Again again, void* event, PropLevel (&lv)[2], const fnr_prop_net* const* nets,
-                      const fnr_prop_net* const* grads, const fnr_warp* const* warps, const fnr_rays* rays,
-                      const float* const* euclid_bins, const int* S, const float* const* feat_save,
-                      const float* const* d_density, float* const* d_position, const fnr_table_adam* const* table_adam,
-                      const fnr_table_adam* weight_adam, const float* grad_arena, void* const* workspace,
-                      const size_t* workspace_bytes, const int* workspace_clean, void* stream) {
-  if (seq::recording() && nets && grads && warps && rays && euclid_bins && S && feat_save && d_density && d_position &&
-      workspace && workspace_bytes && workspace_clean && nets[0] && nets[1] && grads[0] && grads[1] && warps[0] && warps[1]) {
-    struct Pair {
-      fnr_prop_net net[2], grad[2];
-      fnr_warp warp[2];
-      fnr_rays rays;
-      const float *euclid[2], *feat[2], *dd[2];
-      float* dpos[2];
-      fnr_table_adam tadam[2], wadam;
-      bool has_adam;
-      void* ws[2];
-      size_t ws_bytes[2];
-      int S[2], ws_clean[2];
-    } p;
-    for (int q = 0; q < 2; ++q) {
-      p.net[q] = *nets[q], p.grad[q] = *grads[q], p.warp[q] = *warps[q], p.euclid[q] = euclid_bins[q], p.S[q] = S[q];
-      p.feat[q] = feat_save[q], p.dd[q] = d_density[q], p.dpos[q] = d_position[q], p.ws[q] = workspace[q];
-      p.ws_bytes[q] = workspace_bytes[q], p.ws_clean[q] = workspace_clean[q];
-    }
-    p.rays = *rays;
-    p.has_adam = table_adam && table_adam[0] && table_adam[1] && weight_adam;
-    if (p.has_adam) p.tadam[0] = *table_adam[0], p.tadam[1] = *table_adam[1], p.wadam = *weight_adam;
-    seq::push(name, [=](const fnr_step_scalars* sc) {
-      const fnr_prop_net* n_[2] = {&p.net[0], &p.net[1]};
-      const fnr_prop_net* g_[2] = {&p.grad[0], &p.grad[1]};
-      const fnr_warp* w_[2] = {&p.warp[0], &p.warp[1]};
-      const fnr_table_adam t0 = seq::patched(p.tadam[0], sc), t1 = seq::patched(p.tadam[1], sc), wa = seq::patched(p.wadam, sc);
-      const fnr_table_adam* t_[2] = {&t0, &t1};
-      return again(event, n_, g_, w_, &p.rays, p.euclid, p.S, p.feat, p.dd, p.dpos, p.has_adam ? t_ : nullptr,
-                   p.has_adam ? &wa : nullptr, grad_arena, p.ws, p.ws_bytes, p.ws_clean, stream);
-    });
-  }
+// A per-level array of the paired exports, as a step program keeps it (sequencer.hpp): the replay patches the optimiser
+// descriptors among them from its scalars.
+template <class T>
+static auto both(const T* per_level) {
+  return seq::host_array<2>(per_level, 2);
+}
+
+// What the paired exports share behind their recording hooks: the checks of the pair and, if there are rays, of its levels -> lv.
+static int pair_begin(const char* name, PropLevel (&lv)[2], const fnr_prop_net* const* nets, const fnr_prop_net* const* grads,
+                      const fnr_warp* const* warps, const fnr_rays* rays, const float* const* euclid_bins, const int* S,
+                      const float* const* feat_save, const float* const* d_density, float* const* d_position,
+                      const fnr_table_adam* const* table_adam, const fnr_table_adam* weight_adam, const float* grad_arena,
+                      void* const* workspace, const size_t* workspace_bytes, const int* workspace_clean) {
   const char* who = name + 4;   // the messages name the export without its prefix
   FNR_CHECK_ARG(nets && grads && warps && rays && euclid_bins && S && feat_save && d_density && d_position && workspace &&
                     workspace_bytes && workspace_clean,
@@ -531,9 +502,11 @@ extern "C" int fnr_prop_density_bwd_pair(const fnr_prop_net* const* nets, const 
                                          const float* grad_arena, void* const* workspace, const size_t* workspace_bytes,
                                          const int* workspace_clean, void* stream) {
   PropLevel lv[2];
-  int rc = pair_begin("fnr_prop_density_bwd_pair", [](void*, auto... args) { return fnr_prop_density_bwd_pair(args...); }, nullptr,
-                      lv, nets, grads, warps, rays, euclid_bins, S, feat_save, d_density, d_position, table_adam, weight_adam,
-                      grad_arena, workspace, workspace_bytes, workspace_clean, stream);
+  FNR_SEQ_RECORD(fnr_prop_density_bwd_pair, both(nets), both(grads), both(warps), rays, both(euclid_bins), both(S),
+                 both(feat_save), both(d_density), both(d_position), both(table_adam), seq::optional(weight_adam), grad_arena,
+                 both(workspace), both(workspace_bytes), both(workspace_clean), stream);
+  int rc = pair_begin("fnr_prop_density_bwd_pair", lv, nets, grads, warps, rays, euclid_bins, S, feat_save, d_density, d_position,
+                      table_adam, weight_adam, grad_arena, workspace, workspace_bytes, workspace_clean);
   if (rc || rays->n_rays == 0) return rc;
   FNR_PROF(OP_PROP_BWD, rays->n_rays * ((long long)S[0] + (long long)S[1]));   // one scope: both levels + the joint accumulate
   const hipStream_t st = as_stream(stream);
@@ -559,10 +532,11 @@ extern "C" int fnr_prop_density_bwd_pair_split(const fnr_prop_net* const* nets, 
                                                const float* grad_arena, void* const* workspace, const size_t* workspace_bytes,
                                                const int* workspace_clean, void* stream, void* position_ready_event) {
   PropLevel lv[2];
-  int rc = pair_begin("fnr_prop_density_bwd_pair_split",
-                      [](void* ev, auto... args) { return fnr_prop_density_bwd_pair_split(args..., ev); }, position_ready_event,
-                      lv, nets, grads, warps, rays, euclid_bins, S, feat_save, d_density, d_position, table_adam, weight_adam,
-                      grad_arena, workspace, workspace_bytes, workspace_clean, stream);
+  FNR_SEQ_RECORD(fnr_prop_density_bwd_pair_split, both(nets), both(grads), both(warps), rays, both(euclid_bins), both(S),
+                 both(feat_save), both(d_density), both(d_position), both(table_adam), seq::optional(weight_adam), grad_arena,
+                 both(workspace), both(workspace_bytes), both(workspace_clean), stream, position_ready_event);
+  int rc = pair_begin("fnr_prop_density_bwd_pair_split", lv, nets, grads, warps, rays, euclid_bins, S, feat_save, d_density,
+                      d_position, table_adam, weight_adam, grad_arena, workspace, workspace_bytes, workspace_clean);
   if (rc) return rc;
   const hipStream_t st = as_stream(stream);
   const hipEvent_t position_ready = reinterpret_cast<hipEvent_t>(position_ready_event);

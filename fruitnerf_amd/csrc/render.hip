@@ -94,13 +94,8 @@ extern "C" int fnr_composite_fwd(const fnr_rays* rays, int S, const float* eucli
                                  const float* rgb, const float* logit, int training, float* weights, float* out_rgb,
                                  float* out_accumulation, float* out_depth, float* out_semantics,
                                  int64_t* out_label, void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    seq::push("fnr_composite_fwd", [=](const fnr_step_scalars*) {
-      return fnr_composite_fwd(&rays_, S, euclid_bins, density, rgb, logit, training, weights, out_rgb, out_accumulation,
-                               out_depth, out_semantics, out_label, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_composite_fwd, rays, S, euclid_bins, density, rgb, logit, training, weights, out_rgb, out_accumulation,
+                 out_depth, out_semantics, out_label, stream);
   FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && weights && out_rgb && out_accumulation &&
                     out_depth && out_semantics,
                 "composite_fwd: null argument");
@@ -123,14 +118,8 @@ extern "C" int fnr_composite_fwd_opt(const fnr_rays* rays, int S, const float* e
   if (composite_options_ok(opt) && opt->background == FNR_BACKGROUND_LAST_SAMPLE)
     return fnr_composite_fwd(rays, S, euclid_bins, density, rgb, logit, training, weights, out_rgb, out_accumulation,
                              out_depth, out_semantics, out_label, stream);
-  if (seq::recording() && rays && opt) {
-    const fnr_rays rays_ = *rays;
-    const fnr_composite_options opt_ = *opt;
-    seq::push("fnr_composite_fwd_opt", [=](const fnr_step_scalars*) {
-      return fnr_composite_fwd_opt(&rays_, S, euclid_bins, density, rgb, logit, training, &opt_, weights, out_rgb,
-                                   out_accumulation, out_depth, out_semantics, out_label, stream);
-    });
-  }
+  FNR_SEQ_RECORD(fnr_composite_fwd_opt, rays, S, euclid_bins, density, rgb, logit, training, opt, weights, out_rgb,
+                 out_accumulation, out_depth, out_semantics, out_label, stream);
   FNR_CHECK_COMPOSITE_OPTIONS("composite_fwd_opt", opt);
   FNR_CHECK_ARG(rays && euclid_bins && density && rgb && logit && weights && out_rgb && out_accumulation && out_depth &&
                     out_semantics,

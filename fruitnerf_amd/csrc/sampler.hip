@@ -40,10 +40,6 @@ static_assert(PDF_MAXE == RAY_MAX_LANE_ELEMS && PDF_MAX_PREV == 64 * PDF_MAXE, "
 // wave's 64 lanes make their calls in one pass, so sharing a call among the four edges of a quad would save no instructions
 // below 256 edges and cost four cross-lane reads per pass; measured).  Only the resampling's `u` differs between
 // the two forms.
-struct EdgeDraw {
-  unsigned long long seed, offset;
-  int level, draw;
-};
 template <int ME, bool EDGES>
 __device__ __forceinline__ void weights_pdf_ray(float* cdf, float* ex, const RaysDev& rays, int kind, int S_prev, int S_new,
                                                 const float* __restrict__ density, const float* __restrict__ spacing_prev,
@@ -262,22 +258,13 @@ extern "C" int fnr_sample_spaced(const fnr_rays* rays, int spacing_kind, int S, 
 }
 
 // edges: NULL for fnr_weights_pdf (rand [R] or NULL), the generator's arguments of fnr_weights_pdf_edges otherwise (rand
-// [R, S_new + 1] or NULL)
+// [R, S_new + 1] or NULL).  name: the export that was called; a step program lists and replays the call under it.
 static int weights_pdf(const char* name, const EdgeDraw* edges, const fnr_rays* rays, int spacing_kind, int S_prev, int S_new,
                        const float* density, const float* spacing_prev, const float* euclid_prev, float anneal,
                        const float* u_base, const float* rand, float* weights, float* median_depth, float* spacing_new,
                        float* euclid_new, void* stream) {
-  if (seq::recording() && rays) {
-    const fnr_rays rays_ = *rays;
-    const bool per_edge = edges != nullptr;
-    const EdgeDraw edges_ = per_edge ? *edges : EdgeDraw{};
-    seq::push(name, [=](const fnr_step_scalars* sc) {
-      EdgeDraw e = edges_;
-      if (sc && e.draw) e.offset = sc->prologue_offset;
-      return weights_pdf(name, per_edge ? &e : nullptr, &rays_, spacing_kind, S_prev, S_new, density, spacing_prev, euclid_prev,
-                         sc ? sc->anneal : anneal, u_base, rand, weights, median_depth, spacing_new, euclid_new, stream);
-    });
-  }
+  seq::record(name, &weights_pdf, name, seq::optional(edges), rays, spacing_kind, S_prev, S_new, density, spacing_prev,
+              euclid_prev, seq::Anneal{anneal}, u_base, rand, weights, median_depth, spacing_new, euclid_new, stream);
   FNR_CHECK_ARG(rays && density && euclid_prev && weights, "weights_pdf: null argument");
   FNR_CHECK_ARG(!edges || !edges->draw ||
                     (!rand && edges->level >= 1 && edges->level < FNR_EDGE_JITTER_MAX_LEVELS && S_new < FNR_EDGE_JITTER_MAX_EDGES),

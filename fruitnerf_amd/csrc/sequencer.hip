@@ -109,22 +109,20 @@ extern "C" int fnr_event_destroy(void* event) {
 
 extern "C" int fnr_event_record(void* event, void* stream) {
   FNR_CHECK_ARG(event, "event_record: null event");
-  if (seq::recording()) seq::push("fnr_event_record", [=](const fnr_step_scalars*) { return fnr_event_record(event, stream); });
+  FNR_SEQ_RECORD(fnr_event_record, event, stream);
   FNR_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(event), as_stream(stream)));
   return FNR_OK;
 }
 
 extern "C" int fnr_stream_wait_event(void* stream, void* event) {
   FNR_CHECK_ARG(event, "stream_wait_event: null event");
-  if (seq::recording())
-    seq::push("fnr_stream_wait_event", [=](const fnr_step_scalars*) { return fnr_stream_wait_event(stream, event); });
+  FNR_SEQ_RECORD(fnr_stream_wait_event, stream, event);
   FNR_HIP(hipStreamWaitEvent(as_stream(stream), reinterpret_cast<hipEvent_t>(event), 0));
   return FNR_OK;
 }
 
 extern "C" int fnr_stream_wait_stream(void* waiting, void* signalling) {
-  if (seq::recording())
-    seq::push("fnr_stream_wait_stream", [=](const fnr_step_scalars*) { return fnr_stream_wait_stream(waiting, signalling); });
+  FNR_SEQ_RECORD(fnr_stream_wait_stream, waiting, signalling);
   if (waiting == signalling) return FNR_OK;
   hipEvent_t e;
   const int rc = seq::ring_event(&e);

@@ -50,4 +50,15 @@ __device__ __forceinline__ float edge_jitter(unsigned long long seed, unsigned l
   return k == 0 ? w[0] : k == 1 ? w[1] : k == 2 ? w[2] : w[3];
 }
 
+// the generator's arguments of a kernel that draws its own per-edge jitter (draw != 0; sampler.hip)
+struct EdgeDraw {
+  unsigned long long seed, offset;
+  int level, draw;
+};
+// replayed from a step program (sequencer.hpp): a draw continues at the step's counter
+static inline EdgeDraw patched(EdgeDraw e, const fnr_step_scalars* s) {
+  if (s && e.draw) e.offset = s->prologue_offset;
+  return e;
+}
+
 }  // namespace fnr

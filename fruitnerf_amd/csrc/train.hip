@@ -514,25 +514,13 @@ extern "C" int fnr_train_losses(int64_t n_rays, const float* rgb, const float* i
                                 const float* const* euclid_p, const float* const* density_p,
                                 float* const* d_density_p, float interlevel_mult, int want_distortion, float* accum,
                                 float* losses, void* stream) {
-  if (seq::recording() && n_levels >= 0 && n_levels <= FNR_MAX_PROPOSAL_LEVELS) {
-    constexpr int M = FNR_MAX_PROPOSAL_LEVELS;
-    const auto S_ = seq::copy_n<int, M>(S_p, n_levels);
-    const auto sp_ = seq::copy_n<const float*, M>(spacing_p, n_levels);
-    const auto wp_ = seq::copy_n<const float*, M>(weights_p, n_levels);
-    const auto dw_ = seq::copy_n<float*, M>(d_weights_p, n_levels);
-    const auto eu_ = seq::copy_n<const float*, M>(euclid_p, n_levels);
-    const auto dn_ = seq::copy_n<const float*, M>(density_p, n_levels);
-    const auto dd_ = seq::copy_n<float*, M>(d_density_p, n_levels);
-    const bool has_sp = spacing_p, has_wp = weights_p, has_dw = d_weights_p, has_eu = euclid_p, has_dn = density_p,
-               has_dd = d_density_p;
-    seq::push("fnr_train_losses", [=](const fnr_step_scalars* sc) {
-      return fnr_train_losses(n_rays, rgb, image, semantics, fruit_mask, semantic_loss_weight, d_rgb, d_semantics, S_f,
-                              spacing_f, weights_f, n_levels, S_.data(), has_sp ? sp_.data() : nullptr,
-                              has_wp ? wp_.data() : nullptr, has_dw ? dw_.data() : nullptr, has_eu ? eu_.data() : nullptr,
-                              has_dn ? dn_.data() : nullptr, has_dd ? dd_.data() : nullptr, interlevel_mult, want_distortion,
-                              accum, (sc && sc->losses) ? sc->losses : losses, stream);
-    });
-  }
+  constexpr int M = FNR_MAX_PROPOSAL_LEVELS;
+  FNR_SEQ_RECORD(fnr_train_losses, n_rays, rgb, image, semantics, fruit_mask, semantic_loss_weight, d_rgb, d_semantics, S_f,
+                 spacing_f, weights_f, n_levels, seq::host_array<M>(S_p, n_levels), seq::host_array<M>(spacing_p, n_levels),
+                 seq::host_array<M>(weights_p, n_levels), seq::host_array<M>(d_weights_p, n_levels),
+                 seq::host_array<M>(euclid_p, n_levels), seq::host_array<M>(density_p, n_levels),
+                 seq::host_array<M>(d_density_p, n_levels), interlevel_mult, want_distortion, accum, seq::Losses{losses},
+                 stream);
   FNR_CHECK_ARG(rgb && image && semantics && fruit_mask && spacing_f && weights_f && accum && losses && n_rays > 0,
                 "train_losses: null argument");
   FNR_CHECK_ARG((d_rgb == nullptr) == (d_semantics == nullptr), "train_losses: d_rgb and d_semantics go together");
