@@ -43,6 +43,11 @@ with the measured constants c below.
   persistent wave, 8 waves, and at most one partial image per compute unit (<= 256) summed in order
   d_c3: |d_rgb| (ds + ds^2 + 3 u s (1 - s)), ds the error of s: at a saturated sigmoid fl(1 - s) loses s's own rounding
   d_h0 = d_density exp(clamp(h0)) selector: relative 4 u + m_h0 [|h0| < 15]
+
+Plain bf16 (Arith("bf16"), the NS = 1 kernels) is not held to such bounds — u = 2^-9 per operand would put nearly every sample
+next to a kink — but EXACTLY, on dyadic inputs: the last section of this file (make_lattice_net, make_lattice_batch, exactness,
+guard, bf16_backward, exact_compare).  Its comment states where the kernels round, where each bias gradient is formed (a row
+sum on the matrix pipe with G rounded, or a float32 sum of the unrounded G), and where the saved h is reused or recomputed.
 """
 import math
 
@@ -174,12 +179,22 @@ def _split(a):
 
 
 class Arith:
-    """name: "f64" | "f32" | "bf16x3".  bf16x3: the piece products with p + q <= level (forward 2: six, backward 1: three of
-    the pieces x1, x2), each exact in float32, float32 accumulate, smallest terms first."""
+    """name: "f64" | "f32" | "bf16x3" | "bf16".  bf16x3: the piece products with p + q <= level (forward 2: six, backward 1:
+    three of the pieces x1, x2), each exact in float32, float32 accumulate, smallest terms first.
+    bf16 (the NS = 1 kernels, "Plain bf16" below): a float64 product of operands that were each rounded through torch.bfloat16;
+    the accumulator start (bias, ray_bias) is not rounded.  rule / mut: the sensitivity mutations of
+    tests/test_field_bf16_exact_cpu.py.  trace=True keeps every accumulation's operands in .log (exactness, rounding_stats)."""
 
-    def __init__(self, name, fwd_level=2, bwd_level=1):
+    def __init__(self, name, fwd_level=2, bwd_level=1, rule="rne", mut=(), trace=False):
         self.name, self.fwd_level, self.bwd_level = name, fwd_level, bwd_level
-        self.dtype = F8 if name == "f64" else F4
+        self.dtype = F4 if name in ("f32", "bf16x3") else F8
+        self.rule, self.mut, self.log = rule, tuple(mut), ([] if trace else None)
+
+    def rnd(self, a):
+        """The operand conversion of the plain bf16 mode: round to nearest even through torch.bfloat16."""
+        if self.name != "bf16":
+            return a
+        return a.float().bfloat16().to(a.dtype) if self.rule == "rne" else round8(a, self.rule)
 
     def _mm(self, a, b, level):
         if self.name != "bf16x3":
@@ -192,14 +207,34 @@ class Arith:
                 out = t if out is None else out + t
         return out
 
-    def fwd(self, x, w):
-        return self._mm(x, w.T, self.fwd_level)
+    def _note(self, kind, layer, x, w, xu, start=None):
+        if self.log is not None:
+            self.log.append(dict(kind=kind, layer=layer, x=x.detach().double(), w=w.detach().double(), xu=xu.detach().double(),
+                                 start=None if start is None else start.detach().double()))
 
-    def dx(self, g, w):
-        return self._mm(g, w, self.bwd_level)
+    def fwd(self, x, w, layer=None, start=None):
+        xr, wr = self.rnd(x), self.rnd(w)
+        if ("unrounded_input", layer) in self.mut:
+            xr = x
+        if ("swap_slots", layer) in self.mut:            # K-slots 1 and 2 of the layer's first 16 x 32 weight block
+            wr = wr.clone()
+            wr[:16, 1], wr[:16, 2] = wr[:16, 2].clone(), wr[:16, 1].clone()
+        self._note("fwd", layer, xr, wr, x, start)
+        return self._mm(xr, wr.T, self.fwd_level)
 
-    def dw(self, g, x):
-        return self._mm(g.T.contiguous(), x, self.bwd_level)
+    def affine(self, x, w, start, layer=None):
+        """start + x w^T: the accumulator starts at the bias (the per-ray bias in the colour branch's first layer)."""
+        y = self.fwd(x, w, layer, start)
+        return y + (self.rnd(start) if "bias_converted" in self.mut else start)
+
+    def dx(self, g, w, layer=None):
+        gr, wr = self.rnd(g), self.rnd(w)
+        self._note("dx", layer, gr, wr.T, g)
+        return self._mm(gr, wr, self.bwd_level)
+
+    def dw(self, g, x, layer=None):
+        gr = g if ("g_unrounded", layer) in self.mut else self.rnd(g)
+        return self._mm(gr.T.contiguous(), self.rnd(x), self.bwd_level)
 
 
 REF = Arith("f64")
@@ -259,27 +294,27 @@ def forward(net, batch, ar=REF, mean_embedding=None, semgrad=False, p=None, x=No
     sel = batch["sel"].to(dt)
     ray = torch.arange(batch["N"]) // S
     f = {"x": x}
-    f["a1"] = ar.fwd(x, p["base0"][0]) + p["base0"][1]
-    f["h"] = ar.fwd(torch.relu(f["a1"]), p["base1"][0]) + p["base1"][1]
+    f["a1"] = ar.affine(x, *p["base0"], "base0")
+    f["h"] = ar.affine(torch.relu(f["a1"]), *p["base1"], "base1")
     f["density"] = _TruncExp.apply(f["h"][:, 0]) * sel
     f["geo"] = f["h"][:, 1:]
     s = f["geo"] if semgrad else f["geo"].detach()
     sem = [k for k in layer_names(net["shape"]) if k.startswith("sem")]
     for i, k in enumerate(sem):
         f["in_" + k] = s
-        f["pre_" + k] = ar.fwd(s, p[k][0]) + p[k][1]
+        f["pre_" + k] = ar.affine(s, *p[k], k)
         s = f["pre_" + k] if i == len(sem) - 1 else torch.relu(f["pre_" + k])
     f["in_head"] = s
-    f["logit"] = (ar.fwd(s, p["head"][0]) + p["head"][1])[:, 0]
+    f["logit"] = ar.affine(s, *p["head"], "head")[:, 0]
     const, gcol = _cols(geo)
     f["sh"] = sh16((batch["dirs"].to(dt) + 1.0) / 2.0)
     emb = p["embedding"][batch["cam"]] if mean_embedding is None else mean_embedding.to(dt)[None].expand(batch["R"], 32)
     f["c_ray"] = torch.cat([f["sh"], emb], 1)
     w0, b0 = p["col0"]
     f["ray_bias"] = f["c_ray"] @ w0[:, const].T + b0                       # a float32 chain in every arithmetic
-    f["c1"] = f["ray_bias"][ray] + ar.fwd(f["geo"], w0[:, gcol])
-    f["c2"] = ar.fwd(torch.relu(f["c1"]), p["col1"][0]) + p["col1"][1]
-    f["c3"] = ar.fwd(torch.relu(f["c2"]), p["col2"][0]) + p["col2"][1]
+    f["c1"] = ar.affine(f["geo"], w0[:, gcol], f["ray_bias"][ray], "col0")
+    f["c2"] = ar.affine(torch.relu(f["c1"]), *p["col1"], "col1")
+    f["c3"] = ar.affine(torch.relu(f["c2"]), *p["col2"], "col2")
     f["rgb"] = torch.sigmoid(f["c3"]) if dt == F8 else 1.0 / (1.0 + torch.exp(-f["c3"]))
     pad = 16 * ((1 + geo + 15) // 16) - (1 + geo)
     f["h_pad"] = torch.cat([f["h"], torch.zeros(batch["N"], pad, dtype=dt)], 1)
@@ -308,7 +343,11 @@ def _seg(t, R, S):
 
 def manual_backward(net, batch, up, ar, semgrad=False, mut=()):
     """The backward as the kernels organise it, in ar's arithmetic (float32 element-wise; matrix products through ar).
-    mut: the sensitivity mutations of tests/test_field_kernels_cpu.py."""
+    mut: the sensitivity mutations of tests/test_field_kernels_cpu.py.  Plain bf16 has its roundings, its two kinds of bias
+    sums and `fruit_nerf_big`'s factored head gradient written out in bf16_backward (below); here as plain tensors."""
+    if ar.name == "bf16":
+        f, out = bf16_backward(net, batch, up, ar, semgrad, mut)
+        return f, sums_to_tensors(out)
     dt, geo, R, S, N = ar.dtype, net["geo"], batch["R"], batch["S"], batch["N"]
     with torch.no_grad():
         p = params(net, dt)
@@ -627,3 +666,389 @@ def excluded_share_ok(case):
 def scaled(ratios, mode):
     """worst |err| / bound -> worst |err| / (c bound)."""
     return {k: v / C[mode][k] for k, v in ratios.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Plain bf16 (mlp_mode 1, the NS = 1 kernels), tested EXACTLY on dyadic ("lattice") inputs:
+# tests/test_field_bf16_exact_cpu.py, tests/test_gpu_field_bf16_exact.py
+# ---------------------------------------------------------------------------------------------------------------------
+# The mode's contract.  Every layer is acc = start (fp32: the bias, or ray_bias[ray] in the colour branch's first layer), both
+# operands rounded to bf16 (round to nearest even: v_cvt_pk_bf16_f32 for activations and gradients, bf_piece(w, 0) for the
+# weights, once, when the fragment image is packed or bf_build_T builds sem0's transposed fragments), products accumulated in
+# float32 by the matrix pipe.  Where the NS = 1 kernels convert (k_field_mlp_fwd_bf16, k_field_mlp_fwd_sem_big_bf16,
+# field_mlp_bwd_pw.hip, k_field_mlp_bwd_sem_big_bf16):
+#   forward   rounded: the hash features, the input of every layer (relu first), h as the input of sem0 and col0 (the SAVED h
+#             is the unrounded accumulator), `fruit_nerf_big`: s3 = sem2's output as the head's input.  Never rounded: biases,
+#             ray_bias (a float32 fmaf chain of its own kernel), accumulators, h, geo_out, logit; density = expf(h0),
+#             rgb = 1 / (1 + expf(-c3)) in float32.
+#   backward  the saved h is REUSED by the colour branch (input of col0, X of col0's dW), the semantic branch (input of sem0,
+#             X of sem0's dW) and the base branch (h0 of trunc_exp'); RECOMPUTED from it with the forward's roundings: c1, c2,
+#             c3 (and s = sigmoid(c3) in float32, d_c3 = (d_rgb s) (1 - s) in float32), s1, s2; recomputed from the features:
+#             a1 (base0 only: base1 is not run again).  Rounded: every G that enters a transposed layer (dX = W^T G) and both
+#             operands of every dW product (G and the same rounded activation the forward multiplied).  The relu gates read the
+#             sign of the rounded activation (= the sign of the activation).  d_h (colour dX, + the semantic dX under semgrad: a
+#             float32 add) and d_h0 = d_density expf(clamp(h0)) [selector] are float32.
+#   bias gradients  per-wave kernels (every branch of `fruit_nerf`, colour and base of `fruit_nerf_big`): float32 sums of the
+#             UNROUNDED G.  `fruit_nerf_big`'s semantic branch (cs_bias): row sums on the matrix pipe, G ROUNDED.  col0: the
+#             per-ray sums g_ray are matrix-pipe row sums of the ROUNDED G1 when S >= 16 (SelOperand) and float32 atomic sums of
+#             the UNROUNDED G1 when S < 16; the bias is their float32 sum over the rays, the ray-constant columns
+#             g_ray^T [SH16 | embedding row] an fmaf chain, the embedding rows sum_o W_c0[o, k] (sum of the camera's g_ray)[o]
+#             with the UNROUNDED float32 weights.
+#   `fruit_nerf_big`'s head: dW_head = W_sem2 v + b_sem2 sum(bf(dlogit)), v = bf(dlogit)^T bf(s2) on the matrix pipe, the rest
+#             a float32 fmaf chain over the UNROUNDED W_sem2: s3 is NOT rounded here (it is in the forward); `fruit_nerf`'s
+#             head: bf(dlogit)^T bf(s2), s2 its rounded input.
+# Exactness.  A sum whose every partial sum, in whatever order, is a float32 number comes out exact from any correct
+# accumulator: sufficient is log2(sum|addends|) - (exponent of the lowest set bit among the addends) < 24 (`bits` below).
+# Sums that miss it are held to (n - 1) 2^-23 sum|addends|, n the number of addends: the worst case of any summation order
+# ((n - 1) roundings of at most 2^-24 each), doubled because the guides do not say whether the matrix pipe's accumulator rounds
+# or truncates — an assumption, not a measurement.  The SH columns of col0's weight gradient have a float32 SH basis as one
+# factor (not on the lattice, evaluated on the device): n 2^-23 sum|addends| + sum|g| 4 u |SH terms| there (the product is
+# rounded too, and the basis carries the 4 u of forward_bounds' c_ray).
+
+BIG_LB = 1.0e6          # "no set bit": the lowbit of 0
+LATTICE_VARIANTS = ("a", "b")
+
+
+def round8(a, rule="rne"):
+    """a (any float dtype, normal range) rounded to 8 significant bits: "rne" (= torch.bfloat16), "trunc", "away" (half away
+    from zero)."""
+    m, e = torch.frexp(a.double())
+    y = m * 256.0
+    r = torch.round(y) if rule == "rne" else torch.trunc(y) if rule == "trunc" else torch.sign(y) * torch.floor(y.abs() + 0.5)
+    return torch.ldexp(r, e - 8).to(a.dtype)
+
+
+def lowbit(t):
+    """Exponent of the lowest set bit of every entry (float64 tensor of the same shape; BIG_LB at 0)."""
+    t = t.double()
+    m, e = torch.frexp(t)
+    v = (m.abs() * 2.0 ** 53).to(torch.int64)
+    tz = torch.log2((v & -v).clamp_min(1).double()).round()
+    return torch.where(t == 0, torch.full_like(t, BIG_LB), e.double() - 53.0 + tz)
+
+
+def _minplus(a, b, chunk=64):
+    """a [n,p], b [n,q] -> min over n of a[n,i] + b[n,j]  [p,q]."""
+    out = torch.full((a.shape[1], b.shape[1]), 4 * BIG_LB, dtype=F8)
+    for i in range(0, a.shape[0], chunk):
+        out = torch.minimum(out, (a[i:i + chunk, :, None] + b[i:i + chunk, None, :]).amin(0))
+    return out
+
+
+def bits_of(mag, lb):
+    """log2(sum|addends|) - lowest set bit; -inf for an empty sum."""
+    return torch.where(mag > 0, torch.log2(mag.clamp_min(1e-300)) - lb, torch.full_like(mag, -math.inf))
+
+
+def exactness(log, conservative=False, kinds=("fwd", "dx", "add")):
+    """log: Arith(..., trace=True).log -> [(kind, layer, bits [n,out])]: per accumulation acc = start + sum_k x[n,k] w[out,k]
+    the bit count of the condition.  conservative: min lowbit(w[out]) + min lowbit(x[n]) instead of the minimum over k of the
+    sums (large N)."""
+    out = []
+    for e in log:
+        if e["kind"] not in kinds:
+            continue
+        x, w = e["x"], e["w"]
+        mag = x.abs() @ w.abs().T
+        lx, lw = lowbit(x), lowbit(w)
+        if conservative:
+            lb = lx.amin(1, keepdim=True) + lw.amin(1)[None]
+        else:
+            lb = torch.cat([_minplus(lw.T.contiguous(), lx[i:i + 256].T.contiguous()).T for i in range(0, x.shape[0], 256)])
+        if e["start"] is not None:
+            st = e["start"].expand(x.shape[0], w.shape[0])
+            mag, lb = mag + st.abs(), torch.minimum(lb, lowbit(st))
+        out.append((e["kind"], e["layer"], bits_of(mag, lb)))
+    return out
+
+
+def rounding_stats(log, kinds=("fwd", "dx")):
+    """-> {(kind, layer): (nonzero inputs, changed by the conversion, exact ties)} of every traced operand conversion."""
+    out = {}
+    for e in log:
+        if e["kind"] not in kinds:
+            continue
+        xu = e["xu"]
+        m, _ = torch.frexp(xu)
+        y = (m * 256.0).abs()
+        tie = (y - torch.floor(y)) == 0.5
+        key = (e["kind"], e["layer"])
+        prev = out.get(key, (0, 0, 0))
+        out[key] = (prev[0] + int((xu != 0).sum()), prev[1] + int((round8(xu) != xu).sum()), prev[2] + int(tie.sum()))
+    return out
+
+
+_LNETS = {}
+
+
+def make_lattice_net(shape, variant="a"):
+    """Dyadic networks.  "a": weights in {0, +-1/4, +-1/2} at 50 % density, biases multiples of 1/4, the embedding multiples
+    of 1/64; "b": coarser weights ({0, +-1} at 8 per row, base0: {0, +-1/2, +-1} at 1/4) for the finer features of
+    make_lattice_batch(variant="b"), so that base0's and base1's conversions round and tie as well.  The 16 SH columns of col0
+    are zero: ray_bias = b_c0 + W_c0[:, embedding columns] embedding[camera] is on the lattice too."""
+    key = (shape, variant)
+    if key not in _LNETS:
+        g = torch.Generator().manual_seed(90210 + (1000 if shape == "fruit_nerf_big" else 0) + (7 if variant == "b" else 0))
+        geo = SHAPES[shape][0]
+
+        def pick(values, density, *s):
+            v = torch.tensor(values, dtype=F4)[torch.randint(0, len(values), s, generator=g)]
+            return (v * (torch.rand(*s, generator=g) < density)).contiguous()
+
+        net = {"shape": shape, "geo": geo, "variant": variant}
+        for name, (o, i) in layer_dims(shape).items():
+            if name == "col2":      # small: |c3| stays small, s (1 - s) within a few octaves over the three channels
+                w = pick([-0.125, 0.125], 0.25, o, i)
+            elif name == "head":    # dense (every unit of mlp_semantics receives a gradient) and small (under semgrad the
+                w = pick([-1.0, -0.5, 0.5, 1.0], 0.5, o, i) / 64.0   # semantic dX meets the colour dX in one float32 add)
+            elif variant == "a":
+                w = pick([-0.5, -0.25, 0.25, 0.5], 0.5, o, i)
+            elif name == "base0":
+                w = pick([-1.0, -0.5, 0.5, 1.0], 0.25, o, i)
+            else:
+                w = pick([-1.0, 1.0], 5.0 / i if i >= 32 else 0.2, o, i)
+            net[name] = (w, pick([-0.5, -0.25, 0.25, 0.5, 0.75], 0.9, o))
+        w0 = net["col0"][0]                             # [SH 16 | geo | embedding 32]
+        w0[:, 16 + geo:] = pick([-0.5, -0.25, 0.25, 0.5], 0.5, 64, 32)   # either variant: ray_bias gets more than 8 bits
+        if variant == "a":                              # (fewer terms per dX sum of the colour gradient's first layer)
+            w0[:, 16:16 + geo] *= (torch.rand(64, geo, generator=g) < 0.5)
+        w0[:, :16] = 0.0
+        net["base1"][0][0] *= 0.25                      # the density logit stays small: exp(h0) within a few octaves
+        net["embedding"] = (torch.randint(-48, 49, (N_IMAGES, 32), generator=g).to(F4) / 64.0).contiguous()
+        _LNETS[key] = net
+    return _LNETS[key]
+
+
+def make_lattice_batch(R, S, variant="a"):
+    """feats [16,N,2]: multiples of 1/8 ("b": of 1/512) within +-0.75; N >= 64: an all-zero feature row, rows of extremes, ~12 %
+    of the selector false; directions and cameras as make_batch (LONE_CAM on exactly one ray, UNUSED_CAM on none)."""
+    N = R * S
+    base = make_batch(R, S)
+    g = torch.Generator().manual_seed(31337 * R + 11 * S + (5 if variant == "b" else 0))
+    q = 8 if variant == "a" else 512
+    feats = torch.randint(-(3 * q) // 4, (3 * q) // 4 + 1, (16, N, 2), generator=g).to(F4) / q
+    if N >= 64:
+        feats[:, 3] = 0.0
+        feats[:, 4] = 0.75
+        feats[:, 5] = -0.75
+    return dict(base, feats=feats.contiguous(), variant=variant)
+
+
+def make_lattice_upstream(batch):
+    """d_density [N] in {0, +-1/4} (exp(h0) multiplies it), d_rgb [N,3], d_logit [N]: multiples of 1/4 within +-1; N >= 64: a few samples, and with R >= 3 a whole
+    ray, zero."""
+    N, R, S = batch["N"], batch["R"], batch["S"]
+    g = torch.Generator().manual_seed(55 * N + 3)
+    dd, dr, dl = (torch.randint(-k, k + 1, sh, generator=g).to(F4) / 4.0 for k, sh in ((1, (N,)), (4, (N, 3)), (4, (N,))))
+    keep = torch.ones(N, dtype=F4)
+    if N >= 64:
+        keep[torch.randint(0, N, (max(2, N // 100),), generator=g)] = 0.0
+        if R >= 3:
+            keep[S:2 * S] = 0.0
+    return dict(dd=(dd * keep).contiguous(), dr=(dr * keep[:, None]).contiguous(), dl=(dl * keep).contiguous())
+
+
+def exact_outputs(f):
+    """forward(..., Arith("bf16" | "f64")) on lattice inputs -> what the device must return bit for bit (float32)."""
+    for k in ("h_pad", "geo", "logit", "ray_bias"):
+        assert torch.equal(f[k].float().double(), f[k]), k + ": not a float32 number"
+    return dict(h_pad=f["h_pad"].float(), geo_out=f["geo"].float(), logit=f["logit"].float(), ray_bias=f["ray_bias"].float())
+
+
+def transcendental_ratios(got, f, sel):
+    """density and rgb against float64 exp / sigmoid of the exact h0 / c3: the formulas of forward_bounds at zero propagated
+    error (density: relative 3 u; rgb: 2 u s (1 - s) + 2 u s) -> worst |err| / bound of each."""
+    d = torch.exp(f["h"][:, 0]) * sel.double()
+    s = torch.sigmoid(f["c3"])
+    return {"density": float(((got["density"].double() - d).abs() / (3 * U * d + 1e-300)).max()),
+            "rgb": float(((got["rgb"].double() - s).abs() / (2 * U * s * (1 - s) + 2 * U * s)).max())}
+
+
+def _stable(v32):
+    """Whether the bf16 rounding of a float32 value survives a perturbation of +-2 ulp."""
+    up = dn = v32
+    for _ in range(2):
+        up = torch.nextafter(up, torch.full_like(up, math.inf))
+        dn = torch.nextafter(dn, torch.full_like(dn, -math.inf))
+    r = v32.bfloat16()
+    return (up.bfloat16() == r) & (dn.bfloat16() == r)
+
+
+def transcendental_grads(up, density, rgb):
+    """d_c3 = (d_rgb s) (1 - s) and d_h0 = d_density density in float32, the kernels' operation order, from the RETURNED
+    float32 rgb and density (density = expf(h0) [selector], and |h0| < 15 on the lattice: expf(clamp(h0)) is the same call)."""
+    return (up["dr"] * rgb) * (1.0 - rgb), up["dd"] * density
+
+
+def guard(up, density, rgb):
+    """The fair-question guard: a sample whose d_h0 (or a d_c3 channel) would round to another bf16 value under +-2 ulp gets its
+    d_density (its d_rgb row) zeroed and stays in the batch.  -> (upstream, guarded samples [N] bool)."""
+    d_c3, d_h0 = transcendental_grads(up, density, rgb)
+    bad_c, bad_h = ~_stable(d_c3).all(1), ~_stable(d_h0)
+    new = dict(dd=(up["dd"] * (~bad_h)).contiguous(), dr=(up["dr"] * (~bad_c)[:, None]).contiguous(), dl=up["dl"])
+    return new, bad_c | bad_h
+
+
+class Sum:
+    """A gradient entry as the sum the device forms: value (float64), sum of |addends|, lowest set bit among the addends,
+    number of addends; extra: a bound term outside the summation's own (the SH columns)."""
+
+    def __init__(self, val, mag, lb, n, extra=None):
+        n = n if torch.is_tensor(n) else torch.full_like(val, float(n))
+        self.val, self.mag, self.lb, self.n, self.extra = val, mag, lb, n, torch.zeros_like(val) if extra is None else extra
+
+    def plus(self, pre, mask=None):
+        """... added to a pre-filled float32 gradient (mask: where the device adds at all)."""
+        pre = pre.double()
+        m = torch.ones_like(pre, dtype=torch.bool) if mask is None else mask
+        return Sum(self.val + pre, self.mag + pre.abs(), torch.where(m, torch.minimum(self.lb, lowbit(pre)), self.lb),
+                   self.n + m.double(), self.extra)
+
+    def exact(self):
+        return bits_of(self.mag, self.lb) < 24.0
+
+    def bound(self):
+        return (self.n - 1).clamp_min(0) * 2.0 ** -23 * self.mag + self.extra
+
+
+def _dw_sum(ar, G, X, layer, keep):
+    Gr = (G if ("g_unrounded", layer) in ar.mut else ar.rnd(G)) * keep
+    Xr = ar.rnd(X)
+    return Sum(Gr.T @ Xr, Gr.abs().T @ Xr.abs(), _minplus(lowbit(Gr), lowbit(Xr)), G.shape[0])
+
+
+def _row_sum(ar, G, pipe, keep):
+    Gq = (ar.rnd(G) if pipe else G) * keep
+    return Sum(Gq.sum(0), Gq.abs().sum(0), lowbit(Gq).amin(0), G.shape[0])
+
+
+def bf16_backward(net, batch, up, ar, semgrad=False, mut=(), returned=None):
+    """The backward of the NS = 1 kernels on lattice inputs (the comment above says where every rounding sits).  returned: the
+    device's float32 (density, rgb), else the reference's own rounded to float32.  -> (forward dict, {layer: (Sum W, Sum b),
+    "embedding": Sum, "d_feats": float64 [16,N,2]}); ar.log (trace) receives the dX chain."""
+    geo, S, N = net["geo"], batch["S"], batch["N"]
+    big = len(SHAPES[net["shape"]][1]) == 2
+    with torch.no_grad():
+        p = params(net, F8)
+        f = forward(net, batch, ar, p=p)
+        assert float(f["h"][:, 0].abs().max()) < 15.0, "the lattice keeps h0 inside trunc_exp's clamp"
+        sel = batch["sel"].double()
+        density, rgb = returned if returned is not None else ((torch.exp(f["h"][:, 0]) * sel).float(), f["rgb"].float())
+        d_c3, d_h0 = transcendental_grads(up, density, rgb)
+        keep = torch.ones(N, 1, dtype=F8)
+        if "drop_tile" in mut:
+            t0 = 16 * ((N // 16) // 2)
+            keep[t0:t0 + 16] = 0.0
+        const, gcol = _cols(geo)
+        ray = torch.arange(N) // S
+        out = {}
+        # colour branch
+        G3 = d_c3.double()
+        r1c, r2c = torch.relu(f["c1"]), torch.relu(f["c2"])
+        out["col2"] = (_dw_sum(ar, G3, r2c, "col2", keep), _row_sum(ar, G3, False, keep))
+        G2 = ar.dx(G3, p["col2"][0], "col2") * (f["c2"] > 0)
+        out["col1"] = (_dw_sum(ar, G2, r1c, "col1", keep), _row_sum(ar, G2, False, keep))
+        G1 = ar.dx(G2, p["col1"][0], "col1") * (f["c1"] > 0)
+        w0 = p["col0"][0]
+        Gq = (ar.rnd(G1) if S >= 16 else G1) * keep                        # what the per-ray sums add up
+        lq = lowbit(Gq)
+        c_ray = f["c_ray"][ray]                                            # [N,48]
+        wg = _dw_sum(ar, G1, f["geo"], "col0", keep)
+        val, mag, lb = (torch.zeros(64, 48 + geo, dtype=F8) for _ in range(3))
+        nn, extra = torch.full((64, 48 + geo), float(N), dtype=F8), torch.zeros(64, 48 + geo, dtype=F8)
+        val[:, gcol], mag[:, gcol], lb[:, gcol] = wg.val, wg.mag, wg.lb
+        val[:, const], mag[:, const] = Gq.T @ c_ray, Gq.abs().T @ c_ray.abs()
+        lb[:, const] = _minplus(lq, lowbit(c_ray))
+        sh_abs = sh16((batch["dirs"].double() + 1.0) / 2.0, absolute=True)[ray]
+        extra[:, :16] = 4 * U * (Gq.abs().T @ sh_abs)
+        nn[:, :16] = N + 1.0
+        out["col0"] = (Sum(val, mag, lb, nn, extra), Sum(Gq.sum(0), Gq.abs().sum(0), lq.amin(0), N))
+        # embedding row c, column k: sum over o and the samples s of camera c's rays of W_c0[o, 16 + geo + k] Gq[s, o]
+        we = w0[:, const[16:]]                                             # [64,32], not rounded
+        cam_s = batch["cam"][ray]
+        z = lambda: torch.zeros(N_IMAGES, 64, dtype=F8)   # noqa: E731
+        g_cam, a_cam = z().index_add_(0, cam_s, Gq), z().index_add_(0, cam_s, Gq.abs())
+        l_cam = torch.stack([lq[cam_s == c].amin(0) if bool((cam_s == c).any()) else torch.full((64,), BIG_LB, dtype=F8)
+                             for c in range(N_IMAGES)])
+        n_cam = 64.0 * torch.bincount(cam_s, minlength=N_IMAGES).double()[:, None].expand(N_IMAGES, 32)
+        out["embedding"] = Sum(g_cam @ we, a_cam @ we.abs(), _minplus(l_cam.T.contiguous(), lowbit(we)), n_cam)
+        Gh = torch.zeros(N, 1 + geo, dtype=F8)
+        Gh[:, 1:] = ar.dx(G1, w0[:, gcol], "col0")
+        # semantic branch
+        sem = [k for k in layer_names(net["shape"]) if k.startswith("sem")]
+        Gs = up["dl"].double()[:, None]
+        if big:                    # W_sem2 v + b_sem2 sum(bf(dlogit)): s3 is not rounded, W_sem2 is the float32 tensor
+            dl, s2 = ar.rnd(Gs) * keep, ar.rnd(f["in_" + sem[-1]])
+            w2, b2 = p[sem[-1]]
+            mag = (dl.abs().T @ s2.abs()) @ w2.abs().T + b2.abs()[None] * dl.abs().sum()
+            lb = lowbit(dl).amin() + torch.minimum(_minplus(lowbit(s2).amin(0, keepdim=True).T.contiguous(), lowbit(w2).T.contiguous()),
+                                                   lowbit(b2)[None])
+            out["head"] = (Sum((dl.T @ s2) @ w2.T + b2[None] * dl.sum(), mag, lb, N * (w2.shape[1] + 1)), _row_sum(ar, Gs, True, keep))
+        else:
+            out["head"] = (_dw_sum(ar, Gs, f["in_head"], "head", keep), _row_sum(ar, Gs, False, keep))
+        Gs = ar.dx(Gs, p["head"][0], "head")
+        for i, k in reversed(list(enumerate(sem))):
+            if i != len(sem) - 1:
+                Gs = Gs * (f["pre_" + k] > 0)
+            out[k] = (_dw_sum(ar, Gs, f["in_" + k], k, keep), _row_sum(ar, Gs, big, keep))
+            if i > 0 or semgrad:
+                Gs = ar.dx(Gs, p[k][0], k)
+        if semgrad:
+            ar._note("add", "d_h", torch.stack([Gh[:, 1:].reshape(-1), Gs.reshape(-1)], 1), torch.ones(1, 2, dtype=F8), Gs)
+            Gh[:, 1:] += Gs
+        Gh[:, 0] = d_h0.double() * sel
+        # base branch
+        r1 = torch.relu(f["a1"])
+        out["base1"] = (_dw_sum(ar, Gh, r1, "base1", keep), _row_sum(ar, Gh, False, keep))
+        Ga = ar.dx(Gh, p["base1"][0], "base1") * (f["a1"] > 0)
+        out["base0"] = (_dw_sum(ar, Ga, f["x"], "base0", keep), _row_sum(ar, Ga, False, keep))
+        out["d_feats"] = x_to_feats(ar.dx(Ga, p["base0"][0], "base0")).contiguous()
+    return f, out
+
+
+def sums_to_tensors(out):
+    """bf16_backward's result as plain gradients (what a device that forms every sum exactly would return)."""
+    return {k: (tuple(s.val for s in v) if isinstance(v, tuple) else v.val if isinstance(v, Sum) else v) for k, v in out.items()}
+
+
+def exact_compare(net, got, ref, prefill=None):
+    """got: the device's (or a mutated emulation's) gradients; ref: bf16_backward's.  -> {tensor: dict(entries, compared =
+    entries with a non-empty sum, exact = of those under the condition, wrong = exact entries that differ, ratio = worst
+    |err| / bound of the others)} for "d_feats", "embedding" and "<layer>.w" / "<layer>.b"."""
+    res = {}
+
+    def one(name, g, s, pre, mask=None):
+        if pre is not None:
+            s = s.plus(pre, mask)
+        g = g.double()
+        ex = s.exact()
+        err = (g - s.val).abs()
+        rest = ~ex
+        ratio = float((err[rest] / s.bound()[rest].clamp_min(1e-300)).max()) if bool(rest.any()) else 0.0
+        res[name] = dict(entries=g.numel(), compared=int((s.mag > 0).sum()), exact=int((ex & (s.mag > 0)).sum()),
+                         wrong=int((err[ex] != 0).sum()), ratio=ratio)
+
+    for k in layer_names(net["shape"]):
+        for j, suffix in enumerate((".w", ".b")):
+            one(k + suffix, got[k][j], ref[k][j], None if prefill is None else prefill[k][j])
+    e = ref["embedding"]
+    one("embedding", got["embedding"], e, None if prefill is None else prefill["embedding"], e.val != 0)   # `if (s != 0) +=`
+    d = got["d_feats"].double()
+    res["d_feats"] = dict(entries=d.numel(), compared=d.numel(), exact=d.numel(), wrong=int((d != ref["d_feats"]).sum()), ratio=0.0)
+    return res
+
+
+def exact_failures(res):
+    return {k: (v["wrong"], round(v["ratio"], 3)) for k, v in res.items() if v["wrong"] or not v["ratio"] <= 1.0}
+
+
+_LPREP = {}
+
+
+def prepare_lattice(shape, R, S, variant="a"):
+    """Network, batch and upstream gradients of a lattice case, made once."""
+    key = (shape, R, S, variant)
+    if key not in _LPREP:
+        batch = make_lattice_batch(R, S, variant)
+        _LPREP[key] = dict(net=make_lattice_net(shape, variant), batch=batch, up=make_lattice_upstream(batch))
+    return _LPREP[key]

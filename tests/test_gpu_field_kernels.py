@@ -2,7 +2,8 @@
 field_mlp.hip, field_mlp_bf16.hip, field_mlp_bwd.hip, field_mlp_bwd_pw.hip — against the float64 reference of
 tests/field_reference.py (plain torch, not oracle/ns_torch.py's float32 path): per sample, per weight entry and per embedding
 row, never against a batch or tensor maximum, for both built shapes (`fruit_nerf`: geo 15, semantic 2 x 64; `fruit_nerf_big`:
-geo 30, semantic 3 x 128) in the fp32 and bf16x3 arithmetics.  Plain bf16 gets the structural assertions only.
+geo 30, semantic 3 x 128) in the fp32 and bf16x3 arithmetics.  Plain bf16 gets the structural assertions here; its numerics are
+held bit for bit to the rounded-operand reference on lattice inputs by tests/test_gpu_field_bf16_exact.py.
 
 Isolation: the features [16][N][2] (uniform in +-0.8 + an all-zero row and rows of extremes), the selector, directions and
 cameras are generated on the CPU; the network is raw tensors behind an fnr_field_net (Kaiming-uniform weights, non-zero biases
