@@ -616,6 +616,93 @@ def tsdf_mesh(vol: TsdfVolumeArg):
     return vertices, faces, normals, colors
 
 
+def _mesh_faces(faces: Tensor, who: str) -> Tensor:
+    L.require_gpu_tensor(faces, f"{who} faces")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{who}: faces are int32 [F,3], got {faces.dtype} {tuple(faces.shape)}")
+    return faces.contiguous()
+
+
+def _workspace(nbytes: int, dev) -> Tensor:
+    """nbytes of device memory, 16-byte aligned (the allocator's granule is larger)."""
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def mesh_components(faces: Tensor, n_vertices: int):
+    """Connected components over shared edges (fnr_mesh_components; the contract is in include/fruitnerf_hip.h).
+    faces int32 [F,3] with indices in [0, n_vertices) -> (face_component int32 [F], n_components, workspace); the
+    workspace holds the edge table mesh_component_stats needs.  F == 0 launches nothing."""
+    faces = _mesh_faces(faces, "mesh_components")
+    dev, F = faces.device, faces.shape[0]
+    labels = torch.empty(F, dtype=torch.int32, device=dev)
+    if F == 0:
+        return labels, 0, None
+    lib = L.load()
+    ws = _workspace(lib.fnr_mesh_workspace_bytes(F), dev)
+    counts = torch.zeros(1, dtype=torch.int64, device=dev)
+    L.check(lib.fnr_mesh_components(int(n_vertices), F, L.ptr(faces), L.ptr(labels), L.ptr(counts), L.ptr(ws),
+                                    ws.numel() * 8, L.stream_ptr(dev)), "mesh_components")
+    return labels, int(counts.item()), ws
+
+
+def mesh_component_stats(vertices: Tensor, faces: Tensor, face_component: Tensor, n_components: int, workspace) -> dict:
+    """Per-component statistics (fnr_mesh_component_stats) -> dict of device tensors: n_faces, boundary_edges,
+    nonmanifold_edges int32 [C]; lo, hi float32 [C,3]; area, volume float64 [C]; moment float64 [C,3].  `workspace`
+    is the one mesh_components returned for these faces."""
+    faces = _mesh_faces(faces, "mesh_component_stats")
+    L.require_gpu_tensor(vertices, "mesh_component_stats vertices")
+    dev, F, C_ = faces.device, faces.shape[0], int(n_components)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or vertices.device != dev \
+            or face_component.shape != (F,) or face_component.dtype != torch.int32 or face_component.device != dev:
+        raise ValueError("mesh_component_stats: vertices are float32 [V,3] and face_component int32 [F], on the faces' device")
+    vertices, face_component = vertices.contiguous(), face_component.contiguous()
+    out = {"n_faces": torch.zeros(C_, dtype=torch.int32, device=dev),
+           "boundary_edges": torch.zeros(C_, dtype=torch.int32, device=dev),
+           "nonmanifold_edges": torch.zeros(C_, dtype=torch.int32, device=dev),
+           "lo": torch.empty(C_, 3, device=dev), "hi": torch.empty(C_, 3, device=dev),
+           "area": torch.empty(C_, dtype=torch.float64, device=dev),
+           "volume": torch.empty(C_, dtype=torch.float64, device=dev),
+           "moment": torch.empty(C_, 3, dtype=torch.float64, device=dev)}
+    if F == 0:
+        if C_ != 0:
+            raise ValueError("mesh_component_stats: a mesh without faces has no components")
+        return out
+    if workspace is None:
+        raise ValueError("mesh_component_stats: needs the workspace mesh_components returned")
+    arg = L.fnr_mesh_stats(*[out[k].data_ptr() for k in ("n_faces", "boundary_edges", "nonmanifold_edges", "lo", "hi",
+                                                        "area", "volume", "moment")])
+    L.check(L.load().fnr_mesh_component_stats(vertices.shape[0], F, L.ptr(vertices), L.ptr(faces), L.ptr(face_component),
+                                              C_, L.ptr(workspace), workspace.numel() * 8, C.byref(arg),
+                                              L.stream_ptr(dev)), "mesh_component_stats")
+    return out
+
+
+def mesh_select(faces: Tensor, n_vertices: int, face_keep: Tensor):
+    """Order-preserving selection (fnr_mesh_select_count, one host read of the two counts, fnr_mesh_select_emit).
+    face_keep [F] bool / uint8 -> (new_faces int32 [F',3], vertex_ids int32 [V'] ascending, face_ids int32 [F']
+    ascending)."""
+    faces = _mesh_faces(faces, "mesh_select")
+    dev, F, V = faces.device, faces.shape[0], int(n_vertices)
+    if face_keep.shape != (F,):
+        raise ValueError(f"mesh_select: face_keep is [F] = [{F}], got {tuple(face_keep.shape)}")
+    L.require_gpu_tensor(face_keep, "mesh_select face_keep")
+    empty = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)          # noqa: E731
+    if F == 0:
+        return empty(0, 3), empty(0), empty(0)
+    keep = (face_keep != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    lib = L.load()
+    ws = _workspace(lib.fnr_mesh_select_workspace_bytes(V, F), dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    L.check(lib.fnr_mesh_select_count(V, F, L.ptr(faces), L.ptr(keep), L.ptr(counts), L.ptr(ws), ws.numel() * 8,
+                                      L.stream_ptr(dev)), "mesh_select_count")
+    n_new_vertices, n_new_faces = counts.tolist()
+    new_faces, vertex_ids, face_ids = empty(n_new_faces, 3), empty(n_new_vertices), empty(n_new_faces)
+    L.check(lib.fnr_mesh_select_emit(V, F, L.ptr(faces), L.ptr(ws), ws.numel() * 8, n_new_vertices, n_new_faces,
+                                     L.ptr(new_faces), L.ptr(vertex_ids), L.ptr(face_ids), L.stream_ptr(dev)),
+            "mesh_select_emit")
+    return new_faces, vertex_ids, face_ids
+
+
 # ---- training ---------------------------------------------------------------------------------------
 
 

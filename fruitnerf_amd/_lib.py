@@ -124,6 +124,13 @@ def tsdf_mesh_workspace_bytes(n_nodes: int) -> int:
     return 4 * n_nodes + 16 * ((n_nodes + 255) // 256) + 16
 
 
+class fnr_mesh_stats(C.Structure):
+    # output arrays of fnr_mesh_component_stats, n_components entries each (lo / hi / moment: [C][3])
+    _fields_ = [("n_faces", C.c_void_p), ("boundary_edges", C.c_void_p), ("nonmanifold_edges", C.c_void_p),
+                ("lo", C.c_void_p), ("hi", C.c_void_p), ("area", C.c_void_p), ("volume", C.c_void_p),
+                ("moment", C.c_void_p)]
+
+
 class fnr_image_set(C.Structure):
     _fields_ = [("n_images", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("images", C.c_void_p),
                 ("masks", C.c_void_p), ("c2w", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float),
@@ -285,6 +292,12 @@ SIGNATURES = {
                                 _vp]),
     "fnr_tsdf_mesh_count": (_i, [P(fnr_tsdf_volume), _vp, _vp, C.c_size_t, _vp]),
     "fnr_tsdf_mesh_emit": (_i, [P(fnr_tsdf_volume), _vp, C.c_size_t, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "fnr_mesh_workspace_bytes": (C.c_size_t, [_i64]),
+    "fnr_mesh_components": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_mesh_component_stats": (_i, [_i64, _i64, _vp, _vp, _vp, _i64, _vp, C.c_size_t, P(fnr_mesh_stats), _vp]),
+    "fnr_mesh_select_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "fnr_mesh_select_count": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_mesh_select_emit": (_i, [_i64, _i64, _vp, _vp, C.c_size_t, _i64, _i64, _vp, _vp, _vp, _vp]),
     "fnr_field_normals": (_i, [P(fnr_field_net), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fnr_render_normals": (_i, [_i64, _i, _vp, _vp, _i, _vp, _vp]),
     "fnr_cloud_knn_workspace_bytes": (C.c_size_t, [_i64, C.c_int32]),

@@ -229,7 +229,8 @@ def generate_point_cloud(pipeline, num_points: int = 1_000_000, remove_outliers:
 def export_tsdf_mesh(pipeline, output_dir, downscale_factor: int = 2, depth_output_name: str = "depth",
                      rgb_output_name: str = "rgb", resolution=128, batch_size: int = 10, use_bounding_box: bool = True,
                      bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
-                     semantic_threshold: Optional[float] = None):
+                     semantic_threshold: Optional[float] = None, min_component_faces: Optional[int] = None,
+                     largest_components: Optional[int] = None):
     """Nerfstudio's ExportTSDFMesh.main / export_tsdf_mesh (`ns-export tsdf`; its fields as recalled): every camera of
     `pipeline.datamanager.train_dataset.cameras` is rendered at 1 / downscale_factor of its resolution (pinhole: the
     fusion does not model distortion, so the rays are generated without it), its `depth_output_name` / `rgb_output_name`
@@ -238,7 +239,31 @@ def export_tsdf_mesh(pipeline, output_dir, downscale_factor: int = 2, depth_outp
     tetrahedra mesh is written to <output_dir>/tsdf_mesh.ply (ply.write_triangle_mesh).  -> the TSDF.
 
     semantic_threshold (this project's addition): pixels whose sigmoid(outputs["semantics"]) is below it are left out
-    of the fusion, so the mesh is the fruit alone — what the counting stage looks at.  A missing output is a KeyError."""
+    of the fusion, so the mesh is the fruit alone — what the counting stage looks at.  A missing output is a KeyError.
+
+    min_component_faces / largest_components (what users of `ns-export tsdf` do next with Open3D's
+    cluster_connected_triangles): the written mesh loses its connected components of fewer than min_component_faces
+    faces, then keeps only its largest_components largest (export/mesh.py::TriangleMesh).  With both None the function
+    makes the calls and writes the bytes it always did.  The returned TSDF is not affected."""
+    tsdf = _fuse_tsdf(pipeline, downscale_factor, depth_output_name, rgb_output_name, resolution, batch_size, use_bounding_box,
+                      bounding_box_min, bounding_box_max, semantic_threshold)
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    if min_component_faces is None and largest_components is None:
+        tsdf.export(str(out / "tsdf_mesh.ply"))
+        return tsdf
+    mesh = tsdf.get_triangle_mesh()
+    if min_component_faces is not None:
+        mesh = mesh.remove_small_components(int(min_component_faces))
+    if largest_components is not None:
+        mesh = mesh.keep_largest_components(int(largest_components))
+    mesh.write(out / "tsdf_mesh.ply")
+    return tsdf
+
+
+def _fuse_tsdf(pipeline, downscale_factor, depth_output_name, rgb_output_name, resolution, batch_size, use_bounding_box,
+               bounding_box_min, bounding_box_max, semantic_threshold):
+    """The fusion of export_tsdf_mesh: every training camera rendered as a pinhole and fused.  -> the TSDF."""
     from ..cameras.cameras import Cameras, _column, _image_size, generate_rays_of
     from .tsdf import TSDF
     if int(downscale_factor) < 1 or int(batch_size) < 1:
@@ -273,10 +298,87 @@ def export_tsdf_mesh(pipeline, output_dir, downscale_factor: int = 2, depth_outp
             mask = torch.sigmoid(torch.stack(images["semantics"])[..., 0]) >= float(semantic_threshold)
         tsdf.integrate(cameras.camera_to_worlds[batch.start:batch.stop], intrinsics[batch.start:batch.stop],
                        torch.stack(images[depth_output_name])[..., 0], torch.stack(images[rgb_output_name]), mask)
+    return tsdf
+
+
+class FruitMeshes:
+    """What export_fruit_meshes returns: `mesh` (the fruit faces, small components removed), `face_component` int32 [F]
+    and `stats` (export/mesh.py::ComponentStats) of that mesh, `vertex_probability` float32 [V] of the FULL mesh `full`,
+    and the `tsdf`; len() is the number of fruits."""
+
+    def __init__(self, mesh, face_component, stats, full, vertex_probability, tsdf):
+        self.mesh, self.face_component, self.stats = mesh, face_component, stats
+        self.full, self.vertex_probability, self.tsdf = full, vertex_probability, tsdf
+
+    def __len__(self) -> int:
+        return len(self.stats)
+
+    def records(self):
+        """One dict per fruit in component order: faces, area, volume, closed, centroid, lo, hi (host numbers)."""
+        s = self.stats
+        cols = {k: getattr(s, k).cpu().tolist() for k in ("n_faces", "area", "volume", "closed", "centroid", "lo", "hi")}
+        return [{"faces": int(cols["n_faces"][c]), "area": cols["area"][c], "volume": cols["volume"][c],
+                 "closed": bool(cols["closed"][c]), "centroid": cols["centroid"][c], "lo": cols["lo"][c],
+                 "hi": cols["hi"][c]} for c in range(len(s))]
+
+
+def vertex_fruit_probability(model, vertices, normals):
+    """sigmoid of the field's semantic logit at every vertex [V], through the public FruitField.forward on a generic
+    [V] RaySamples: origin = the vertex, direction = -normal ((0, 0, -1) where the normal is zero), starts = ends = 0.
+    The model is put in eval mode for the query (the mean appearance embedding; camera index 0 is supplied for a field
+    that asks for one) and restored."""
+    from ..fruit_field import FieldHeadNames
+    from ..rays import Frustums, RaySamples
+    n = vertices.shape[0]
+    if n == 0:
+        return torch.empty(0, device=vertices.device)
+    directions = -normals
+    flat = (normals == 0).all(dim=1)
+    directions[flat] = torch.tensor([0.0, 0.0, -1.0], device=vertices.device)
+    zeros = torch.zeros(n, 1, device=vertices.device)
+    samples = RaySamples(Frustums(vertices, directions, zeros, zeros.clone(), zeros.clone()),
+                         camera_indices=torch.zeros(n, 1, dtype=torch.int32, device=vertices.device))
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            logit = model.field.forward(samples)[FieldHeadNames.SEMANTICS]
+    finally:
+        model.train(was_training)
+    return torch.sigmoid(logit.reshape(n).float())
+
+
+def export_fruit_meshes(pipeline, output_dir, semantic_threshold: float = 0.9, min_component_faces: int = 24,
+                        **tsdf_arguments):
+    """One surface patch per fruit, with its size.  The whole scene is fused (export_tsdf_mesh's fusion with
+    `tsdf_arguments`: downscale_factor, resolution, batch_size, the bounding box, the output names — NOT its
+    semantic_threshold: masking pixels leaves their nodes unobserved, unobserved nodes count as inside, and the mesh is
+    then sheets between carved and never-seen space, not fruit surfaces), the mesh extracted, and every vertex labelled
+    with the field's own fruit probability (vertex_fruit_probability).  The faces whose three vertices all have
+    probability >= semantic_threshold (0.9: the reference's threshold, fruit_nerf.py:264) are kept, split into connected
+    components, and the components of fewer than min_component_faces faces dropped.  Writes <output_dir>/fruit_mesh.ply
+    and <output_dir>/fruits.json — one record per fruit in component order: faces, area, volume (signed; meaningful where
+    closed), closed, centroid, lo, hi — and returns a FruitMeshes."""
+    import json
+    names = ("downscale_factor", "depth_output_name", "rgb_output_name", "resolution", "batch_size", "use_bounding_box",
+             "bounding_box_min", "bounding_box_max")
+    defaults = (2, "depth", "rgb", 128, 10, True, (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
+    unknown = set(tsdf_arguments) - set(names)
+    if unknown:
+        raise TypeError(f"export_fruit_meshes: unexpected arguments {sorted(unknown)}")
+    tsdf = _fuse_tsdf(pipeline, *[tsdf_arguments.get(k, d) for k, d in zip(names, defaults)], None)
+    full = tsdf.get_triangle_mesh()
+    probability = vertex_fruit_probability(pipeline.model, full.vertices, full.normals)
+    fruit = full.select_by_vertex_mask(probability >= float(semantic_threshold))
+    fruit = fruit.remove_small_components(int(min_component_faces))
+    face_component, _ = fruit.connected_components()
+    result = FruitMeshes(fruit, face_component, fruit.component_stats(), full, probability, tsdf)
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
-    tsdf.export(str(out / "tsdf_mesh.ply"))
-    return tsdf
+    fruit.write(out / "fruit_mesh.ply")
+    with open(out / "fruits.json", "w") as fh:
+        json.dump(result.records(), fh, indent=1)
+    return result
 
 
 def export_point_cloud(pipeline, output_dir, **kwargs):

@@ -75,6 +75,12 @@ class TSDF:
         ascend by edge key, faces by (cell, tetrahedron, triangle): the same volume gives the same arrays."""
         return K.tsdf_mesh(self._arg)
 
+    def get_triangle_mesh(self):
+        """get_mesh() as an export.mesh.TriangleMesh (connected components, selection, writing)."""
+        from .mesh import TriangleMesh
+        vertices, faces, normals, colors = self.get_mesh()
+        return TriangleMesh(vertices, faces, normals, colors)
+
     def export(self, path: str) -> None:
         from . import ply
         vertices, faces, normals, colors = self.get_mesh()

@@ -29,7 +29,8 @@ extern "C" {
 
 /* 13 also covers the per-image camera table (fnr_camera_table, the fnr_*_cams entry points and fnr_camera_rays): pure
  * additions — no existing symbol or struct changed, so a caller built against the earlier 13 runs unchanged.  The TSDF
- * mesh export (fnr_tsdf_volume, the three fnr_tsdf_* entry points) is an addition of the same kind. */
+ * mesh export (fnr_tsdf_volume, the three fnr_tsdf_* entry points) is an addition of the same kind, and so is the mesh
+ * connectivity (fnr_mesh_stats, the fnr_mesh_* entry points). */
 #define FNR_ABI_VERSION 13
 #define FNR_MAX_LEVELS 16
 #define FNR_MAX_SEM_LAYERS 4
@@ -980,6 +981,80 @@ int fnr_tsdf_mesh_count(const fnr_tsdf_volume* volume, uint64_t* counts, void* w
                         void* stream);
 int fnr_tsdf_mesh_emit(const fnr_tsdf_volume* volume, const void* workspace, size_t workspace_bytes, int64_t n_vertices,
                        int64_t n_faces, float* vertices, float* normals, float* colors, int32_t* faces, void* stream);
+
+/* ---- triangle-mesh connectivity: components, their statistics, selection (csrc/mesh.hip) ------- */
+/* What users of a TSDF mesh do next with Open3D — cluster_connected_triangles(), remove_triangles_by_mask(),
+ * select_by_index() — as recalled; Open3D is not available to this project, so THIS text is the contract
+ * (tests/mesh_components_reference.py restates it in float64).  Pure additions to ABI 13.
+ *
+ * Mesh.  vertices [V][3] fp32, faces [F][3] int32 with indices in [0, V); V, F <= 2^31 - 1; DEVICE arrays.  F == 0 is
+ * valid everywhere and launches nothing.  An index outside [0, V) is found on the device and refused (see Errors).
+ *
+ * Connectivity.  Two faces are connected iff they share an undirected edge {a, b} with a != b; sharing only a vertex does
+ * not connect them.  Each face contributes three edge incidences, one per slot s (the edge from index s to index
+ * (s + 1) % 3); a slot with a == b (a face that repeats an index) contributes nothing: no incidence, no connection.  An
+ * edge with three or more incidences connects all its faces; a face listed twice connects to itself and to its copy.  A
+ * component is numbered by the rank of its smallest face index among all components' smallest face indices: component 0
+ * holds face 0 — the order a sweep from face 0 upwards assigns.  fnr_mesh_components writes face_component [F] int32 and
+ * counts[0] (DEVICE uint64) = the number of components, and leaves the edge table in `workspace` (>=
+ * fnr_mesh_workspace_bytes(n_faces) bytes, 16-byte aligned) for fnr_mesh_component_stats.  No vertex array is read: edge
+ * keys are 64 bits, (min(a, b) << 32) | max(a, b), so V may be 2^31 - 1 whatever F is.
+ *   How.  An open-addressing table of at least 4 F slots (key, smallest face of the edge, incidence count), slots claimed
+ * by 64-bit compare-and-swap at device scope; union-find over faces in which every face of an edge is united with the
+ * edge's smallest face and a hook always puts the larger root under the smaller, so a component's root is its smallest
+ * face; the trees are flattened in a later launch (the launch boundary is the visibility guarantee) and the roots numbered
+ * by an exclusive scan over "is a root".  No workgroup waits for another; the only retry loops are compare-and-swap
+ * retries; every probe sequence is bounded by the table size and every parent chain by F.
+ *
+ * Statistics of component c, over its faces in the mesh (fnr_mesh_component_stats, arrays of n_components entries):
+ *   exact integers: n_faces; boundary_edges — edges with exactly one incidence; nonmanifold_edges — edges with three or
+ *   more (an edge belongs to the component of its faces; all faces of an edge are in one component by construction);
+ *   exact fp32: lo[3], hi[3] over the vertices the component's faces reference;
+ *   float64 raw sums, the vertices converted to float64 first, every operation rounded (no fused multiply-add):
+ *     area   = sum |(v1 - v0) x (v2 - v0)| / 2,
+ *     volume = sum v0 . (v1 x v2) / 6   — signed: positive for outward normals, and meaningful only where
+ *              boundary_edges == nonmanifold_edges == 0,
+ *     moment[3] = sum area_f * (v0 + v1 + v2) / 3   (the surface centroid is moment / area; the caller divides).
+ *   Orientation consistency is NOT checked: a closed component whose faces disagree in winding has a meaningless volume.
+ *   The float64 sums are the same bits for the same mesh, run to run: no floating-point atomics; the faces are grouped by
+ *   component with a stable radix sort (count -> scan -> ordered emit per 8-bit digit, so a component's faces ascend) and
+ *   added by a fixed-shape segmented reduction — runs of one component inside blocks of 256 sorted positions in position
+ *   order, a component's block records by lane l = l, l + 64, ... in order, the 64 lanes by a butterfly.
+ *   The call needs the workspace fnr_mesh_components left for these faces and its n_components; it reads the workspace's
+ *   header back first (a synchronisation) and refuses an n_components that is inconsistent with counts.
+ *
+ * Selection.  Given face_keep [F] uint8, the new mesh keeps the faces with a non-zero byte in their old order and the
+ * vertices those faces reference in their old order.  fnr_mesh_select_count writes counts[2] (DEVICE uint64) = number of
+ * kept vertices, number of kept faces, and leaves both index maps in `workspace` (>= fnr_mesh_select_workspace_bytes
+ * bytes, 16-byte aligned); the caller reads the counts, allocates, and calls fnr_mesh_select_emit with the SAME workspace
+ * and faces: new_faces [F'][3] re-indexed, vertex_ids [V'] ascending old vertex indices, face_ids [F'] ascending old face
+ * indices (the caller gathers positions and attributes with vertex_ids).  Entries beyond the given sizes are not written.
+ *
+ * Errors.  Arguments are checked on the host before anything is launched.  A bad index or label and any exceeded bound set
+ * an error word in the workspace; every entry point here that launches reads it back before it returns (a
+ * synchronisation of `stream`) and then fails with FNR_ERR_INVALID and a message in fnr_last_error. */
+typedef struct fnr_mesh_stats {
+  int32_t* n_faces;           /* [C] */
+  int32_t* boundary_edges;    /* [C] */
+  int32_t* nonmanifold_edges; /* [C] */
+  float* lo;                  /* [C][3] */
+  float* hi;                  /* [C][3] */
+  double* area;               /* [C] */
+  double* volume;             /* [C] */
+  double* moment;             /* [C][3] */
+} fnr_mesh_stats;
+size_t fnr_mesh_workspace_bytes(int64_t n_faces);
+int fnr_mesh_components(int64_t n_vertices, int64_t n_faces, const int32_t* faces, int32_t* face_component,
+                        uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int fnr_mesh_component_stats(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                             const int32_t* face_component, int64_t n_components, void* workspace,
+                             size_t workspace_bytes, const fnr_mesh_stats* out, void* stream);
+size_t fnr_mesh_select_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int fnr_mesh_select_count(int64_t n_vertices, int64_t n_faces, const int32_t* faces, const uint8_t* face_keep,
+                          uint64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int fnr_mesh_select_emit(int64_t n_vertices, int64_t n_faces, const int32_t* faces, const void* workspace,
+                         size_t workspace_bytes, int64_t n_new_vertices, int64_t n_new_faces, int32_t* new_faces,
+                         int32_t* vertex_ids, int32_t* face_ids, void* stream);
 
 /* ---- point-cloud front-end of the counting stage ---------------------------------------------- */
 /* FruitClustering.cluster (clustering/clustering_base.py:183-207) runs, on the exported cloud, Open3D's
