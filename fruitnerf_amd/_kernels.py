@@ -703,6 +703,129 @@ def mesh_select(faces: Tensor, n_vertices: int, face_keep: Tensor):
     return new_faces, vertex_ids, face_ids
 
 
+MESH_ROWS_NEIGHBOURS, MESH_ROWS_FACES = 0, 1                   # FNR_MESH_ROWS_* of include/fruitnerf_hip.h
+MESH_WEIGHTS = {"uniform": 0, "inverse_distance": 1}           # FNR_MESH_WEIGHTS_*
+
+
+def _mesh_vertices(vertices: Tensor, dev, who: str) -> Tensor:
+    L.require_gpu_tensor(vertices, f"{who} vertices")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or vertices.device != dev:
+        raise ValueError(f"{who}: vertices are float32 [V,3] on the mesh's device, got {vertices.dtype} "
+                         f"{tuple(vertices.shape)}")
+    return vertices.contiguous()
+
+
+def _mesh_rows(offsets: Tensor, entries: Tensor, n_rows: int, who: str):
+    L.require_gpu_tensor(offsets, f"{who} offsets")
+    if offsets.shape != (n_rows + 1,) or offsets.dtype != torch.int32 or entries.dim() != 1 \
+            or entries.dtype != torch.int32 or entries.device != offsets.device:
+        raise ValueError(f"{who}: rows are offsets int32 [{n_rows + 1}] and entries int32 [E] on one device")
+    return offsets.contiguous(), entries.contiguous()
+
+
+def mesh_vertex_rows(faces: Tensor, n_vertices: int, kind: int):
+    """Per-vertex rows (fnr_mesh_vertex_rows_count, one host read of the count, fnr_mesh_vertex_rows_emit).  kind
+    MESH_ROWS_NEIGHBOURS: row a = every b != a sharing a face with a; MESH_ROWS_FACES: row a = every face listing a; each
+    once, ascending.  -> (offsets int32 [V + 1], entries int32 [E])."""
+    faces = _mesh_faces(faces, "mesh_vertex_rows")
+    dev, F, V = faces.device, faces.shape[0], int(n_vertices)
+    if kind not in (MESH_ROWS_NEIGHBOURS, MESH_ROWS_FACES):
+        raise ValueError(f"mesh_vertex_rows: kind {kind} is neither MESH_ROWS_NEIGHBOURS nor MESH_ROWS_FACES")
+    if F == 0:
+        return torch.zeros(V + 1, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    lib = L.load()
+    ws = _workspace(lib.fnr_mesh_vertex_rows_workspace_bytes(V, F, kind), dev)
+    counts = torch.zeros(1, dtype=torch.int64, device=dev)
+    L.check(lib.fnr_mesh_vertex_rows_count(V, F, L.ptr(faces), kind, L.ptr(counts), L.ptr(ws), ws.numel() * 8,
+                                           L.stream_ptr(dev)), "mesh_vertex_rows_count")
+    E = int(counts.item())
+    offsets = torch.empty(V + 1, dtype=torch.int32, device=dev)
+    entries = torch.empty(E, dtype=torch.int32, device=dev)
+    L.check(lib.fnr_mesh_vertex_rows_emit(V, F, kind, L.ptr(ws), ws.numel() * 8, E, L.ptr(offsets), L.ptr(entries),
+                                          L.stream_ptr(dev)), "mesh_vertex_rows_emit")
+    return offsets, entries
+
+
+def mesh_smooth(vertices: Tensor, offsets: Tensor, neighbours: Tensor, factors, weights: str = "inverse_distance") -> Tensor:
+    """fnr_mesh_smooth: one step per factor, p' = p + factor * (weighted mean of the row - p), in float64 across the
+    steps.  -> float32 [V,3]."""
+    vertices = _mesh_vertices(vertices, vertices.device, "mesh_smooth")
+    if weights not in MESH_WEIGHTS:
+        raise ValueError(f"mesh_smooth: weights is one of {sorted(MESH_WEIGHTS)}, got {weights!r}")
+    dev, V = vertices.device, vertices.shape[0]
+    offsets, neighbours = _mesh_rows(offsets, neighbours, V, "mesh_smooth")
+    out = torch.empty_like(vertices)
+    if V == 0:
+        return out
+    factors = [float(f) for f in factors]
+    lib = L.load()
+    ws = _workspace(lib.fnr_mesh_smooth_workspace_bytes(V), dev)
+    L.check(lib.fnr_mesh_smooth(V, L.ptr(vertices), neighbours.shape[0], L.ptr(offsets), L.ptr(neighbours), len(factors),
+                                (C.c_double * max(len(factors), 1))(*factors), MESH_WEIGHTS[weights], L.ptr(out), L.ptr(ws),
+                                ws.numel() * 8, L.stream_ptr(dev)), "mesh_smooth")
+    return out
+
+
+def mesh_vertex_normals(vertices: Tensor, faces: Tensor, offsets: Tensor, face_rows: Tensor) -> Tensor:
+    """fnr_mesh_vertex_normals: area-weighted vertex normals over the MESH_ROWS_FACES rows -> float32 [V,3]."""
+    faces = _mesh_faces(faces, "mesh_vertex_normals")
+    vertices = _mesh_vertices(vertices, faces.device, "mesh_vertex_normals")
+    dev, V = faces.device, vertices.shape[0]
+    offsets, face_rows = _mesh_rows(offsets, face_rows, V, "mesh_vertex_normals")
+    normals = torch.empty_like(vertices)
+    if V == 0:
+        return normals
+    ws = _workspace(64, dev)
+    L.check(L.load().fnr_mesh_vertex_normals(V, faces.shape[0], L.ptr(vertices), L.ptr(faces), face_rows.shape[0],
+                                             L.ptr(offsets), L.ptr(face_rows), L.ptr(normals), L.ptr(ws), 64,
+                                             L.stream_ptr(dev)), "mesh_vertex_normals")
+    return normals
+
+
+def mesh_cluster(vertices: Tensor, faces: Tensor, voxel_size: float, origin) -> dict:
+    """Vertex clustering (fnr_mesh_cluster_count, one host read of the two counts, fnr_mesh_cluster_emit).  origin: three
+    host numbers.  -> dict of device tensors: vertex_cluster int32 [V]; offsets int32 [V' + 1] and members int32 [V]
+    (the cluster rows); new_faces int32 [F',3] and face_ids int32 [F']."""
+    faces = _mesh_faces(faces, "mesh_cluster")
+    vertices = _mesh_vertices(vertices, faces.device, "mesh_cluster")
+    dev, V, F = faces.device, vertices.shape[0], faces.shape[0]
+    empty = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)          # noqa: E731
+    lib = L.load()
+    ws = _workspace(lib.fnr_mesh_cluster_workspace_bytes(V, F), dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    vertex_cluster = empty(V)
+    o = (C.c_double * 3)(*[float(x) for x in origin])
+    L.check(lib.fnr_mesh_cluster_count(V, F, L.ptr(vertices), L.ptr(faces), float(voxel_size), o, L.ptr(vertex_cluster),
+                                       L.ptr(counts), L.ptr(ws), ws.numel() * 8, L.stream_ptr(dev)), "mesh_cluster_count")
+    n_clusters, n_new_faces = counts.tolist() if V + F > 0 else (0, 0)
+    out = {"vertex_cluster": vertex_cluster, "offsets": torch.zeros(n_clusters + 1, dtype=torch.int32, device=dev),
+           "members": empty(V), "new_faces": empty(n_new_faces, 3), "face_ids": empty(n_new_faces)}
+    if V > 0:
+        L.check(lib.fnr_mesh_cluster_emit(V, F, L.ptr(faces), L.ptr(ws), ws.numel() * 8, n_clusters, n_new_faces,
+                                          L.ptr(out["offsets"]), L.ptr(out["members"]), L.ptr(out["new_faces"]),
+                                          L.ptr(out["face_ids"]), L.stream_ptr(dev)), "mesh_cluster_emit")
+    return out
+
+
+def mesh_rows_mean(offsets: Tensor, members: Tensor, values: Tensor) -> Tensor:
+    """fnr_mesh_rows_mean: float64 mean of values [N,3] over every row's members, rounded -> float32 [rows,3]."""
+    L.require_gpu_tensor(values, "mesh_rows_mean values")
+    if values.dim() != 2 or values.shape[1] != 3 or values.dtype != torch.float32 or offsets.dim() != 1 or offsets.shape[0] < 1:
+        raise ValueError("mesh_rows_mean: values are float32 [N,3] and offsets int32 [rows + 1]")
+    R = offsets.shape[0] - 1
+    offsets, members = _mesh_rows(offsets, members, R, "mesh_rows_mean")
+    if values.device != offsets.device:
+        raise ValueError("mesh_rows_mean: values and rows are on one device")
+    dev, values = values.device, values.contiguous()
+    out = torch.empty(R, 3, device=dev)
+    if R == 0:
+        return out
+    ws = _workspace(64, dev)
+    L.check(L.load().fnr_mesh_rows_mean(R, members.shape[0], L.ptr(offsets), L.ptr(members), values.shape[0], L.ptr(values),
+                                        L.ptr(out), L.ptr(ws), 64, L.stream_ptr(dev)), "mesh_rows_mean")
+    return out
+
+
 # ---- training ---------------------------------------------------------------------------------------
 
 

@@ -298,6 +298,16 @@ SIGNATURES = {
     "fnr_mesh_select_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "fnr_mesh_select_count": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fnr_mesh_select_emit": (_i, [_i64, _i64, _vp, _vp, C.c_size_t, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "fnr_mesh_vertex_rows_workspace_bytes": (C.c_size_t, [_i64, _i64, C.c_int32]),
+    "fnr_mesh_vertex_rows_count": (_i, [_i64, _i64, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_mesh_vertex_rows_emit": (_i, [_i64, _i64, C.c_int32, _vp, C.c_size_t, _i64, _vp, _vp, _vp]),
+    "fnr_mesh_smooth_workspace_bytes": (C.c_size_t, [_i64]),
+    "fnr_mesh_smooth": (_i, [_i64, _vp, _i64, _vp, _vp, C.c_int32, P(C.c_double), C.c_int32, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_mesh_vertex_normals": (_i, [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_mesh_cluster_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "fnr_mesh_cluster_count": (_i, [_i64, _i64, _vp, _vp, C.c_double, P(C.c_double), _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fnr_mesh_cluster_emit": (_i, [_i64, _i64, _vp, _vp, C.c_size_t, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "fnr_mesh_rows_mean": (_i, [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fnr_field_normals": (_i, [P(fnr_field_net), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fnr_render_normals": (_i, [_i64, _i, _vp, _vp, _i, _vp, _vp]),
     "fnr_cloud_knn_workspace_bytes": (C.c_size_t, [_i64, C.c_int32]),

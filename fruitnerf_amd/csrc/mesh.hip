@@ -7,12 +7,11 @@
 // every probe sequence and pointer chase is bounded by the table size / the face count; a bound that is exceeded, an index
 // outside [0, V) or a label outside [0, C) sets a bit in the workspace's error word, which the entry point reads back.
 #include "common.hpp"
+#include "mesh_common.hpp"
 #include "sequencer.hpp"
 
 namespace fnr {
 
-constexpr int MESH_BLOCK = 256;
-constexpr int SCAN_THREADS = 1024, SCAN_ITEMS = 8;
 constexpr unsigned long long EDGE_EMPTY = ~0ull;     // never a key: a key's halves are both below 2^31
 constexpr int NO_FACE = 0x7fffffff;
 constexpr unsigned OFF_UNSET = 0xffffffffu;
@@ -88,55 +87,6 @@ static SelectWs select_layout(void* base, long long V, long long F) {
   w.fmap = reinterpret_cast<unsigned*>(p + 64 + vbytes);
   w.bytes = 64 + vbytes + fbytes;
   return w;
-}
-
-__device__ __forceinline__ void mesh_error(unsigned long long* header, unsigned bit) {
-  atomicOr(reinterpret_cast<unsigned*>(header), bit);
-}
-
-// ---- exclusive scan of n 32-bit counts by ONE workgroup (every total here is below 2^31) -----------------------------
-// MARK: the input is 0 / 1 flags and the output is "index + 1" for a set flag, 0 for a clear one.  in == out is allowed.
-template <bool MARK>
-__global__ __launch_bounds__(SCAN_THREADS) void k_mesh_scan(const unsigned* in, unsigned* out, long long n,
-                                                            unsigned long long* total_a, unsigned long long* total_b) {
-  __shared__ unsigned s_wave[SCAN_THREADS / 64];
-  __shared__ unsigned s_carry;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = 0u;
-  __syncthreads();
-  for (long long start = 0; start < n; start += (long long)SCAN_THREADS * SCAN_ITEMS) {
-    const long long base = start + (long long)threadIdx.x * SCAN_ITEMS;
-    unsigned v[SCAN_ITEMS], sum = 0u;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-      v[k] = (base + k < n) ? in[base + k] : 0u;
-      sum += v[k];
-    }
-    unsigned incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned wave_off = 0u;
-    for (int q = 0; q < wave; ++q) wave_off += s_wave[q];
-    const unsigned carry = s_carry;
-    unsigned run = carry + wave_off + incl - sum;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-      if (base + k < n) out[base + k] = MARK ? (v[k] ? run + 1u : 0u) : run;
-      run += v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == SCAN_THREADS - 1) s_carry = carry + wave_off + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    if (total_a) *total_a = s_carry;
-    if (total_b) *total_b = s_carry;
-  }
 }
 
 // ---- edge incidences ----------------------------------------------------------------------------------------------------
@@ -600,8 +550,6 @@ static const char* mesh_error_text(unsigned bits) {
   return "a parent chain exceeded the face count";
 }
 
-static inline unsigned grid_for(long long n) { return (unsigned)((n + MESH_BLOCK - 1) / MESH_BLOCK); }
-
 // the header back on the host: a synchronisation of the stream
 static int read_header(const char* who, const unsigned long long* header, unsigned long long (&host)[4], hipStream_t st) {
   FNR_HIP(hipMemcpyAsync(host, header, sizeof(host), hipMemcpyDeviceToHost, st));
@@ -611,19 +559,6 @@ static int read_header(const char* who, const unsigned long long* header, unsign
     set_error("%s: %s (error word 0x%x)", who, mesh_error_text(bits), bits);
     return FNR_ERR_INVALID;
   }
-  return FNR_OK;
-}
-
-static int mesh_sizes_check(const char* who, int64_t n_vertices, int64_t n_faces) {
-  FNR_CHECK_ARG(n_vertices >= 0 && n_faces >= 0, "%s: n_vertices / n_faces < 0", who);
-  FNR_CHECK_ARG(n_vertices <= 0x7fffffffll && n_faces <= 0x7fffffffll, "%s: more than 2^31 - 1 vertices or faces", who);
-  return FNR_OK;
-}
-
-static int mesh_workspace_check(const char* who, const void* workspace, size_t workspace_bytes, size_t needed) {
-  FNR_CHECK_ARG(workspace != nullptr, "%s: null workspace", who);
-  FNR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, "%s: workspace is not 16-byte aligned", who);
-  FNR_CHECK_ARG(workspace_bytes >= needed, "%s: workspace %zu < %zu bytes", who, workspace_bytes, needed);
   return FNR_OK;
 }
 

@@ -230,7 +230,8 @@ def export_tsdf_mesh(pipeline, output_dir, downscale_factor: int = 2, depth_outp
                      rgb_output_name: str = "rgb", resolution=128, batch_size: int = 10, use_bounding_box: bool = True,
                      bounding_box_min=(-1.0, -1.0, -1.0), bounding_box_max=(1.0, 1.0, 1.0),
                      semantic_threshold: Optional[float] = None, min_component_faces: Optional[int] = None,
-                     largest_components: Optional[int] = None):
+                     largest_components: Optional[int] = None, smooth_iterations: Optional[int] = None,
+                     smooth_lambda: float = 0.5, smooth_mu: float = -0.53, simplify_voxel_size: Optional[float] = None):
     """Nerfstudio's ExportTSDFMesh.main / export_tsdf_mesh (`ns-export tsdf`; its fields as recalled): every camera of
     `pipeline.datamanager.train_dataset.cameras` is rendered at 1 / downscale_factor of its resolution (pinhole: the
     fusion does not model distortion, so the rays are generated without it), its `depth_output_name` / `rgb_output_name`
@@ -244,12 +245,19 @@ def export_tsdf_mesh(pipeline, output_dir, downscale_factor: int = 2, depth_outp
     min_component_faces / largest_components (what users of `ns-export tsdf` do next with Open3D's
     cluster_connected_triangles): the written mesh loses its connected components of fewer than min_component_faces
     faces, then keeps only its largest_components largest (export/mesh.py::TriangleMesh).  With both None the function
-    makes the calls and writes the bytes it always did.  The returned TSDF is not affected."""
+    makes the calls and writes the bytes it always did.  The returned TSDF is not affected.
+
+    smooth_iterations / smooth_lambda / smooth_mu / simplify_voxel_size (what those users do before they measure
+    anything: filter_smooth_taubin, simplify_vertex_clustering, compute_vertex_normals): after the component cleaning the
+    written mesh is Taubin-smoothed with smooth_iterations (lambda, mu) pairs, then simplified by vertex clustering on a
+    grid of simplify_voxel_size, and its normals are recomputed from its faces if either ran (_filter_mesh).  With both
+    None nothing changes."""
     tsdf = _fuse_tsdf(pipeline, downscale_factor, depth_output_name, rgb_output_name, resolution, batch_size, use_bounding_box,
                       bounding_box_min, bounding_box_max, semantic_threshold)
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
-    if min_component_faces is None and largest_components is None:
+    if min_component_faces is None and largest_components is None and smooth_iterations is None \
+            and simplify_voxel_size is None:
         tsdf.export(str(out / "tsdf_mesh.ply"))
         return tsdf
     mesh = tsdf.get_triangle_mesh()
@@ -257,8 +265,21 @@ def export_tsdf_mesh(pipeline, output_dir, downscale_factor: int = 2, depth_outp
         mesh = mesh.remove_small_components(int(min_component_faces))
     if largest_components is not None:
         mesh = mesh.keep_largest_components(int(largest_components))
+    mesh = _filter_mesh(mesh, smooth_iterations, smooth_lambda, smooth_mu, simplify_voxel_size)
     mesh.write(out / "tsdf_mesh.ply")
     return tsdf
+
+
+def _filter_mesh(mesh, smooth_iterations, smooth_lambda, smooth_mu, simplify_voxel_size):
+    """The filters of the mesh exporters, in their order: Taubin smoothing, vertex clustering, and vertex normals from the
+    faces if either ran.  With both None the mesh itself is returned."""
+    if smooth_iterations is None and simplify_voxel_size is None:
+        return mesh
+    if smooth_iterations is not None:
+        mesh = mesh.filter_smooth_taubin(int(smooth_iterations), float(smooth_lambda), float(smooth_mu))
+    if simplify_voxel_size is not None:
+        mesh = mesh.simplify_vertex_clustering(float(simplify_voxel_size))
+    return mesh.compute_vertex_normals()
 
 
 def _fuse_tsdf(pipeline, downscale_factor, depth_output_name, rgb_output_name, resolution, batch_size, use_bounding_box,
@@ -349,7 +370,8 @@ def vertex_fruit_probability(model, vertices, normals):
 
 
 def export_fruit_meshes(pipeline, output_dir, semantic_threshold: float = 0.9, min_component_faces: int = 24,
-                        **tsdf_arguments):
+                        smooth_iterations: Optional[int] = None, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
+                        simplify_voxel_size: Optional[float] = None, **tsdf_arguments):
     """One surface patch per fruit, with its size.  The whole scene is fused (export_tsdf_mesh's fusion with
     `tsdf_arguments`: downscale_factor, resolution, batch_size, the bounding box, the output names — NOT its
     semantic_threshold: masking pixels leaves their nodes unobserved, unobserved nodes count as inside, and the mesh is
@@ -358,7 +380,12 @@ def export_fruit_meshes(pipeline, output_dir, semantic_threshold: float = 0.9, m
     probability >= semantic_threshold (0.9: the reference's threshold, fruit_nerf.py:264) are kept, split into connected
     components, and the components of fewer than min_component_faces faces dropped.  Writes <output_dir>/fruit_mesh.ply
     and <output_dir>/fruits.json — one record per fruit in component order: faces, area, volume (signed; meaningful where
-    closed), closed, centroid, lo, hi — and returns a FruitMeshes."""
+    closed), closed, centroid, lo, hi — and returns a FruitMeshes.
+
+    smooth_iterations / smooth_lambda / smooth_mu / simplify_voxel_size: export_tsdf_mesh's filters, applied to the fruit
+    mesh after the small components are gone; components and statistics are those of the FILTERED mesh (clustering can
+    merge patches), so the sizes in fruits.json are sizes of the smoothed surface.  `full`, `vertex_probability` and
+    `tsdf` stay those of the unfiltered scene mesh."""
     import json
     names = ("downscale_factor", "depth_output_name", "rgb_output_name", "resolution", "batch_size", "use_bounding_box",
              "bounding_box_min", "bounding_box_max")
@@ -371,6 +398,7 @@ def export_fruit_meshes(pipeline, output_dir, semantic_threshold: float = 0.9, m
     probability = vertex_fruit_probability(pipeline.model, full.vertices, full.normals)
     fruit = full.select_by_vertex_mask(probability >= float(semantic_threshold))
     fruit = fruit.remove_small_components(int(min_component_faces))
+    fruit = _filter_mesh(fruit, smooth_iterations, smooth_lambda, smooth_mu, simplify_voxel_size)
     face_component, _ = fruit.connected_components()
     result = FruitMeshes(fruit, face_component, fruit.component_stats(), full, probability, tsdf)
     out = Path(output_dir)

@@ -1,7 +1,11 @@
 """TriangleMesh: the mesh of the TSDF export as an object, with the Open3D calls its users follow the export with —
 cluster_connected_triangles(), selection by face / vertex mask, removal of small components — as recalled (Open3D is not
 available to this project; the contract is the one stated in include/fruitnerf_hip.h, "triangle-mesh connectivity").
-Connectivity, statistics and selection run in libfruitnerf_hip.so (csrc/mesh.hip); there is no CPU path."""
+Connectivity, statistics and selection run in libfruitnerf_hip.so (csrc/mesh.hip); there is no CPU path.
+
+The filters those users call first — filter_smooth_laplacian / filter_smooth_taubin, compute_vertex_normals,
+simplify_vertex_clustering — follow the section "triangle-mesh filters" of the same header (csrc/mesh_filters.hip): every
+sum is a sequential float64 sum over a per-vertex row with a fixed order, so a filtered mesh has one defined bit pattern."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -53,6 +57,9 @@ class TriangleMesh:
         self.colors = None if colors is None else colors.contiguous()
         self._components = None      # (face_component, n_components, workspace)
         self._stats = None
+        self._adjacency = None       # (offsets, neighbours)
+        self._vertex_faces = None    # (offsets, faces)
+        self.vertex_cluster = None   # int32 [V of the source mesh]: set on the result of simplify_vertex_clustering
 
     @property
     def device(self):
@@ -121,6 +128,65 @@ class TriangleMesh:
         keep = torch.zeros_like(n, dtype=torch.bool)
         keep[order] = True
         return self._select_components(keep)
+
+    # ---- filters ----------------------------------------------------------------------------------------------------------
+    def vertex_adjacency(self) -> Tuple[Tensor, Tensor]:
+        """-> (offsets int32 [V + 1], neighbours int32 [E]): row a holds every b != a that shares a face with a, once,
+        ascending; computed once."""
+        if self._adjacency is None:
+            self._adjacency = K.mesh_vertex_rows(self.faces, self.n_vertices, K.MESH_ROWS_NEIGHBOURS)
+        return self._adjacency
+
+    def vertex_faces(self) -> Tuple[Tensor, Tensor]:
+        """-> (offsets int32 [V + 1], faces int32 [E]): row a holds every face that lists a, once, ascending; computed once."""
+        if self._vertex_faces is None:
+            self._vertex_faces = K.mesh_vertex_rows(self.faces, self.n_vertices, K.MESH_ROWS_FACES)
+        return self._vertex_faces
+
+    def _smoothed(self, factors, weights: str) -> "TriangleMesh":
+        offsets, neighbours = self.vertex_adjacency()
+        mesh = TriangleMesh(K.mesh_smooth(self.vertices, offsets, neighbours, factors, weights), self.faces, self.normals,
+                            self.colors)
+        mesh._adjacency, mesh._vertex_faces, mesh._components = self._adjacency, self._vertex_faces, self._components
+        return mesh
+
+    def filter_smooth_laplacian(self, number_of_iterations: int = 1, lambda_filter: float = 0.5,
+                                weights: str = "inverse_distance") -> "TriangleMesh":
+        """number_of_iterations steps p' = p + lambda_filter * (weighted mean of the neighbours - p); it shrinks the mesh.
+        Faces, colours and the OLD normals are kept (compute_vertex_normals refreshes them)."""
+        return self._smoothed([float(lambda_filter)] * max(int(number_of_iterations), 0), weights)
+
+    def filter_smooth_taubin(self, number_of_iterations: int = 1, lambda_filter: float = 0.5, mu: float = -0.53,
+                             weights: str = "inverse_distance") -> "TriangleMesh":
+        """number_of_iterations pairs of a lambda_filter step and a mu step (mu < -lambda_filter < 0): smooths without
+        the shrinkage of the Laplacian filter.  Faces, colours and the OLD normals are kept."""
+        return self._smoothed([float(lambda_filter), float(mu)] * max(int(number_of_iterations), 0), weights)
+
+    def compute_vertex_normals(self) -> "TriangleMesh":
+        """The mesh with area-weighted vertex normals of its faces ((0, 0, 0) for a vertex without a face of any area)."""
+        offsets, rows = self.vertex_faces()
+        mesh = TriangleMesh(self.vertices, self.faces, K.mesh_vertex_normals(self.vertices, self.faces, offsets, rows),
+                            self.colors)
+        mesh._adjacency, mesh._vertex_faces = self._adjacency, self._vertex_faces
+        mesh._components, mesh._stats = self._components, self._stats
+        return mesh
+
+    def simplify_vertex_clustering(self, voxel_size: float) -> "TriangleMesh":
+        """One vertex per occupied cell of a voxel_size grid whose origin is the minimum bound minus half a voxel: the
+        mean of the cell's vertices (and of their colours); the faces re-indexed, without those that collapse and
+        without later duplicates; the normals recomputed if the mesh had any.  The result's `vertex_cluster` int32 [V]
+        maps this mesh's vertices to its own."""
+        voxel_size = float(voxel_size)
+        origin = [0.0, 0.0, 0.0]
+        if self.n_vertices > 0:
+            origin = [x - 0.5 * voxel_size for x in self.vertices.min(dim=0).values.double().tolist()]
+        c = K.mesh_cluster(self.vertices, self.faces, voxel_size, origin)
+        mean = lambda t: None if t is None else K.mesh_rows_mean(c["offsets"], c["members"], t.float())   # noqa: E731
+        mesh = TriangleMesh(mean(self.vertices), c["new_faces"], None, mean(self.colors))
+        if self.normals is not None:
+            mesh = mesh.compute_vertex_normals()
+        mesh.vertex_cluster = c["vertex_cluster"]
+        return mesh
 
     def write(self, path) -> None:
         """Binary PLY through ply.write_triangle_mesh (missing normals / colours are written as zeros)."""

@@ -1056,6 +1056,93 @@ int fnr_mesh_select_emit(int64_t n_vertices, int64_t n_faces, const int32_t* fac
                          size_t workspace_bytes, int64_t n_new_vertices, int64_t n_new_faces, int32_t* new_faces,
                          int32_t* vertex_ids, int32_t* face_ids, void* stream);
 
+/* ---- triangle-mesh filters: vertex rows, smoothing, normals, vertex clustering (csrc/mesh_filters.hip) ---- */
+/* What users of a mesh do with Open3D before they look at connectivity and sizes — filter_smooth_laplacian(),
+ * filter_smooth_taubin(), compute_vertex_normals(), simplify_vertex_clustering() — as recalled; Open3D is not available to
+ * this project, so THIS text is the contract (tests/mesh_filters_reference.py restates it in float64, and the device
+ * arrays equal the restatement's bit for bit).  Pure additions to ABI 13.  The mesh, the error word and the host-side
+ * argument checks are those of the connectivity section; V == 0 and F == 0 are valid everywhere and launch no kernel.
+ *
+ * The primitive is the per-vertex ROW with a fixed order: offsets int32 [V + 1] (offsets[0] = 0, ascending, offsets[V] =
+ * E) and entries int32 [E]; row a is entries[offsets[a] .. offsets[a + 1]).  Every floating-point sum below is the
+ * sequential float64 sum of a row's terms in row order, starting from 0.0, every product, difference, quotient and square
+ * root rounded once (no fused multiply-add, no floating-point atomics): a result has one defined bit pattern.
+ *
+ * Vertex rows (fnr_mesh_vertex_rows_count / _emit; 6 n_faces <= 2^31 - 1).  No vertex array is read.
+ *   kind = FNR_MESH_ROWS_NEIGHBOURS: row a holds every b != a that shares a face with a, each once, ascending.  A face
+ *     that repeats an index still connects its distinct indices; the rows are symmetric, and they are the same arrays
+ *     for any order of the faces.
+ *   kind = FNR_MESH_ROWS_FACES: row a holds every face that lists a, each once, ascending.
+ *   _count writes counts[0] (DEVICE uint64) = E and leaves the sorted keys in `workspace` (>=
+ *   fnr_mesh_vertex_rows_workspace_bytes bytes, 16-byte aligned); the caller reads E, allocates, and calls _emit with the
+ *   SAME workspace, sizes and kind: offsets [V + 1], entries [E].
+ *   How.  One 64-bit key (row << 32) | entry per ordered pair of a face's slots (NEIGHBOURS, six a face) or per slot
+ *   (FACES, three a face); a stable least-significant-digit radix sort (count -> one-workgroup scan -> ordered emit per
+ *   8-bit digit) over only the bytes V and F need; the first copy of every key with row != entry is marked, the marks are
+ *   scanned, and offsets[r] is the scan at the first sorted key of a row >= r (a bounded binary search).
+ *
+ * Smoothing (fnr_mesh_smooth; rows of kind NEIGHBOURS).  Positions are converted to float64 once, kept in float64 across
+ * the n_steps steps (two buffers in `workspace`, >= fnr_mesh_smooth_workspace_bytes bytes; one launch per step) and rounded
+ * to fp32 once at the end.  Step s, for a vertex p with a non-empty row, over its neighbours n in row order:
+ *     w_n = 1 (FNR_MESH_WEIGHTS_UNIFORM) or 1 / (sqrt((dx*dx + dy*dy) + dz*dz) + 1e-12), d = p - p_n
+ *           (FNR_MESH_WEIGHTS_INVERSE_DISTANCE);
+ *     S += w_n * p_n per axis, W += w_n;   p' = p + factors[s] * (S / W - p).
+ * A vertex with an empty row keeps its position.  factors is a HOST array of n_steps doubles: Laplacian smoothing is
+ * [lambda] * n, Taubin smoothing [lambda, mu] * n (mu < -lambda < 0).  n_steps == 0 copies the positions.  out may not
+ * alias vertices.
+ *
+ * Vertex normals (fnr_mesh_vertex_normals; rows of kind FACES).  The face term is (v1 - v0) x (v2 - v0) in float64, not
+ * normalised (area weighting); the vertex sum n runs over the row in row order; normals = n / sqrt((nx*nx + ny*ny) +
+ * nz*nz) rounded to fp32, and (0, 0, 0) where that square is not positive.  workspace: >= 64 bytes.
+ *
+ * Vertex clustering (fnr_mesh_cluster_count / _emit).  voxel_size is a positive double, origin a HOST pointer to three
+ * finite doubles.  The cell of a vertex per axis is floor((double(v) - origin) / voxel_size); a non-finite coordinate, a
+ * negative cell and a cell >= 2^21 are refused.  (Open3D's simplify_vertex_clustering puts the origin at the minimum
+ * bound minus half a voxel; the caller does.)  A cluster is the set of ALL vertices of one cell, referenced or not;
+ * clusters are numbered by the rank of their smallest member among all clusters' smallest members: cluster 0 holds
+ * vertex 0.  _count writes vertex_cluster [V] and counts[2] (DEVICE uint64) = number of clusters V', number of kept faces
+ * F', and leaves its tables in `workspace` (>= fnr_mesh_cluster_workspace_bytes bytes); _emit, with the SAME workspace,
+ * sizes and faces, writes the cluster rows — offsets [V' + 1], members [V] ascending inside a cluster — and new_faces
+ * [F'][3] with face_ids [F']: the faces re-indexed by cluster, in their old order and with their old rotation, without
+ *   - a face with two equal new indices, and
+ *   - a later duplicate of a kept face: two faces are duplicates iff their new triples are equal after rotating each to
+ *     start at its smallest index.  The same triangle with the opposite winding is therefore NOT a duplicate.
+ *   How.  Vertices sorted by cell key (the same stable sort, so a cell's vertices ascend and its first is its smallest),
+ *   runs numbered by a scan; faces sorted by their rotated triple (equal triples ascend by face), the first of a run kept.
+ *
+ * Row mean (fnr_mesh_rows_mean): out[r] = float64 sum of values[m] [3] over row r's members m in row order, divided by the
+ * member count, rounded to fp32; (0, 0, 0) for an empty row.  values is fp32 [n_values][3].  workspace: >= 64 bytes.  The
+ * clustered positions, colours and normals are row means over the cluster rows.
+ *
+ * Errors.  As in the connectivity section; besides a bad face index, rows that are not rows (offsets that do not ascend
+ * within [0, n_entries], an entry outside its array) and a vertex outside the cells are found on the device and refused. */
+#define FNR_MESH_ROWS_NEIGHBOURS 0
+#define FNR_MESH_ROWS_FACES 1
+#define FNR_MESH_WEIGHTS_UNIFORM 0
+#define FNR_MESH_WEIGHTS_INVERSE_DISTANCE 1
+size_t fnr_mesh_vertex_rows_workspace_bytes(int64_t n_vertices, int64_t n_faces, int32_t kind);
+int fnr_mesh_vertex_rows_count(int64_t n_vertices, int64_t n_faces, const int32_t* faces, int32_t kind, uint64_t* counts,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int fnr_mesh_vertex_rows_emit(int64_t n_vertices, int64_t n_faces, int32_t kind, const void* workspace,
+                              size_t workspace_bytes, int64_t n_entries, int32_t* offsets, int32_t* entries, void* stream);
+size_t fnr_mesh_smooth_workspace_bytes(int64_t n_vertices);
+int fnr_mesh_smooth(int64_t n_vertices, const float* vertices, int64_t n_entries, const int32_t* offsets,
+                    const int32_t* neighbours, int32_t n_steps, const double* factors, int32_t weights, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int fnr_mesh_vertex_normals(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                            int64_t n_entries, const int32_t* offsets, const int32_t* face_rows, float* normals,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t fnr_mesh_cluster_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int fnr_mesh_cluster_count(int64_t n_vertices, int64_t n_faces, const float* vertices, const int32_t* faces,
+                           double voxel_size, const double* origin, int32_t* vertex_cluster, uint64_t* counts,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int fnr_mesh_cluster_emit(int64_t n_vertices, int64_t n_faces, const int32_t* faces, void* workspace,
+                          size_t workspace_bytes, int64_t n_clusters, int64_t n_new_faces, int32_t* offsets,
+                          int32_t* members, int32_t* new_faces, int32_t* face_ids, void* stream);
+int fnr_mesh_rows_mean(int64_t n_rows, int64_t n_entries, const int32_t* offsets, const int32_t* members,
+                       int64_t n_values, const float* values, float* out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* ---- point-cloud front-end of the counting stage ---------------------------------------------- */
 /* FruitClustering.cluster (clustering/clustering_base.py:183-207) runs, on the exported cloud, Open3D's
  * remove_radius_outlier (:141-143), Open3D's voxel_down_sample (:138-139) and sklearn.cluster.DBSCAN (:199-200).
