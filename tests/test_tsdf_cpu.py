@@ -244,6 +244,258 @@ def test_reference_smooth_field_reaches_every_case():
     assert len(tr.oriented_faces(mesh["face_keys"])) == mesh["faces"].shape[0]
 
 
+# ---- the array reference and the fixtures of the large-volume GPU tests -----------------------------------------------
+_SMALL = {"field": (tr.smooth_field, tr.FIELD_LO, tr.FIELD_HI),
+          "sphere": (tr.sphere_volume, tr.SPHERE_LO, tr.SPHERE_HI),
+          "zeros": (tr.zeros_volume, tr.FIELD_LO, tr.FIELD_HI),
+          "checker": (tr.checkerboard, tr.CHECKER_LO, tr.CHECKER_HI),
+          "checker_tie": (lambda: tr.checkerboard(magnitude=0.5), tr.CHECKER_LO, tr.CHECKER_HI),
+          "noise": (tr.noise_volume, tr.CHECKER_LO, tr.CHECKER_HI)}
+_small_cache = {}
+
+
+def _small(name):
+    """(values, colors, lo, hi, extract_fast's mesh) of a small fixture, computed once."""
+    if name not in _small_cache:
+        make, lo, hi = _SMALL[name]
+        values, colors = make()
+        _small_cache[name] = (values, colors, lo, hi, tr.extract_fast(values, colors, lo, hi))
+    return _small_cache[name]
+
+
+def _ulps64(a, b):
+    """|a - b| in units of the float64 spacing at max(|a|, |b|, smallest normal)."""
+    return np.abs(a - b) / np.spacing(np.maximum(np.maximum(np.abs(a), np.abs(b)), np.finfo(np.float64).tiny))
+
+
+@pytest.mark.parametrize("name", sorted(_SMALL))
+def test_extract_fast_equals_extract(name):
+    """What lets the GPU tests trust extract_fast where extract cannot run: integers, positions and colours equal exactly,
+    normals within 4 ulp of float64 (the norm is taken differently)."""
+    values, colors, lo, hi, fast = _small(name)
+    slow = tr.extract(values, colors, lo, hi)
+    assert fast["keys"].size > 0 and fast["faces"].shape[0] > 0
+    for k in ("keys", "faces", "face_keys"):
+        assert fast[k].dtype == slow[k].dtype == np.int64 and np.array_equal(fast[k], slow[k]), k
+    for k in ("vertices", "colors"):
+        assert fast[k].dtype == np.float64 and np.array_equal(fast[k], slow[k]), k
+    assert fast["cases"] == slow["cases"]
+    worst = float(_ulps64(fast["normals"], slow["normals"]).max())
+    print(f"[extract_fast {name}] V {fast['keys'].size} F {fast['faces'].shape[0]}; normals differ by {worst:.1f} ulp64")
+    assert worst <= 4.0
+    assert np.array_equal(fast["normals"] == 0, slow["normals"] == 0)
+    # no exclusions: the unnormalised normal is non-zero on every vertex, except where the tie checkerboard makes it so
+    cond = tr.normal_condition(values, lo, hi)
+    assert cond.shape == (fast["keys"].size,) and bool((cond[np.isfinite(cond)] >= 1.0).all())
+    if name != "checker_tie":
+        assert bool(np.isfinite(cond).all())
+
+
+@pytest.mark.parametrize("dims", [d for d in tr.SCAN_DIMS if d != (128, 128, 128)])
+def test_scan_volumes_span_the_trips_of_the_block_scan(dims):
+    blocks, trips = tr.SCAN_DIMS[dims]
+    values, colors = tr.scan_volume(dims)
+    assert values.dtype == colors.dtype == np.float32 and values.shape == dims and not bool((values == 0).any())
+    assert -(-values.size // 256) == blocks and -(-blocks // tr.SCAN_BLOCKS_PER_TRIP) == trips
+    if dims == (45, 343, 17):
+        assert blocks % tr.SCAN_BLOCKS_PER_TRIP == 1 and values.size % 256 == 251
+    if dims == (64, 64, 64):
+        assert blocks == tr.SCAN_BLOCKS_PER_TRIP and values.size % 256 == 0
+    # colours are not constant: not over the nodes, not over the channels
+    flat = colors.reshape(-1, 3)
+    assert float(flat.std(0).min()) > 0.1
+    assert float((flat[:, 0] != flat[:, 1]).mean()) > 0.99 and float((flat[:, 1] != flat[:, 2]).mean()) > 0.99
+    assert float((flat[1:] != flat[:-1]).any(1).mean()) > 0.99
+    mesh = tr.extract_fast(values, colors, tr.SCAN_LO, tr.SCAN_HI)
+    owners = np.unique(tr.block_of_key(mesh["keys"]))
+    print(f"[scan {dims}] {blocks} blocks, {trips} trips; V {mesh['keys'].size} F {mesh['faces'].shape[0]}; "
+          f"{owners.size} blocks own a vertex")
+    assert 0.9 * blocks < owners.size < blocks                   # nearly every block offset is used, and some count zero
+    assert int(owners.max()) // tr.SCAN_BLOCKS_PER_TRIP == trips - 1          # the last trip owns vertices too
+    assert mesh["cases"] == set(range(16))
+    assert bool(np.isfinite(tr.normal_condition(values, tr.SCAN_LO, tr.SCAN_HI)).all())
+    expected = {(64, 64, 64): (82059, 161066, 1011), (45, 343, 17): (117089, 226716, 1002),
+                (81, 81, 81): (132397, 260932, 2012)}[dims]
+    assert (mesh["keys"].size, mesh["faces"].shape[0], owners.size) == expected
+
+
+def test_checkerboard_fills_the_packed_word():
+    """4 owned edges per interior node (direction codes 1, 2, 4, 7) and 12 faces per cell: the face prefix inside a block
+    passes 2048, the top of the 13-bit field."""
+    values, colors, lo, hi, mesh = _small("checker")
+    n = tr.CHECKER_DIMS[0]
+    assert float(np.abs(values).min()) >= 0.25 and float(np.abs(values).max()) <= 1.0 and np.unique(np.abs(values)).size > 1000
+    assert mesh["faces"].shape[0] == 12 * (n - 1) ** 3 == 40500
+    assert mesh["keys"].size == 14895
+    owned = np.bincount(mesh["keys"] // 8, minlength=values.size).reshape(values.shape)
+    assert bool((owned[:-1, :-1, :-1] == 4).all())
+    assert set((mesh["keys"][np.isin(mesh["keys"] // 8, np.arange(values.size).reshape(values.shape)[:-1, :-1, :-1])] % 8)
+               .tolist()) == {1, 2, 4, 7}
+    prefix = tr.face_prefix_in_block(values)
+    vertex_prefix = (np.cumsum(owned.reshape(-1, 256), axis=1) - owned.reshape(-1, 256))
+    print(f"[checkerboard] largest face prefix in a block {int(prefix.max())}, largest vertex prefix {int(vertex_prefix.max())}")
+    assert int(prefix.max()) > 2048 and int(prefix.max()) < 1 << 13 and int(vertex_prefix.max()) < 1 << 11
+
+
+def test_tie_checkerboard_has_ties_and_zero_normals():
+    values, colors, lo, hi, mesh = _small("checker_tie")
+    assert bool((np.abs(values) == 0.5).all())
+    a, b, m = tr.active_edges(values)
+    assert a.size == mesh["keys"].size == 14895
+    flat = colors.reshape(-1, 3).astype(np.float64)
+    assert np.array_equal(mesh["colors"], flat[a]) and int((flat[a] != flat[b]).any(1).sum()) == a.size   # a tie goes to a
+    P = tr.node_positions(lo, hi, values.shape).reshape(-1, 3)
+    assert np.array_equal(mesh["vertices"], P[a] + 0.5 * (P[b] - P[a]))
+    # an edge whose endpoints are interior on all three axes: both central differences are 0 - 0, the normal is (0, 0, 0);
+    # an edge that touches the border has a one-sided, non-zero gradient
+    ijk = lambda n: np.stack(np.unravel_index(n, values.shape), axis=1)                                  # noqa: E731
+    interior = lambda n: ((ijk(n) > 0) & (ijk(n) < np.array(values.shape) - 1)).all(1)                   # noqa: E731
+    both = interior(a) & interior(b)
+    zero = (mesh["normals"] == 0).all(1)
+    print(f"[tie checkerboard] {int(zero.sum())} zero normals, {int((~zero).sum())} others of {a.size}")
+    assert bool(zero[both].all()) and int(both.sum()) > 1000 and int((~zero).sum()) > 1000
+    assert bool((~both[~zero]).all())
+    assert np.allclose(np.linalg.norm(mesh["normals"][~zero], axis=1), 1.0, atol=1e-12)
+
+
+def test_noise_volume_reaches_every_cell_pattern():
+    values, colors, lo, hi, mesh = _small("noise")
+    inside = values < 0
+    n = tr.CHECKER_DIMS[0]
+    pattern = sum(inside[(c & 1):n - 1 + (c & 1), ((c >> 1) & 1):n - 1 + ((c >> 1) & 1), (c >> 2):n - 1 + (c >> 2)]
+                  .astype(np.int64) << c for c in range(8))
+    assert np.unique(pattern).size == 256
+    assert float(np.abs(values).min()) >= 0.25 and mesh["cases"] == set(range(16))
+
+
+def test_zeros_volume_puts_vertices_on_nodes():
+    values, colors, lo, hi, mesh = _small("zeros")
+    plain, _ = tr.smooth_field()
+    flat = values.reshape(-1)
+    positive, negative = (flat == 0) & ~np.signbit(flat), (flat == 0) & np.signbit(flat)
+    assert int(positive.sum()) == int(negative.sum()) == round(0.05 * flat.size) and np.array_equal(colors, tr.smooth_field()[1])
+    assert np.array_equal(flat[flat != 0], plain.reshape(-1)[flat != 0])
+    a, b, m = tr.active_edges(values)
+    t, _, _ = tr.normal_terms(values, lo, hi)
+    va, vb = flat[a].astype(np.float64), flat[b].astype(np.float64)
+    assert not bool((va == vb).any())                            # +0 and -0 are both outside: never an active edge
+    for name, at_zero in (("+0.0", positive), ("-0.0", negative)):
+        assert int(((t == 0) & at_zero[a]).sum()) > 0, f"no active edge leaves a node of {name}"
+        assert int(((t == 1) & at_zero[b]).sum()) > 0, f"no active edge ends on a node of {name}"
+    assert np.array_equal(t == 0, va == 0) and np.array_equal(t == 1, vb == 0)
+    # a vertex with t = 0 or 1 lies on its node, and several edges meet there
+    P = tr.node_positions(lo, hi, values.shape).reshape(-1, 3)
+    on = np.where(t == 0, a, b)[(t == 0) | (t == 1)]
+    assert np.array_equal(mesh["vertices"][(t == 0) | (t == 1)], P[on])
+    assert int(np.bincount(on).max()) > 1
+    assert np.array_equal(mesh["colors"][(t == 0) | (t == 1)], colors.reshape(-1, 3).astype(np.float64)[on])
+
+
+def test_normal_yardstick_of_the_float32_evaluation():
+    """The yardstick of the GPU normal test: the normal's formulas in float32 NumPy against extract_fast, as the worst of
+    |error| / (eps32 cond) over the fixtures (cond = |S| / |n|, tr.normal_condition).  Measured: 0.51 to 0.67 per fixture
+    (0.05 on the tie checkerboard, whose arithmetic is nearly exact), with cond up to 308 on the checkerboard; the kernel
+    is granted 4 x the worst over the GPU module's fixtures."""
+    worst = {}
+    cases = [(name,) + _small(name)[:4] + (_small(name)[4]["normals"],) for name in sorted(_SMALL)]
+    for dims in tr.SCAN_DIMS:
+        if dims != (128, 128, 128):
+            values, colors = tr.scan_volume(dims)
+            cases.append((f"scan {dims}", values, colors, tr.SCAN_LO, tr.SCAN_HI,
+                          tr.extract_fast(values, colors, tr.SCAN_LO, tr.SCAN_HI)["normals"]))
+    for name, values, colors, lo, hi, normals in cases:
+        cond = tr.normal_condition(values, lo, hi)
+        got = tr.normals_float32(values, lo, hi)
+        assert got.dtype == np.float32 and got.shape == normals.shape
+        worst[name] = tr.normal_ratio(got, normals, cond)
+        assert np.array_equal((got == 0).all(1), ~np.isfinite(cond))         # zero exactly where the reference is zero
+        print(f"[normal yardstick {name}] float32 on the CPU: worst |error| / (eps32 cond) {worst[name]:.3f}; "
+              f"largest cond {float(cond[np.isfinite(cond)].max()):.3g}; worst |error| "
+              f"{float(np.abs(got - normals).max()):.3g}")
+    print(f"[normal yardstick] worst over the fixtures {max(worst.values()):.3f}")
+    # a float32 evaluation of a dozen operations whose error the condition number accounts for: a few eps32, not more
+    assert 0.1 < max(worst.values()) < 4.0
+
+
+def test_fusion_special_depths_reach_nodes():
+    """NaN, +inf, negative, -0.0 and 1e-30 in camera 0's depth: nodes project onto each kind; +inf gives a valid sample
+    with s = 1, the others give none; the nodes that may be left out stay under 1 %."""
+    fx = tr.fusion_fixture()
+    special, pixels = tr.fusion_special_depths(fx)
+    assert set(pixels) == set(tr.SPECIAL_DEPTHS) and all(len(set(p)) == 4 for p in pixels.values())
+    assert len({rc for p in pixels.values() for rc in p}) == 20
+    n_nodes = int(np.prod(tr.FUSION_DIMS))
+    _, inside, row, col = tr.project(tr.FUSION_LO, tr.FUSION_HI, tr.FUSION_DIMS, fx["c2w"][0], fx["intrinsics"][0],
+                                     tr.FUSION_H, tr.FUSION_W)
+    for kind in (0, 1):
+        key = "depth_ray" if kind else "depth_z"
+        changed = special[key] != fx[key]
+        assert int(changed.sum()) == 20 and not bool(changed[1:].any())          # the old depths there are positive
+        for name, value in tr.SPECIAL_DEPTHS.items():
+            for r, c in pixels[name]:
+                got = special[key][0, r, c]
+                assert (np.isnan(got) if name == "nan" else got == value and np.signbit(got) == np.signbit(value))
+        args = (tr.FUSION_LO, tr.FUSION_HI, fx["c2w"][:1], fx["intrinsics"][:1])
+        (values, weights, _), near = tr.integrate(tr.empty_volume(tr.FUSION_DIMS), *args, special[key][:1], fx["rgb"][:1],
+                                                  depth_kind=kind, max_weight=1e9)
+        (_, before, _), _ = tr.integrate(tr.empty_volume(tr.FUSION_DIMS), *args, fx[key][:1], fx["rgb"][:1],
+                                         depth_kind=kind, max_weight=1e9)
+        for name in tr.SPECIAL_DEPTHS:
+            on = np.zeros(tr.FUSION_DIMS, dtype=bool)
+            for r, c in pixels[name]:
+                on |= inside & (row == r) & (col == c)
+            assert int(on.sum()) >= 4, f"{name}: no node projects there"
+            if name == "inf":
+                assert bool((weights[on] == 1.0).all()) and bool((values[on] == 1.0).all())
+            else:
+                assert bool((weights[on] == 0.0).all()) and bool((values[on] == -1.0).all())
+                assert int((before[on] == 1.0).sum()) > 0 or name == "tiny"      # the pixel took a sample away
+        for max_weight in (1.0, 1e9):
+            for mask in (None, fx["mask"]):
+                (values, weights, colors), near = tr.integrate(
+                    tr.empty_volume(tr.FUSION_DIMS), tr.FUSION_LO, tr.FUSION_HI, fx["c2w"], fx["intrinsics"], special[key],
+                    fx["rgb"], mask, depth_kind=kind, max_weight=max_weight)
+                assert int(near.sum()) <= 0.01 * n_nodes
+                assert bool(np.isfinite(values).all()) and bool(np.isfinite(colors).all()) and bool(np.isfinite(weights).all())
+
+
+@pytest.mark.parametrize("max_weight", [2.0, 2.5])
+def test_fusion_max_weight_between_one_and_the_cameras(max_weight):
+    """With three cameras the clamp binds on the third only: a node seen twice has weight 2, a node seen three times has
+    max_weight, and its value is the average that the clamped weight gives."""
+    fx = tr.fusion_fixture()
+    args = (tr.FUSION_LO, tr.FUSION_HI, fx["c2w"], fx["intrinsics"], fx["depth_ray"], fx["rgb"])
+    (values, weights, _), near = tr.integrate(tr.empty_volume(tr.FUSION_DIMS), *args, max_weight=max_weight)
+    (plain, seen, _), _ = tr.integrate(tr.empty_volume(tr.FUSION_DIMS), *args, max_weight=1e9)
+    assert float(weights.max()) == max_weight and int(near.sum()) <= 0.01 * near.size
+    assert int((seen == 2).sum()) > 0 and bool((weights[seen == 2] == 2.0).all())
+    assert int((seen == 3).sum()) > 0 and bool((weights[seen == 3] == max_weight).all())
+    assert np.array_equal(values, plain)          # the clamp acts after the last camera: nothing is averaged with it
+    (two, w2, _), _ = tr.integrate(tr.empty_volume(tr.FUSION_DIMS), tr.FUSION_LO, tr.FUSION_HI, fx["c2w"][:2],
+                                   fx["intrinsics"][:2], fx["depth_ray"][:2], fx["rgb"][:2], max_weight=max_weight)
+    assert float(w2.max()) == 2.0 and int((w2 == 2.0).sum()) > 0
+
+
+def test_fusion_translated_scene_stays_clear_of_ties():
+    """The scene moved by (100, -200, 300): the bound grows with the coordinate, the share of nodes near a tie does not."""
+    fx = tr.fusion_fixture()
+    moved, lo, hi = tr.fusion_translated(fx, tr.FUSION_OFFSET)
+    assert lo == (99.0, -201.0, 299.0) and hi == (101.0, -199.0, 301.0)
+    assert np.array_equal(moved["c2w"][:, :, :3], fx["c2w"][:, :, :3])
+    assert float(np.abs(moved["c2w"][:, :, 3].astype(np.float64) - fx["c2w"][:, :, 3] - np.array(tr.FUSION_OFFSET)).max()) \
+        <= 0.5 * tr.EPS32 * 512
+    for kind in (0, 1):
+        for max_weight in (1.0, 1e9):
+            for mask in (None, fx["mask"]):
+                (values, weights, _), near = tr.integrate(
+                    tr.empty_volume(tr.FUSION_DIMS), lo, hi, moved["c2w"], moved["intrinsics"],
+                    moved["depth_ray" if kind else "depth_z"], moved["rgb"], mask, depth_kind=kind, max_weight=max_weight)
+                assert int(near.sum()) <= 0.01 * near.size
+                assert float(weights.max()) == (1.0 if max_weight == 1.0 else 3.0) and 0 < int((values < 0).sum()) < near.size
+    bound = tr.fusion_bound(lo, hi, tr.FUSION_DIMS, moved["c2w"])
+    assert 90 < bound / tr.fusion_bound(tr.FUSION_LO, tr.FUSION_HI, tr.FUSION_DIMS, fx["c2w"]) < 110
+
+
 def test_reference_fusion_fixture_stays_clear_of_ties():
     """The fixture of the GPU comparison: every situation the issue names occurs, and the nodes that may be left out (near
     a rounding tie or a validity edge, in float64) stay under 1 % of the volume in every configuration."""
